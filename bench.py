@@ -40,10 +40,18 @@ Other workloads / modes (BASELINE configs 2 and 5, the reference's own bench cir
   --workload complex-circuit  tests/golden/complex-circuit-10000-10000.r1cs (benches/groth16.rs:87-108)
   --mode parts              witness map and each MSM timed separately (device-resident operands)
 
-Rank 0 prints ONE JSON line: metric/value/unit/... plus `roofline` (dominant kernel, live HIP-event
-timing on the kernel's own stream), `cpu_baseline` (the oracle's multithreaded C restatement of the
-reference's CPU prover timed on this box's host cores on the SAME inputs when it fits the time
-bound) and `parity`.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline
+(metric/value/unit/higher_is_better/dtype/ms_per_step, the config); nothing else touches the GPU or
+the host cores.  --full adds every other leg after the timed region: `roofline` (dominant kernel,
+live HIP-event timing on the kernel's own stream, HBM traffic from two rocprofv3 --pmc passes),
+`alu`, `clock`, the PCIe-inclusive and two-in-flight legs, `parts_ms` (--mode parts),
+`cpu_baseline` (the oracle's multithreaded C restatement of the reference's CPU prover timed on
+this box's host cores on the SAME inputs when it fits the time bound), `parity` and `secondary`.
+
+--dump-outputs DIR writes the proof of the last timed step -- what a caller of the timed path
+receives -- as DIR/proof_{a,b,c}.npy: its packed bytes (Montgomery little-endian affine
+coordinates; a and c (2, 32) = x, y; b (4, 32) = x.c0, x.c1, y.c0, y.c1) as float64.  The inputs
+are seeded by --log2 / --workload alone, so two builds compare output for output.
 """
 import argparse
 import json
@@ -599,7 +607,7 @@ def secondary_lines(args):
     out = {}
 
     def child(name, extra, pick, timeout):
-        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--no-pmc", "--no-secondary"] + extra
+        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--full", "--no-pmc", "--no-secondary"] + extra
         env = dict(os.environ)
         env["G16_BENCH_NO_PIPELINE"] = "1"
         t0 = time.time()
@@ -637,6 +645,14 @@ def secondary_lines(args):
                      "verifies": d["parity"]["proof_verifies"], "bytes_equal": bytes_equal(d, 20),
                      "cpu_constraints_per_s": (d.get("cpu_baseline") or {}).get("value")}, 300)
     return out
+
+
+def dump_proof(dirname, proof):
+    """--dump-outputs: the proof's 256 packed bytes as float64 (exact), one file per group element."""
+    os.makedirs(dirname, exist_ok=True)
+    raw = np.frombuffer(proof.raw, dtype=np.uint8).astype(np.float64)
+    for name, lo, hi, shape in (("a", 0, 64, (2, 32)), ("b", 64, 192, (4, 32)), ("c", 192, 256, (2, 32))):
+        np.save(os.path.join(dirname, f"proof_{name}.npy"), raw[lo:hi].reshape(shape))
 
 
 class ClockSampler:
@@ -820,7 +836,14 @@ def main():
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the `secondary` block of the default N = 1 line (BASELINE configs[1] and configs[4], one child run each)")
+    ap.add_argument("--full", action="store_true",
+                    help="every leg beyond the headline: roofline / PMC traffic, alu, clock, PCIe-inclusive and two-in-flight "
+                         "legs, parts_ms, cpu_baseline, parity, secondary")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's proof to DIR/proof_{a,b,c}.npy (its bytes as float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     rank = int(os.environ.get("RANK", "0"))
@@ -998,9 +1021,9 @@ def main():
         for _ in range(args.warmup):
             if active:
                 proof = step()
-        if active:
+        if active and args.full:               # stage spans feed roofline / stages_ms_per_step
             prover.set_profiling(True)
-        sampler = ClockSampler(local_rank if active else None) if rank == 0 else None
+        sampler = ClockSampler(local_rank if active else None) if rank == 0 and args.full else None
         barrier()
         if active:
             torch.cuda.synchronize()
@@ -1085,9 +1108,61 @@ def main():
                 both_vals["value_is"] = "in-library"
             else:
                 both_vals["value_is"] = "rccl"
+    info = prover.info()
+    ms_per_step = elapsed / args.steps * 1e3
+    if mode == "single":
+        par = "single-gpu"
+    else:
+        cut = ("msm-bucket-range-shard (A/B1/B2/L points on every GPU, 1/N of the sorted bucket list per rank; H by point range)"
+               if info.get("shard_mode") == "buckets" else "msm-point-range-shard")
+        par = (f"{cut} x{n_gpus} + four-step witness map (2 all-to-all), "
+               + ("one g16_ctx_create_multi ctx in one process: peer copies over xGMI inside the library"
+                  if mode == "inlib" else "one process per GPU: RCCL all_to_all / all_gather, event hand-offs"))
+        if both_vals and both_vals.get("value_inlib"):
+            par = (f"{cut} x{n_gpus} + four-step witness map (2 all-to-all); BOTH launch shapes timed: one g16_ctx_create_multi "
+                   "ctx in one process (peer copies over xGMI inside the library) and one process per GPU (RCCL all_to_all / "
+                   f"all_gather, event hand-offs); `value` = the faster ({both_vals['value_is']})")
+        if fallback_reason:
+            par += " [fallback: the in-library ctx failed on this node]"
+        if one_gpu:
+            par += " [functional run: every rank on ONE GPU]"
+    line = {
+        "metric": "Groth16 constraints/sec (BN254)", "value": m * args.steps / elapsed,
+        "unit": "constraints/s", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "higher_is_better": True,
+        "scaling": "strong", "vs_baseline": None, "dtype": "int32x9 (29-bit limbs of 254-bit Montgomery integers)",
+        "data": "synthetic",
+        "config": {"workload": f"{desc}, BN254, full prove (witness map + 4 G1 MSM + 1 G2 MSM + finalize), "
+                               "trapdoor key minted on GPU",
+                   "log2_domain": k, "num_constraints": m, "n_vars": n_vars,
+                   "witness_fraction_in_{0,1}": round(frac01, 4),
+                   "parallelism": par, "msm": info},
+        "setup_s": t_setup,
+        "library": lib_path,
+    }
+    if both_vals:
+        line.update(both_vals)
+    elif n_gpus > 1:
+        line["rccl_ranks"] = st["rccl_ranks"]
+    if fallback_reason:
+        line["fallback_reason"] = fallback_reason
+    if args.dump_outputs:
+        dump_proof(args.dump_outputs, proof)
+
+    def finish():
+        print(json.dumps(line), flush=True)
+        if zkey_path and os.path.exists(zkey_path):
+            os.remove(zkey_path)
+        if dist:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:
+        finish()
+        return
+
     stages = prover.stage_times()
     prover.set_profiling(False)
-    info = prover.info()
 
     # ---- the SURVEY 8(d) step: host witness (page-locked staging buffer of the ctx) -> H2D -> proof
     host_ms = None
@@ -1447,79 +1522,39 @@ def main():
            "alu_only_ceiling_mixed_additions_per_s": 16.7e9,
            "by_kernel": {x["kernel"]: x["vmad_frac_of_issue_peak"] for x in kerns}}
 
-    ms_per_step = elapsed / args.steps * 1e3
-    if mode == "single":
-        par = "single-gpu"
-    else:
-        cut = ("msm-bucket-range-shard (A/B1/B2/L points on every GPU, 1/N of the sorted bucket list per rank; H by point range)"
-               if info.get("shard_mode") == "buckets" else "msm-point-range-shard")
-        par = (f"{cut} x{n_gpus} + four-step witness map (2 all-to-all), "
-               + ("one g16_ctx_create_multi ctx in one process: peer copies over xGMI inside the library"
-                  if mode == "inlib" else "one process per GPU: RCCL all_to_all / all_gather, event hand-offs"))
-        if both_vals and both_vals.get("value_inlib"):
-            par = (f"{cut} x{n_gpus} + four-step witness map (2 all-to-all); BOTH launch shapes timed: one g16_ctx_create_multi "
-                   "ctx in one process (peer copies over xGMI inside the library) and one process per GPU (RCCL all_to_all / "
-                   f"all_gather, event hand-offs); `value` = the faster ({both_vals['value_is']})")
-        if fallback_reason:
-            par += " [fallback: the in-library ctx failed on this node]"
-        if one_gpu:
-            par += " [functional run: every rank on ONE GPU]"
-    out = {
-        "metric": "Groth16 constraints/sec (BN254)", "value": m * args.steps / elapsed,
-        "unit": "constraints/s", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_per_step, "higher_is_better": True,
-        "scaling": "strong", "vs_baseline": None, "dtype": "int32x9 (29-bit limbs of 254-bit Montgomery integers)",
-        "data": "synthetic",
-        "config": {"workload": f"{desc}, BN254, full prove (witness map + 4 G1 MSM + 1 G2 MSM + finalize), "
-                               "trapdoor key minted on GPU",
-                   "log2_domain": k, "num_constraints": m, "n_vars": n_vars,
-                   "witness_fraction_in_{0,1}": round(frac01, 4),
-                   "parallelism": par, "msm": info},
+    line.update({
         "roofline": roofline, "alu": alu, "cpu_baseline": cpu, "parity": parity,
         "stages_ms_per_step": {n: ms / args.steps for n, (ms, _c) in stages.items()},
-        "setup_s": t_setup,
         "value_pcie_inclusive": (m / (host_ms * 1e-3)) if host_ms else None,
         "ms_per_step_pcie_inclusive": host_ms,
         "pcie_inclusive_note": "SURVEY 8(d) step: witness in the ctx's page-locked host buffer -> H2D -> ... "
                                "-> 256 B D2H; `value` keeps the witness resident in HBM (bench contract)",
-        "library": lib_path,
-    }
+    })
     if (n_gpus == 1 and args.mode == "prove" and args.workload == "chain" and k == 22 and not args.no_secondary
             and not os.environ.get("G16_AMD_LIB")):
-        out["secondary"] = secondary_lines(args)
-    if both_vals:
-        out.update(both_vals)
-    elif n_gpus > 1:
-        out["rccl_ranks"] = st["rccl_ranks"]
+        line["secondary"] = secondary_lines(args)
     if clock:
-        out["clock_mhz"] = clock["timed"]["sclk_mhz_median"] or clock["after"]["sclk_mhz_median"]
-        out["power_w"] = clock["timed"]["power_w_median"] or clock["after"]["power_w_median"]
-        out["clock"] = clock
+        line["clock_mhz"] = clock["timed"]["sclk_mhz_median"] or clock["after"]["sclk_mhz_median"]
+        line["power_w"] = clock["timed"]["power_w_median"] or clock["after"]["power_w_median"]
+        line["clock"] = clock
     if pipelined:
-        out["value_pipelined"] = pipelined
-    if fallback_reason:
-        out["fallback_reason"] = fallback_reason
+        line["value_pipelined"] = pipelined
     if parts:
-        out["parts_ms"] = parts
+        line["parts_ms"] = parts
     if cpu:
         # a prove() caller hands over a HOST witness: the ratio that compares like with like is the
         # PCIe-inclusive step over the CPU restatement; the resident-witness ratio beside it
-        if out["value_pcie_inclusive"]:
-            out["gpu_over_cpu"] = out["value_pcie_inclusive"] / cpu["value"]
-            out["gpu_over_cpu_note"] = ("PCIe-inclusive GPU step (host witness -> proof) / CPU restatement, the CPU side on "
+        if line["value_pcie_inclusive"]:
+            line["gpu_over_cpu"] = line["value_pcie_inclusive"] / cpu["value"]
+            line["gpu_over_cpu_note"] = ("PCIe-inclusive GPU step (host witness -> proof) / CPU restatement, the CPU side on "
                                         f"{cpu['cores']} threads with MSMs {cpu['msm_parallelism']} threads wide; a baseline, not a kernel-quality figure")
-        out["gpu_resident_over_cpu"] = out["value"] / cpu["value"]
+        line["gpu_resident_over_cpu"] = line["value"] / cpu["value"]
         if cpu.get("value_all_cores"):
             best = max(cpu["value"], cpu["value_all_cores"])
-            out["gpu_over_cpu_all_cores"] = (out["value_pcie_inclusive"] or out["value"]) / best
-            out["gpu_over_cpu_all_cores_note"] = ("the same ratio against the FASTER CPU figure (chunk-parallel MSMs on every "
+            line["gpu_over_cpu_all_cores"] = (line["value_pcie_inclusive"] or line["value"]) / best
+            line["gpu_over_cpu_all_cores_note"] = ("the same ratio against the FASTER CPU figure (chunk-parallel MSMs on every "
                                                   "host thread): the conservative bound")
-    print(json.dumps(out), flush=True)
-    if zkey_path and os.path.exists(zkey_path):
-        os.remove(zkey_path)
-    if dist:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

@@ -8,7 +8,7 @@ for rep in $(seq 1 ${REPS:-2}); do
   i=0
   for knobs in "$@"; do
     i=$((i+1)); [ "$knobs" = "-" ] && knobs=""
-    env $knobs G16_BENCH_NO_PIPELINE=1 python bench.py $ARGS --cpu-log2 0 > $O/ab_${i}_$rep.json 2> $O/ab_${i}_$rep.err
+    env $knobs G16_BENCH_NO_PIPELINE=1 python bench.py --full $ARGS --cpu-log2 0 > $O/ab_${i}_$rep.json 2> $O/ab_${i}_$rep.err
     python - $O/ab_${i}_$rep.json "$knobs" <<'PY'
 import json, sys
 try:

@@ -74,10 +74,10 @@ echo "== 2. bench.py in-library, N = 1, 2, 4, 8"
 for N in 1 2 4 8; do
   [ "$N" -gt "$NDEV" ] && break
   if [ "$N" -eq 1 ]; then
-    python bench.py --gpus 1 --log2 $K --steps $STEPS --warmup 2 --cpu-log2 0 --no-pmc --no-secondary > $O/inlib_$N.json 2> $O/inlib_$N.err
+    python bench.py --gpus 1 --log2 $K --steps $STEPS --warmup 2 --full --cpu-log2 0 --no-pmc --no-secondary > $O/inlib_$N.json 2> $O/inlib_$N.err
   else
     G16_BENCH_MODE=inlib python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29600+N)) \
-      bench.py --gpus $N --log2 $K --steps $STEPS --warmup 2 --cpu-log2 0 > $O/inlib_$N.json 2> $O/inlib_$N.err
+      bench.py --gpus $N --log2 $K --steps $STEPS --warmup 2 --full --cpu-log2 0 > $O/inlib_$N.json 2> $O/inlib_$N.err
   fi
   tail -1 $O/inlib_$N.json | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('inlib N=%d' % d['n_gpus'], round(d['ms_per_step'],2), 'ms', d['parity'], d['config'].get('parallelism'))"
 done
@@ -85,7 +85,7 @@ echo "== 3. bench.py one process per GPU over RCCL, N = 2, 4, 8"
 for N in 2 4 8; do
   [ "$N" -gt "$NDEV" ] && break
   NCCL_DEBUG=INFO NCCL_DEBUG_SUBSYS=INIT G16_BENCH_MODE=ranks python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 \
-    --master-port $((29700+N)) bench.py --gpus $N --log2 $K --steps $STEPS --warmup 2 --cpu-log2 0 > $O/ranks_$N.json 2> $O/ranks_$N.err
+    --master-port $((29700+N)) bench.py --gpus $N --log2 $K --steps $STEPS --warmup 2 --full --cpu-log2 0 > $O/ranks_$N.json 2> $O/ranks_$N.err
   echo "RCCL: $(grep -c 'Init COMPLETE' $O/ranks_$N.err) rank(s) report Init COMPLETE; $(grep -m1 -o 'nranks [0-9]*' $O/ranks_$N.err)"
   tail -1 $O/ranks_$N.json | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('ranks N=%d' % d['n_gpus'], round(d['ms_per_step'],2), 'ms', d['parity'], d['config'].get('parallelism'))"
 done
