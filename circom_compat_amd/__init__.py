@@ -512,6 +512,67 @@ class Prover:
                                               C.c_void_p(w_dev_ptr), self.n_vars, _np_ptr(out)), self.ctx)
         return Proof(out.tobytes())
 
+    def _batch_rs(self, rs):
+        rs = list(rs)
+        if not rs:
+            return np.zeros((0, 4), dtype=np.uint64), np.zeros((0, 4), dtype=np.uint64)
+        if all(isinstance(v, np.ndarray) for pair in rs for v in pair):
+            r = np.ascontiguousarray(np.stack([np.asarray(p[0], dtype=np.uint64).reshape(4) for p in rs]))
+            s = np.ascontiguousarray(np.stack([np.asarray(p[1], dtype=np.uint64).reshape(4) for p in rs]))
+            return r, s
+        both = _as_fr([v for pair in rs for v in pair], self.lib).reshape(len(rs), 2, 4)
+        return np.ascontiguousarray(both[:, 0]), np.ascontiguousarray(both[:, 1])
+
+    def _batch_witnesses(self, witnesses) -> np.ndarray:
+        if isinstance(witnesses, np.ndarray) and witnesses.dtype == np.uint64:
+            w = np.ascontiguousarray(witnesses)
+            if w.ndim != 3 or w.shape[2] != 4:
+                raise G16Error(B.G16_ERR_INVALID, "witnesses: a (count, n_vars, 4) uint64 array")
+            return w
+        ws = [_as_fr(x, self.lib) for x in witnesses]
+        if not ws:
+            return np.zeros((0, self.n_vars, 4), dtype=np.uint64)
+        if any(x.shape != ws[0].shape for x in ws):
+            raise G16Error(B.G16_ERR_INVALID, "witnesses: assignments of different lengths")
+        return np.ascontiguousarray(np.stack(ws))
+
+    def prove_batch(self, rs, witnesses) -> List[Proof]:
+        """proofs of many witnesses under this key (g16_prove_batch): rs = sequence of (r, s), witnesses =
+        sequence of full assignments or a (count, n_vars, 4) uint64 Montgomery array.  Proof i equals
+        prove(*rs[i], witnesses[i]) byte for byte."""
+        r, s = self._batch_rs(rs)
+        w = self._batch_witnesses(witnesses)
+        if w.shape[0] != r.shape[0]:
+            raise G16Error(B.G16_ERR_INVALID, f"{r.shape[0]} (r, s) pairs for {w.shape[0]} witnesses")
+        count = r.shape[0]
+        out = np.empty(max(count, 1) * B.G16_PROOF_BYTES, dtype=np.uint8)
+        self.lib.check(self.lib.g16_prove_batch(self.ctx, count, _np_ptr(r), _np_ptr(s), _np_ptr(w), w.shape[1],
+                                                _np_ptr(out)), self.ctx)
+        raw = out.tobytes()
+        return [Proof(raw[i * B.G16_PROOF_BYTES:(i + 1) * B.G16_PROOF_BYTES]) for i in range(count)]
+
+    def prove_batch_dev(self, rs, w_dev_ptr: int, count: int) -> List[Proof]:
+        """witnesses already resident in HBM: device pointer to count x n_vars x 32 bytes, contiguous"""
+        r, s = self._batch_rs(rs)
+        if r.shape[0] != count:
+            raise G16Error(B.G16_ERR_INVALID, f"{r.shape[0]} (r, s) pairs for {count} witnesses")
+        if count == 0:
+            return []
+        out = np.empty(count * B.G16_PROOF_BYTES, dtype=np.uint8)
+        self.lib.check(self.lib.g16_prove_batch_dev(self.ctx, count, _np_ptr(r), _np_ptr(s), C.c_void_p(w_dev_ptr),
+                                                    self.n_vars, _np_ptr(out)), self.ctx)
+        raw = out.tobytes()
+        return [Proof(raw[i * B.G16_PROOF_BYTES:(i + 1) * B.G16_PROOF_BYTES]) for i in range(count)]
+
+    def witness_map_batch(self, witnesses) -> np.ndarray:
+        """witness_map for many assignments in one pass: (count, domain_size, 4) uint64 Montgomery"""
+        w = self._batch_witnesses(witnesses)
+        h = np.empty((w.shape[0], self.domain_size, 4), dtype=np.uint64)
+        if w.shape[0]:
+            self.lib.check(self.lib.g16_witness_map_batch(self.ctx, w.shape[0], _np_ptr(w), w.shape[1], _np_ptr(h)),
+                           self.ctx)
+        return h
+
     def prove_partial(self, r, s, full_assignment=None, w_dev_ptr: Optional[int] = None) -> bytes:
         """this rank's G16_PARTIAL_BYTES record: its A, B1, B2, L, H sums and s*A, r*B1"""
         rs = _as_fr([r, s], self.lib) if not isinstance(r, np.ndarray) else np.stack([r, s])

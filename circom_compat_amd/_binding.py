@@ -104,6 +104,7 @@ ABI_SYMBOLS = [
     "g16_r1cs_open_mem", "g16_r1cs_close", "g16_r1cs_header_get", "g16_r1cs_matrices",
     "g16_r1cs_wire_mapping", "g16_wtns_read", "g16_wtns_read_mem", "g16_free",
     "g16_fr_from_canonical", "g16_fr_to_canonical",
+    "g16_prove_batch", "g16_prove_batch_dev", "g16_witness_map_batch",
 ]
 
 
@@ -141,6 +142,9 @@ class Library:
             "g16_msm_g2": (C.c_int, [vp, vp, C.c_size_t, vp]),
             "g16_prove": (C.c_int, [vp, vp, vp, vp, C.c_size_t, vp]),
             "g16_prove_dev": (C.c_int, [vp, vp, vp, vp, C.c_size_t, vp]),
+            "g16_prove_batch": (C.c_int, [vp, C.c_size_t, vp, vp, vp, C.c_size_t, vp]),
+            "g16_prove_batch_dev": (C.c_int, [vp, C.c_size_t, vp, vp, vp, C.c_size_t, vp]),
+            "g16_witness_map_batch": (C.c_int, [vp, C.c_size_t, vp, C.c_size_t, vp]),
             "g16_prove_partial": (C.c_int, [vp, vp, vp, vp, C.c_size_t, vp]),
             "g16_prove_partial_dev": (C.c_int, [vp, vp, vp, vp, C.c_size_t, vp]),
             "g16_prove_finish": (C.c_int, [vp, vp, vp, vp, C.c_int, vp]),

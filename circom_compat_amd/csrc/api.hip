@@ -367,55 +367,83 @@ namespace g16 {
 
 void rank_collect_times(g16_ctx* c) { collect_times(c); }
 
-// Small keys: the same proof through the fixed-base tables (msm_table.h).  Main stream: the five
-// witness-scalar G1 sums (A, B1, L, s A, r B1); aux: witness map -> H; red: B2; side: the (r, s)-only
-// fixed-base sums; then the finalisation the sharded provers use (no variable-base product left).
-static void enqueue_prove_tables(g16_ctx* c, const Fr* w_dev) {
+// The buffers of a chunk of table-path proofs: the ctx's own for g16_prove (count = 1), the batch workspace's
+// (g16_ctx::BatchWs) for g16_prove_batch.  Proof z: witness w + z w_stride, (r, s) rs[2 z] (uploaded from
+// rs_host + 64 z), its XYZZ record at proj + z FIN_PROJ_BYTES (copied to proj_host).
+struct TabChunk {
+  uint32_t count;
+  const Fr* w;
+  uint32_t w_stride;
+  Fr* rs;
+  const uint8_t* rs_host;
+  int32_t *abc, *spmv;
+  U256* h;
+  ProofSums* sums;
+  FinScratch* scr;
+  G1XYZZ29 *part1, *partH;
+  G2XYZZ29* part2;
+  uint8_t *proj, *proj_host;
+};
+
+// Small keys: `count` proofs through the fixed-base tables (msm_table.h), every stage one launch for the
+// whole chunk.  Main stream: the five witness-scalar G1 sums (A, B1, L, s A, r B1); aux: B2; red: witness
+// map -> H; side: the (r, s)-only fixed-base sums; then the finalisation the sharded provers use (no
+// variable-base product left).  g16_prove is the count = 1 case.
+static void enqueue_prove_tables(g16_ctx* c, const TabChunk& ch) {
   hipStream_t s = c->stream;
   // q carries the G2 sum -- the longest dependent chain of the proof (Fq2 additions) -- on the ctx's
   // HIGH-priority stream (aux), so that its workgroups are placed before the G1 launches' when the chip
   // is full; the witness map -> H chain takes the red stream here
   hipStream_t x = c->overlap ? c->red : s, q = c->overlap ? c->aux : s, sd = c->overlap ? c->side : s;
   StageTimer* tm = c->timer.enabled ? &c->timer : nullptr;
-  ProofSums* S = c->sums_dev.p;
-  G16_HIP(hipMemcpyAsync(c->rs_dev.p, c->pin_io, 64, hipMemcpyHostToDevice, s));
+  const uint32_t n = ch.count;
+  G16_HIP(hipMemcpyAsync(ch.rs, ch.rs_host, (size_t)64 * n, hipMemcpyHostToDevice, s));
   G16_HIP(hipEventRecord(c->ev_start, s));  // (r, s) and the witness are resident
   // the G2 sum first
   G16_HIP(hipStreamWaitEvent(q, c->ev_start, 0));
   int id = tm ? tm->begin(ST_MSM_TABLE_G2, q) : -1;
-  c->tbl.run_g2_witness(w_dev + 1, S, q);
+  c->tbl.run_g2_witness(ch.w + 1, ch.w_stride, ch.sums, ch.part2, n, q);
   if (tm) tm->end(id, q);
   // witness map, then the H sum
   G16_HIP(hipStreamWaitEvent(x, c->ev_start, 0));
   id = tm ? tm->begin(ST_WITNESS_MAP, x) : -1;
-  c->wm.run(w_dev, c->h_canon.p, nullptr, x);
+  c->wm.run_batch(ch.w, ch.w_stride, n, ch.abc, ch.spmv, ch.h, nullptr, x);
   if (tm) tm->end(id, x);
   id = tm ? tm->begin(ST_MSM_TABLE_G1, x) : -1;
-  c->tbl.run_h(c->h_canon.p, S, x);
+  c->tbl.run_h(ch.h, c->wm.n, ch.sums, ch.partH, n, x);
   if (tm) tm->end(id, x);
   G16_HIP(hipEventRecord(c->ev_h, x));
   // side: the (r, s)-only fixed-base sums and what can be added up front
   G16_HIP(hipStreamWaitEvent(sd, c->ev_start, 0));
-  fin_fixed_dist(c->fin_tab.p, c->rs_dev.p, c->fin_scr.p, sd);
-  fin_tab_pre(c->key_dev.p, c->fin_scr.p, sd);
+  fin_fixed_dist(c->fin_tab.p, ch.rs, ch.scr, sd, n);
+  fin_tab_pre(c->key_dev.p, ch.scr, sd, n);
   G16_HIP(hipEventRecord(c->ev_fixed, sd));
   // behind the G2 sum: B = b' + MSM_B2
   G16_HIP(hipStreamWaitEvent(q, c->ev_fixed, 0));
-  fin_tab_b(S, c->fin_scr.p, c->part_dev(), q);
+  fin_tab_b(ch.sums, ch.scr, ch.proj, q, n);
   G16_HIP(hipEventRecord(c->ev_b2, q));
   // main: the five witness-scalar G1 sums, A, the H-free part of C; then C behind the H sum
   id = tm ? tm->begin(ST_MSM_TABLE_G1, s) : -1;
-  c->tbl.run_g1_witness(w_dev + 1, c->rs_dev.p, S, s);
+  c->tbl.run_g1_witness(ch.w + 1, ch.w_stride, ch.rs, ch.sums, ch.part1, n, s);
   if (tm) tm->end(id, s);
   G16_HIP(hipStreamWaitEvent(s, c->ev_fixed, 0));
   id = tm ? tm->begin(ST_FINALIZE, s) : -1;
-  fin_tab_ac(S, c->fin_scr.p, c->part_dev(), s);
+  fin_tab_ac(ch.sums, ch.scr, ch.proj, s, n);
   G16_HIP(hipStreamWaitEvent(s, c->ev_h, 0));
-  fin_tab_c(S, c->fin_scr.p, c->part_dev(), s);
+  fin_tab_c(ch.sums, ch.scr, ch.proj, s, n);
   if (tm) tm->end(id, s);
   G16_HIP(hipStreamWaitEvent(s, c->ev_b2, 0));
-  // A, B, C in XYZZ form (the partial-record slot of out_dev is free on a world = 1 ctx); proof_from_pin() divides
-  G16_HIP(hipMemcpyAsync(c->pin_io + 64 + G16_PROOF_BYTES, c->part_dev(), FIN_PROJ_BYTES, hipMemcpyDeviceToHost, s));
+  // A, B, C in XYZZ form; the host divides (fin_tab_host_affine[_batch])
+  G16_HIP(hipMemcpyAsync(ch.proj_host, ch.proj, (size_t)FIN_PROJ_BYTES * n, hipMemcpyDeviceToHost, s));
+}
+
+// g16_prove's chunk: one proof in the ctx's own buffers (the partial-record slot of out_dev is free on a
+// world = 1 ctx and takes the XYZZ record)
+static void enqueue_prove_tables(g16_ctx* c, const Fr* w_dev) {
+  const TabChunk ch{1,           w_dev,          c->N,          c->rs_dev.p,   c->pin_io,
+                    c->wm.abc.p, c->wm.spmv.partial.p, c->h_canon.p, c->sums_dev.p, c->fin_scr.p,
+                    c->tbl.part1.p, c->tbl.partH.p, c->tbl.part2.p, c->part_dev(), c->pin_io + 64 + G16_PROOF_BYTES};
+  enqueue_prove_tables(c, ch);
 }
 
 // after the main stream is synchronised: the proof bytes of the last enqueue_prove
@@ -916,6 +944,7 @@ g16_status g16_ctx_create_sibling(g16_ctx* donor, const g16_key_desc* key, const
 // repeat a device ordinal) is not freed under its borrowers: the handle dies for the caller, the state
 // stays until the last borrower is destroyed (round 5; rounds 3-4 printed a warning and freed anyway).
 static std::mutex g_lend_mu;
+static void batch_release(g16_ctx* c);  // the batch workspace (below)
 
 void g16_ctx_destroy(g16_ctx* c) {
   if (!c) return;
@@ -977,6 +1006,7 @@ void g16_ctx_destroy(g16_ctx* c) {
   if (c->ev_user) (void)hipEventDestroy(c->ev_user);
   if (c->pinned_w) (void)hipHostFree(c->pinned_w);
   if (c->pin_io) (void)hipHostFree(c->pin_io);
+  batch_release(c);
   delete c;
 }
 
@@ -1337,6 +1367,158 @@ g16_status g16_multi_links(const g16_ctx* c, float* gbps, float* echo_us, int ca
 void* g16_witness_buffer(g16_ctx* c) {
   if (c && c->multi) c = multi_child(c, 0);
   return c ? (void*)c->w_dev.p : nullptr;
+}
+
+// ---- batches: many witnesses under one key --------------------------------------------------------
+// Chunk rule: the largest B whose workspace (batch_bytes_per_proof x B) fits a quarter of the device memory
+// free at the call, at most G16_BATCH_CAP, at least 1; a larger count loops over chunks.
+static constexpr uint32_t G16_BATCH_CAP = 256;
+
+static size_t batch_bytes_per_proof(const g16_ctx* c) {
+  size_t b = (size_t)c->N * sizeof(Fr) + 2 * sizeof(Fr) + sizeof(ProofSums) + sizeof(FinScratch) + FIN_PROJ_BYTES;
+  b += c->wm.batch_bytes_per_witness();
+  if (c->tbl.active) b += c->tbl.batch_bytes_per_proof();
+  return b;
+}
+
+static uint32_t batch_chunk(const g16_ctx* c, size_t count) {
+  size_t fr = 0, tot = 0;
+  G16_HIP(hipMemGetInfo(&fr, &tot));
+  const size_t fit = fr / 4 / batch_bytes_per_proof(c);
+  return (uint32_t)std::max<size_t>(1, std::min<size_t>({fit, (size_t)G16_BATCH_CAP, count}));
+}
+
+static void batch_release(g16_ctx* c) {
+  auto& b = c->bw;
+  b.w.release(); b.rs.release(); b.abc.release(); b.spmv.release(); b.h.release();
+  b.sums.release(); b.scr.release(); b.part1.release(); b.partH.release(); b.part2.release(); b.proj.release();
+  if (b.pin) (void)hipHostFree(b.pin);
+  b.pin = nullptr;
+  b.cap = 0;
+}
+
+// the workspace for chunks of up to B proofs (the ctx's streams are idle between calls)
+static void batch_reserve(g16_ctx* c, uint32_t B) {
+  auto& b = c->bw;
+  if (b.cap >= B) return;
+  batch_release(c);
+  b.w.alloc((size_t)B * c->N);
+  b.rs.alloc((size_t)B * 2);
+  b.abc.alloc((size_t)B * 3 * NTT29_LIMBS * c->wm.n);
+  b.spmv.alloc((size_t)B * c->wm.spmv.n_tasks * 9);
+  b.h.alloc((size_t)B * c->wm.n);
+  b.sums.alloc(B);
+  b.scr.alloc(B);
+  if (c->tbl.active) {
+    b.part1.alloc((size_t)B * c->tbl.part1_len());
+    b.partH.alloc((size_t)B * c->tbl.blocks_h);
+    b.part2.alloc((size_t)B * c->tbl.blocks_w2);
+  }
+  b.proj.alloc((size_t)B * FIN_PROJ_BYTES);
+  G16_HIP(hipHostMalloc((void**)&b.pin, (size_t)B * (64 + FIN_PROJ_BYTES), 0));
+  G16_HIP(hipMemsetAsync(b.sums.p, 0, b.sums.bytes(), c->stream));  // all sums = infinity (as sums_dev)
+  G16_HIP(hipMemsetAsync(b.scr.p, 0, b.scr.bytes(), c->stream));
+  b.cap = B;
+}
+
+// count proofs; w: host (count x N x 4 u64) or device (w_on_device: count x N x 32 bytes) witnesses
+static g16_status prove_batch(g16_ctx* c, size_t count, const uint64_t* r, const uint64_t* s_, const void* w,
+                              bool w_on_device, size_t n_vars, uint8_t* proofs_out) {
+  if (!c) return fail(c, G16_ERR_INVALID, "null argument");
+  if (count == 0) return G16_OK;
+  if (!r || !s_ || !w || !proofs_out) return fail(c, G16_ERR_INVALID, "null argument");
+  if (check_w(c, n_vars) != G16_OK) return G16_ERR_INVALID;
+  const size_t wb = (size_t)c->N * 32;  // bytes of one witness
+  if (c->multi) {  // no batched kernels across devices: one sharded proof after the other
+    for (size_t i = 0; i < count; ++i) {
+      const void* wi = (const uint8_t*)w + i * wb;
+      const g16_status st = multi_prove(c, r + 4 * i, s_ + 4 * i, wi, w_on_device, proofs_out + i * G16_PROOF_BYTES);
+      if (st != G16_OK) return st;
+    }
+    return G16_OK;
+  }
+  if (!c->has_key) return fail(c, G16_ERR_INVALID, "witness-map-only ctx has no resident key");
+  if (c->world != 1) return fail(c, G16_ERR_INVALID, "g16_prove needs world == 1; use partial/finish");
+  if (c->dist_wm) return fail(c, G16_ERR_INVALID, "dist_wm ctx: use the g16_prove_dist_phase* calls");
+  return guarded(c, [&]() -> g16_status {
+    hipStream_t s = c->stream;
+    if (!c->tbl.active) {
+      // bucket path: the single-proof enqueue once per proof (a correct fallback, not a faster one)
+      for (size_t i = 0; i < count; ++i) {
+        const Fr* wi = (const Fr*)((const uint8_t*)w + i * wb);
+        if (!w_on_device) {
+          G16_HIP(hipMemcpyAsync(c->w_dev.p, wi, wb, hipMemcpyHostToDevice, s));
+          wi = c->w_dev.p;
+        }
+        memcpy(c->pin_io, r + 4 * i, 32);
+        memcpy(c->pin_io + 32, s_ + 4 * i, 32);
+        enqueue_prove(c, wi);
+        G16_HIP(hipStreamSynchronize(s));
+        proof_from_pin(c, proofs_out + i * G16_PROOF_BYTES);
+      }
+      collect_times(c);
+      return G16_OK;
+    }
+    const uint32_t B = batch_chunk(c, count);
+    batch_reserve(c, B);
+    auto& bw = c->bw;
+    uint8_t* rs_host = bw.pin;
+    uint8_t* proj_host = bw.pin + (size_t)bw.cap * 64;
+    for (size_t done = 0; done < count; done += B) {
+      const uint32_t n = (uint32_t)std::min<size_t>(B, count - done);
+      for (uint32_t z = 0; z < n; ++z) {
+        memcpy(rs_host + 64 * (size_t)z, r + 4 * (done + z), 32);
+        memcpy(rs_host + 64 * (size_t)z + 32, s_ + 4 * (done + z), 32);
+      }
+      const Fr* wz = (const Fr*)((const uint8_t*)w + done * wb);
+      if (!w_on_device) {
+        G16_HIP(hipMemcpyAsync(bw.w.p, wz, (size_t)n * wb, hipMemcpyHostToDevice, s));
+        wz = bw.w.p;
+      }
+      const TabChunk ch{n,         wz,        c->N,       bw.rs.p,    rs_host,    bw.abc.p,  bw.spmv.p, bw.h.p,
+                        bw.sums.p, bw.scr.p,  bw.part1.p, bw.partH.p, bw.part2.p, bw.proj.p, proj_host};
+      enqueue_prove_tables(c, ch);
+      G16_HIP(hipStreamSynchronize(s));
+      fin_tab_host_affine_batch(proj_host, n, proofs_out + done * G16_PROOF_BYTES);
+    }
+    collect_times(c);
+    return G16_OK;
+  });
+}
+
+g16_status g16_prove_batch(g16_ctx* c, size_t count, const uint64_t* r, const uint64_t* s_, const uint64_t* w,
+                           size_t n_vars, uint8_t* proofs_out) {
+  return prove_batch(c, count, r, s_, w, /*w_on_device=*/false, n_vars, proofs_out);
+}
+
+g16_status g16_prove_batch_dev(g16_ctx* c, size_t count, const uint64_t* r, const uint64_t* s_, const void* w_dev,
+                               size_t n_vars, uint8_t* proofs_out) {
+  return prove_batch(c, count, r, s_, w_dev, /*w_on_device=*/true, n_vars, proofs_out);
+}
+
+g16_status g16_witness_map_batch(g16_ctx* c, size_t count, const uint64_t* w, size_t n_vars, uint64_t* h_out) {
+  if (!c) return fail(c, G16_ERR_INVALID, "null argument");
+  if (count == 0) return G16_OK;
+  if (!w || !h_out) return fail(c, G16_ERR_INVALID, "null argument");
+  if (c->multi) return fail(c, G16_ERR_INVALID, "multi-device ctx proves only (g16_prove)");
+  if (c->dist_wm) return fail(c, G16_ERR_INVALID, "dist_wm ctx holds 1/world of the witness map");
+  if (check_w(c, n_vars) != G16_OK) return G16_ERR_INVALID;
+  return guarded(c, [&]() -> g16_status {
+    hipStream_t s = c->stream;
+    const uint32_t B = batch_chunk(c, count);
+    batch_reserve(c, B);
+    auto& bw = c->bw;
+    const size_t wn = (size_t)c->N * 4, hn = (size_t)c->n * 4;  // u64 words of one witness / one h
+    for (size_t done = 0; done < count; done += B) {
+      const uint32_t n = (uint32_t)std::min<size_t>(B, count - done);
+      G16_HIP(hipMemcpyAsync(bw.w.p, w + done * wn, (size_t)n * wn * 8, hipMemcpyHostToDevice, s));
+      // h in the storage form, in the workspace's h planes (32 bytes an element, like the canonical form)
+      c->wm.run_batch(bw.w.p, c->N, n, bw.abc.p, bw.spmv.p, nullptr, reinterpret_cast<Fr*>(bw.h.p), s);
+      G16_HIP(hipMemcpyAsync(h_out + done * hn, bw.h.p, (size_t)n * hn * 8, hipMemcpyDeviceToHost, s));
+      G16_HIP(hipStreamSynchronize(s));
+    }
+    return G16_OK;
+  });
 }
 
 g16_status g16_witness_upload(g16_ctx* c, const uint64_t* w, size_t n_vars) {

@@ -91,6 +91,21 @@ struct g16_ctx {
   void* pinned_w = nullptr;      // g16_witness_host_buffer: page-locked staging for the witness
   uint8_t* pin_io = nullptr;     // page-locked (r, s) [64 B] | proof [256 B] of g16_prove_dev
 
+  // g16_prove_batch / g16_witness_map_batch: per-proof copies of everything a proof writes, for up to `cap`
+  // proofs in one pass (allocated at the first batch call, grown when a larger chunk is needed)
+  struct BatchWs {
+    uint32_t cap = 0;
+    g16::DevBuf<g16::Fr> w, rs;       // [cap][N] witness staging, [cap][2] (r, s)
+    g16::DevBuf<int32_t> abc, spmv;   // [cap][3][9][n] planes, [cap][n_tasks][9] SpMV task partials
+    g16::DevBuf<g16::U256> h;         // [cap][n] h_canon (or h in the storage form: g16_witness_map_batch)
+    g16::DevBuf<g16::ProofSums> sums;
+    g16::DevBuf<g16::FinScratch> scr;
+    g16::DevBuf<g16::G1XYZZ29> part1, partH;  // [cap][5 blocks_w], [cap][blocks_h]
+    g16::DevBuf<g16::G2XYZZ29> part2;         // [cap][blocks_w2]
+    g16::DevBuf<uint8_t> proj;                // [cap][FIN_PROJ_BYTES]
+    uint8_t* pin = nullptr;                   // page-locked: [cap][64] (r, s) | [cap][FIN_PROJ_BYTES] records
+  } bw;
+
   g16::StageTimer timer;
   float st_ms[g16::ST_COUNT] = {0};
   uint32_t st_cnt[g16::ST_COUNT] = {0};

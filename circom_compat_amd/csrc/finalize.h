@@ -71,7 +71,8 @@ void fin_host_affine_c(const uint8_t* proj_host, uint8_t* proof_out);
 // which leaves only fixed-base products (table tree-sums) and three affine conversions after the
 // all-gather.
 void fin_partial_var(ProofSums* sums, const Fr* rs_dev, hipStream_t stream);  // sA, rB1 from A, B1
-void fin_fixed_dist(const FinTables* tab, const Fr* rs_dev, FinScratch* scr, hipStream_t stream);
+// count > 1: (r, s) of proof z at rs_dev + 2 z -> scr[z] (one launch)
+void fin_fixed_dist(const FinTables* tab, const Fr* rs_dev, FinScratch* scr, hipStream_t stream, uint32_t count = 1);
 void fin_final_dist(const KeyHeaderDev* key, const ProofSums* sums, const FinScratch* scr,
                     uint8_t* proof_dev, hipStream_t stream);
 // ---- small keys through fixed-base tables (msm_table.h): the same equations in stages, each enqueued
@@ -84,11 +85,14 @@ void fin_final_dist(const KeyHeaderDev* key, const ProofSums* sums, const FinScr
 // divides (fin_tab_host_affine: three field inversions by binary Euclid, ~5 us each on a CPU core against
 // 150-250 us on one GPU lane; the host waits for these bytes anyway).  Same field elements, same bytes.
 constexpr int FIN_PROJ_A = 0, FIN_PROJ_B = 128, FIN_PROJ_C = 384, FIN_PROJ_BYTES = 512;
-void fin_tab_pre(const KeyHeaderDev* key, FinScratch* scr, hipStream_t stream);
-void fin_tab_ac(const ProofSums* sums, FinScratch* scr, uint8_t* proj_dev, hipStream_t stream);
-void fin_tab_c(const ProofSums* sums, const FinScratch* scr, uint8_t* proj_dev, hipStream_t stream);
-void fin_tab_b(const ProofSums* sums, const FinScratch* scr, uint8_t* proj_dev, hipStream_t stream);
+// count > 1: one launch for proofs z < count: sums[z], scr[z], proj_dev + z FIN_PROJ_BYTES
+void fin_tab_pre(const KeyHeaderDev* key, FinScratch* scr, hipStream_t stream, uint32_t count = 1);
+void fin_tab_ac(const ProofSums* sums, FinScratch* scr, uint8_t* proj_dev, hipStream_t stream, uint32_t count = 1);
+void fin_tab_c(const ProofSums* sums, const FinScratch* scr, uint8_t* proj_dev, hipStream_t stream, uint32_t count = 1);
+void fin_tab_b(const ProofSums* sums, const FinScratch* scr, uint8_t* proj_dev, hipStream_t stream, uint32_t count = 1);
 void fin_tab_host_affine(const uint8_t* proj_host, uint8_t* proof_out);  // host: FIN_PROJ_BYTES -> 256 proof bytes
+// host: count records -> count x 256 proof bytes with one field inversion for the whole batch (same bytes)
+void fin_tab_host_affine_batch(const uint8_t* proj_host, size_t count, uint8_t* proofs_out);
 constexpr int FIN_PARTIAL_BYTES = 1024;  // A | B1 | B2 | L | H | sA | rB1 in XYZZ storage form (G1 128 B, G2 256 B)
 // ProofSums -> one rank's record (projective: no inversion before the all-gather)
 void sums_to_partial(const ProofSums* sums, uint8_t* partial_dev, hipStream_t stream);

@@ -3,6 +3,8 @@
 // the zkey point encoding of reference src/zkey.rs:340-360) only when written to the proof.
 #include "finalize.h"
 
+#include <vector>
+
 namespace g16 {
 
 namespace {
@@ -294,9 +296,12 @@ __global__ void __launch_bounds__(64) k_fin_partial_var(ProofSums* sums, const F
 }
 
 // blocks 0..2: k * delta1 (k = r, s, rs); 3: s * delta2; 4: s * (a0 + alpha1); 5: r * (b1_0 + beta1)
+// grid.y = proof z of a batch: (r, s) = rs[2 z], rs[2 z + 1] -> scr[z]
 __global__ void __launch_bounds__(FIN_T) k_fin_fixed_dist(const FinTables* tab, const Fr* rs,
                                                           FinScratch* scr) {
   G16_DYN_SMEM(smem_raw);
+  rs += 2 * blockIdx.y;
+  scr += blockIdx.y;
   const int t = threadIdx.x;
   const Fr r = rs[0], s = rs[1];
   const int b = blockIdx.x;
@@ -355,8 +360,10 @@ __global__ void __launch_bounds__(64) k_fin_final_dist(const KeyHeaderDev* key, 
 // affine conversion follow the last sum of each proof element ------------------------------------------
 // after fin_fixed_dist (side stream).  block 0: a' = r delta1 + a0 + alpha1 -> scr->sga;
 // block 1: b' = s delta2 + b2_0 + beta2 -> scr->sd2 (in place)
+// (every k_fin_tab_* kernel: grid.y = proof z of a batch -- sums[z], scr[z], proj + z FIN_PROJ_BYTES)
 __global__ void __launch_bounds__(64) k_fin_tab_pre(const KeyHeaderDev* key, FinScratch* scr) {
   if (threadIdx.x != 0) return;
+  scr += blockIdx.y;
   if (blockIdx.x == 0) {
     G1XYZZ29 a = scr->rd1;
     a.madd(affine_from_mont256<Fq>(key->a0));
@@ -376,6 +383,9 @@ __global__ void __launch_bounds__(64) k_fin_tab_pre(const KeyHeaderDev* key, Fin
 // block 1: c' = s A + r B1 + s (a0 + alpha1) + r (b1_0 + beta1) + rs delta1 + L -> scr->rgb
 __global__ void __launch_bounds__(64) k_fin_tab_ac(const ProofSums* sums, FinScratch* scr, uint8_t* proj) {
   if (threadIdx.x != 0) return;
+  sums += blockIdx.y;
+  scr += blockIdx.y;
+  proj += (size_t)blockIdx.y * FIN_PROJ_BYTES;
   if (blockIdx.x == 0) {
     G1XYZZ29 a = scr->sga;
     a.add(sums->A);
@@ -393,6 +403,9 @@ __global__ void __launch_bounds__(64) k_fin_tab_ac(const ProofSums* sums, FinScr
 // after the H sum: C = c' + MSM_H -> proof
 __global__ void __launch_bounds__(64) k_fin_tab_c(const ProofSums* sums, const FinScratch* scr, uint8_t* proj) {
   if (threadIdx.x != 0) return;
+  sums += blockIdx.y;
+  scr += blockIdx.y;
+  proj += (size_t)blockIdx.y * FIN_PROJ_BYTES;
   G1XYZZ29 c = scr->rgb;
   c.add(sums->H);
   *reinterpret_cast<XYZZ<Fq>*>(proj + FIN_PROJ_C) = xyzz_to_mont256<Fq>(c);
@@ -400,6 +413,9 @@ __global__ void __launch_bounds__(64) k_fin_tab_c(const ProofSums* sums, const F
 // after the B2 sum: B = b' + MSM_B2 -> proof
 __global__ void __launch_bounds__(64) k_fin_tab_b(const ProofSums* sums, const FinScratch* scr, uint8_t* proj) {
   if (threadIdx.x != 0) return;
+  sums += blockIdx.y;
+  scr += blockIdx.y;
+  proj += (size_t)blockIdx.y * FIN_PROJ_BYTES;
   G2XYZZ29 b = scr->sd2;
   b.add(sums->B2);
   *reinterpret_cast<XYZZ<Fq2>*>(proj + FIN_PROJ_B) = xyzz_to_mont256<Fq2>(b);
@@ -523,8 +539,8 @@ void fin_b(const KeyHeaderDev* key, const ProofSums* sums, const FinScratch* scr
 void fin_partial_var(ProofSums* sums, const Fr* rs_dev, hipStream_t stream) {
   G16_LAUNCH(k_fin_partial_var, 2, 64, 0, stream, sums, rs_dev);
 }
-void fin_fixed_dist(const FinTables* tab, const Fr* rs_dev, FinScratch* scr, hipStream_t stream) {
-  G16_LAUNCH(k_fin_fixed_dist, 6, FIN_T, FIN_T * sizeof(G2XYZZ29), stream, tab, rs_dev, scr);
+void fin_fixed_dist(const FinTables* tab, const Fr* rs_dev, FinScratch* scr, hipStream_t stream, uint32_t count) {
+  G16_LAUNCH(k_fin_fixed_dist, dim3(6, count), FIN_T, FIN_T * sizeof(G2XYZZ29), stream, tab, rs_dev, scr);
 }
 void fin_final_dist(const KeyHeaderDev* key, const ProofSums* sums, const FinScratch* scr,
                     uint8_t* proof_dev, hipStream_t stream) {
@@ -633,6 +649,63 @@ void fin_tab_host_affine(const uint8_t* proj, uint8_t* proof) {
   memcpy(proof + 192, (const void*)&pc, 64);
 }
 
+// The batch: the same divisions with ONE inversion (Montgomery's trick).  Every denominator of the batch -- zzz of A
+// and C, the norm c0^2 + c1^2 of B's zzz (host_inv(Fq2) inverts exactly that) -- enters a running product; one
+// host_inv of the total, then the walk back hands every denominator its own inverse.  Points at infinity are
+// skipped and a zero denominator keeps host_inv's 0 -> 0, so every inverse is the field element host_inv returns:
+// the same bytes as fin_tab_host_affine proof by proof.
+void fin_tab_host_affine_batch(const uint8_t* proj, size_t count, uint8_t* proofs) {
+  std::vector<XYZZ<Fq>> a(count), c(count);
+  std::vector<XYZZ<Fq2>> b(count);
+  std::vector<Fq> den(3 * count), inv(3 * count), pre(3 * count + 1);
+  std::vector<uint8_t> live(3 * count);
+  for (size_t z = 0; z < count; ++z) {
+    const uint8_t* p = proj + z * FIN_PROJ_BYTES;
+    memcpy((void*)&a[z], p + FIN_PROJ_A, sizeof a[z]);
+    memcpy((void*)&b[z], p + FIN_PROJ_B, sizeof b[z]);
+    memcpy((void*)&c[z], p + FIN_PROJ_C, sizeof c[z]);
+    den[3 * z] = a[z].zzz;
+    den[3 * z + 1] = b[z].zzz.c0.sqr() + b[z].zzz.c1.sqr();
+    den[3 * z + 2] = c[z].zzz;
+    live[3 * z] = !a[z].is_inf();
+    live[3 * z + 1] = !b[z].is_inf();
+    live[3 * z + 2] = !c[z].is_inf();
+  }
+  const Fq zero = Fq::zero();
+  for (size_t k = 0; k < den.size(); ++k)
+    if (den[k] == zero) live[k] = 0;  // host_inv(0) = 0: stays out of the product
+  pre[0] = Fq::one();
+  for (size_t k = 0; k < den.size(); ++k) pre[k + 1] = live[k] ? pre[k] * den[k] : pre[k];
+  Fq t = host_inv(pre[den.size()]);  // 1 / (product of the live denominators)
+  for (size_t k = den.size(); k-- > 0;) {
+    if (!live[k]) {
+      inv[k] = zero;
+      continue;
+    }
+    inv[k] = t * pre[k];
+    t = t * den[k];
+  }
+  auto g1 = [](const XYZZ<Fq>& p, const Fq& iz3) {
+    if (p.is_inf()) return G1Affine::infinity();
+    const Fq iz2 = iz3.sqr() * p.zz.sqr();
+    return G1Affine{p.x * iz2, p.y * iz3};
+  };
+  for (size_t z = 0; z < count; ++z) {
+    uint8_t* out = proofs + z * 256;
+    const G1Affine pa = g1(a[z], inv[3 * z]), pc = g1(c[z], inv[3 * z + 2]);
+    G2Affine pb = G2Affine::infinity();
+    if (!b[z].is_inf()) {
+      const Fq n = inv[3 * z + 1];
+      const Fq2 iz3{b[z].zzz.c0 * n, (b[z].zzz.c1 * n).neg()};
+      const Fq2 iz2 = iz3.sqr() * b[z].zz.sqr();
+      pb = G2Affine{b[z].x * iz2, b[z].y * iz3};
+    }
+    memcpy(out, (const void*)&pa, 64);
+    memcpy(out + 64, (const void*)&pb, 128);
+    memcpy(out + 192, (const void*)&pc, 64);
+  }
+}
+
 void fin_host_affine_c(const uint8_t* proj, uint8_t* proof) {
   XYZZ<Fq> c;
   memcpy((void*)&c, proj + FIN_PROJ_C, sizeof c);
@@ -640,17 +713,17 @@ void fin_host_affine_c(const uint8_t* proj, uint8_t* proof) {
   memcpy(proof + 192, (const void*)&pc, 64);
 }
 
-void fin_tab_pre(const KeyHeaderDev* key, FinScratch* scr, hipStream_t stream) {
-  G16_LAUNCH(k_fin_tab_pre, 2, 64, 0, stream, key, scr);
+void fin_tab_pre(const KeyHeaderDev* key, FinScratch* scr, hipStream_t stream, uint32_t count) {
+  G16_LAUNCH(k_fin_tab_pre, dim3(2, count), 64, 0, stream, key, scr);
 }
-void fin_tab_ac(const ProofSums* sums, FinScratch* scr, uint8_t* proof_dev, hipStream_t stream) {
-  G16_LAUNCH(k_fin_tab_ac, 2, 64, 0, stream, sums, scr, proof_dev);
+void fin_tab_ac(const ProofSums* sums, FinScratch* scr, uint8_t* proof_dev, hipStream_t stream, uint32_t count) {
+  G16_LAUNCH(k_fin_tab_ac, dim3(2, count), 64, 0, stream, sums, scr, proof_dev);
 }
-void fin_tab_c(const ProofSums* sums, const FinScratch* scr, uint8_t* proof_dev, hipStream_t stream) {
-  G16_LAUNCH(k_fin_tab_c, 1, 64, 0, stream, sums, scr, proof_dev);
+void fin_tab_c(const ProofSums* sums, const FinScratch* scr, uint8_t* proof_dev, hipStream_t stream, uint32_t count) {
+  G16_LAUNCH(k_fin_tab_c, dim3(1, count), 64, 0, stream, sums, scr, proof_dev);
 }
-void fin_tab_b(const ProofSums* sums, const FinScratch* scr, uint8_t* proof_dev, hipStream_t stream) {
-  G16_LAUNCH(k_fin_tab_b, 1, 64, 0, stream, sums, scr, proof_dev);
+void fin_tab_b(const ProofSums* sums, const FinScratch* scr, uint8_t* proof_dev, hipStream_t stream, uint32_t count) {
+  G16_LAUNCH(k_fin_tab_b, dim3(1, count), 64, 0, stream, sums, scr, proof_dev);
 }
 void sums_to_partial(const ProofSums* sums, uint8_t* partial_dev, hipStream_t stream) {
   G16_LAUNCH(k_sums_to_partial, 7, 64, 0, stream, const_cast<ProofSums*>(sums), partial_dev);

@@ -46,6 +46,7 @@ __global__ void __launch_bounds__(256) k_powers(PowTable T, Fr scale, Fr* out, u
 struct FrOut {
   Fr* out;
   __device__ __forceinline__ void put(uint32_t i, const Fr29* v) const { out[i] = v[0].to_mont256(); }
+  __device__ __forceinline__ FrOut at(uint32_t) const { return *this; }  // one vector per launch
 };
 __global__ void __launch_bounds__(256) k_spmv(SpmvDev M, const Fr* x, FrOut out, uint32_t rows) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;

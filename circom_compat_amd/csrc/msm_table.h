@@ -39,7 +39,9 @@ inline size_t tbl_bytes(size_t g1_points, size_t g2_points) {
   return (g1_points * 64 + g2_points * 128) * TBL_W * TBL_E;
 }
 
-// one MSM of a launch: table, scalars, where the partials and the sum go
+// one MSM of a launch: table, scalars, where the partials and the sum go.  A launch covers a batch of
+// proofs (grid.z in k_tbl_msm, grid.y in k_tbl_final): proof z reads scalars + z sc_stride and rs + 2 z,
+// writes partial + z part_stride and sum + z sum_stride bytes (all strides 0 / unused for one proof)
 struct TblJob {
   const void* table;    // Affine<F>[count][TBL_W][TBL_E], packed internal form
   const void* scalars;  // Fr[count] (Montgomery) or U256[count] (canonical)
@@ -48,6 +50,9 @@ struct TblJob {
   int mul;        // 0: k = scalar; 1: k = r * scalar; 2: k = s * scalar   (rs_dev = r | s, Montgomery)
   void* partial;  // XYZZ29[blocks]
   void* sum;      // XYZZ29*
+  uint32_t sc_stride;    // scalars (elements of 32 bytes) between proofs
+  uint32_t part_stride;  // partials (XYZZ29 elements) between proofs
+  uint32_t sum_stride;   // bytes between the sums of consecutive proofs (sizeof(ProofSums))
 };
 constexpr int TBL_MAX_JOBS = 5;
 struct TblJobs {
@@ -66,6 +71,11 @@ struct TableSet {
   DevBuf<G1XYZZ29> partH;
   DevBuf<G2XYZZ29> part2;
   uint32_t blocks_w = 0, blocks_w2 = 0, blocks_h = 0;
+  // partial-sum elements of one proof: part1 / part2 / partH (a batch holds `count` of each, proof-major)
+  size_t part1_len() const { return (size_t)TBL_MAX_JOBS * blocks_w; }
+  size_t batch_bytes_per_proof() const {
+    return part1_len() * sizeof(G1XYZZ29) + (size_t)blocks_w2 * sizeof(G2XYZZ29) + (size_t)blocks_h * sizeof(G1XYZZ29);
+  }
 
   // host pointers to storage-form points (possibly unaligned: zero-copy zkey views)
   void build(const uint8_t* a, const uint8_t* b1, const uint8_t* b2, const uint8_t* l, const uint8_t* h,
@@ -80,10 +90,14 @@ struct TableSet {
   }
   size_t table_bytes() const { return tbl_bytes((size_t)2 * len_w + l_cnt + len_h, len_w); }
 
+  // `count` proofs in one launch each: proof z has its witness at w1 + z w_stride, (r, s) at rs_dev + 2 z, its
+  // h at h_canon + z h_stride, its sums at sums[z] and its partials at part + z * (that launch's per-proof length).
   // A, B1, L, s*A, r*B1 over the witness (w1 = w_dev + 1: entry i pairs with w[1 + i])
-  void run_g1_witness(const Fr* w1, const Fr* rs_dev, ProofSums* sums, hipStream_t stream);
-  void run_g2_witness(const Fr* w1, ProofSums* sums, hipStream_t stream);
-  void run_h(const U256* h_canon, ProofSums* sums, hipStream_t stream);
+  void run_g1_witness(const Fr* w1, uint32_t w_stride, const Fr* rs_dev, ProofSums* sums, G1XYZZ29* part,
+                      uint32_t count, hipStream_t stream);
+  void run_g2_witness(const Fr* w1, uint32_t w_stride, ProofSums* sums, G2XYZZ29* part, uint32_t count,
+                      hipStream_t stream);
+  void run_h(const U256* h_canon, uint32_t h_stride, ProofSums* sums, G1XYZZ29* part, uint32_t count, hipStream_t stream);
 };
 
 }  // namespace g16

@@ -64,23 +64,25 @@ __device__ __forceinline__ A block_tree_sum(A v, A* sh, int nthreads) {
   return sh[0];
 }
 
-// grid = (blocks, jobs).  Thread (i, g) of job y: windows 4 g .. 4 g + 3 of scalar i.
+// grid = (blocks, jobs, proofs).  Thread (i, g) of job y, proof z: windows 4 g .. 4 g + 3 of scalar i.
 template <class F, int NT>
 __global__ void __launch_bounds__(NT) k_tbl_msm(TblJobs J, const Fr* rs) {
   G16_DYN_SMEM(smem_raw);
   using X = XYZZ29<LazyT<F>>;
   X* sh = reinterpret_cast<X*>(smem_raw);
   const TblJob job = J.j[blockIdx.y];
+  const uint32_t z = blockIdx.z;
   const uint32_t gid = blockIdx.x * NT + threadIdx.x;
   const uint32_t i = gid / TBL_TPP, g = gid % TBL_TPP;
   X acc = X::infinity();
   if (i < job.count) {
     U256 k;
+    const size_t si = (size_t)z * job.sc_stride + i;
     if (job.canonical) {
-      k = reinterpret_cast<const U256*>(job.scalars)[i];
+      k = reinterpret_cast<const U256*>(job.scalars)[si];
     } else {
-      Fr v = reinterpret_cast<const Fr*>(job.scalars)[i];
-      if (job.mul) v = v * rs[job.mul - 1];
+      Fr v = reinterpret_cast<const Fr*>(job.scalars)[si];
+      if (job.mul) v = v * rs[2 * z + job.mul - 1];
       k = v.to_canonical();
     }
     // signed 8-bit digits: t = byte + carry; t > 128 -> digit t - 256, carry 1.  The carry into this
@@ -102,21 +104,22 @@ __global__ void __launch_bounds__(NT) k_tbl_msm(TblJobs J, const Fr* rs) {
     }
   }
   const X tot = block_tree_sum(acc, sh, NT);
-  if (threadIdx.x == 0) reinterpret_cast<X*>(job.partial)[blockIdx.x] = tot;
+  if (threadIdx.x == 0) reinterpret_cast<X*>(job.partial)[(size_t)z * job.part_stride + blockIdx.x] = tot;
 }
 
-// one block per job: strided sums of the partials, then the tree
+// one block per (job, proof): strided sums of the partials, then the tree
 template <class F, int NT>
 __global__ void __launch_bounds__(NT) k_tbl_final(TblJobs J, uint32_t blocks) {
   G16_DYN_SMEM(smem_raw);
   using X = XYZZ29<LazyT<F>>;
   X* sh = reinterpret_cast<X*>(smem_raw);
   const TblJob job = J.j[blockIdx.x];
-  const X* part = reinterpret_cast<const X*>(job.partial);
+  const uint32_t z = blockIdx.y;
+  const X* part = reinterpret_cast<const X*>(job.partial) + (size_t)z * job.part_stride;
   X acc = X::infinity();
   for (uint32_t b = threadIdx.x; b < blocks; b += NT) acc.add(part[b]);
   const X tot = block_tree_sum(acc, sh, NT);
-  if (threadIdx.x == 0) *reinterpret_cast<X*>(job.sum) = tot;
+  if (threadIdx.x == 0) *reinterpret_cast<X*>(reinterpret_cast<char*>(job.sum) + (size_t)z * job.sum_stride) = tot;
 }
 
 template <class F>
@@ -181,11 +184,13 @@ void TableSet::borrow(const TableSet& o) {
   active = o.active;
 }
 
-void TableSet::run_g1_witness(const Fr* w1, const Fr* rs_dev, ProofSums* S, hipStream_t s) {
+void TableSet::run_g1_witness(const Fr* w1, uint32_t w_stride, const Fr* rs_dev, ProofSums* S, G1XYZZ29* part,
+                              uint32_t count, hipStream_t s) {
   TblJobs J{};
   J.n = 5;
+  const uint32_t ps = (uint32_t)part1_len(), ss = sizeof(ProofSums);
   auto job = [&](int k, const G1Affine* tab, const Fr* sc, uint32_t cnt, int mul, G1XYZZ29* sum) {
-    J.j[k] = TblJob{tab, sc, cnt, 0, mul, part1.p + (size_t)k * blocks_w, sum};
+    J.j[k] = TblJob{tab, sc, cnt, 0, mul, part + (size_t)k * blocks_w, sum, w_stride, ps, ss};
   };
   job(0, tA, w1, len_w, 0, &S->A);
   job(1, tB1, w1, len_w, 0, &S->B1);
@@ -193,26 +198,27 @@ void TableSet::run_g1_witness(const Fr* w1, const Fr* rs_dev, ProofSums* S, hipS
   job(3, tA, w1, len_w, 2, &S->sA);    // s * A   = MSM_A(s w)
   job(4, tB1, w1, len_w, 1, &S->rB1);  // r * B1  = MSM_B1(r w)
   const size_t smem = (size_t)TBL_BLOCK * sizeof(G1XYZZ29);
-  G16_LAUNCH((k_tbl_msm<Fq, TBL_BLOCK>), dim3(blocks_w, J.n), TBL_BLOCK, smem, s, J, rs_dev);
-  G16_LAUNCH((k_tbl_final<Fq, TBL_BLOCK>), J.n, TBL_BLOCK, smem, s, J, blocks_w);
+  G16_LAUNCH((k_tbl_msm<Fq, TBL_BLOCK>), dim3(blocks_w, J.n, count), TBL_BLOCK, smem, s, J, rs_dev);
+  G16_LAUNCH((k_tbl_final<Fq, TBL_BLOCK>), dim3(J.n, count), TBL_BLOCK, smem, s, J, blocks_w);
 }
 
-void TableSet::run_g2_witness(const Fr* w1, ProofSums* S, hipStream_t s) {
+void TableSet::run_g2_witness(const Fr* w1, uint32_t w_stride, ProofSums* S, G2XYZZ29* part, uint32_t count,
+                              hipStream_t s) {
   TblJobs J{};
   J.n = 1;
-  J.j[0] = TblJob{tB2, w1, len_w, 0, 0, part2.p, &S->B2};
+  J.j[0] = TblJob{tB2, w1, len_w, 0, 0, part, &S->B2, w_stride, blocks_w2, (uint32_t)sizeof(ProofSums)};
   const size_t smem = (size_t)TBL_BLOCK_G2 * sizeof(G2XYZZ29);  // 36 KiB, as the G1 launches
-  G16_LAUNCH((k_tbl_msm<Fq2, TBL_BLOCK_G2>), dim3(blocks_w2, 1), TBL_BLOCK_G2, smem, s, J, (const Fr*)nullptr);
-  G16_LAUNCH((k_tbl_final<Fq2, TBL_BLOCK_G2>), 1, TBL_BLOCK_G2, smem, s, J, blocks_w2);
+  G16_LAUNCH((k_tbl_msm<Fq2, TBL_BLOCK_G2>), dim3(blocks_w2, 1, count), TBL_BLOCK_G2, smem, s, J, (const Fr*)nullptr);
+  G16_LAUNCH((k_tbl_final<Fq2, TBL_BLOCK_G2>), dim3(1, count), TBL_BLOCK_G2, smem, s, J, blocks_w2);
 }
 
-void TableSet::run_h(const U256* h_canon, ProofSums* S, hipStream_t s) {
+void TableSet::run_h(const U256* h_canon, uint32_t h_stride, ProofSums* S, G1XYZZ29* part, uint32_t count, hipStream_t s) {
   TblJobs J{};
   J.n = 1;
-  J.j[0] = TblJob{tH, h_canon, len_h, 1, 0, partH.p, &S->H};
+  J.j[0] = TblJob{tH, h_canon, len_h, 1, 0, part, &S->H, h_stride, blocks_h, (uint32_t)sizeof(ProofSums)};
   const size_t smem = (size_t)TBL_BLOCK * sizeof(G1XYZZ29);
-  G16_LAUNCH((k_tbl_msm<Fq, TBL_BLOCK>), dim3(blocks_h, 1), TBL_BLOCK, smem, s, J, (const Fr*)nullptr);
-  G16_LAUNCH((k_tbl_final<Fq, TBL_BLOCK>), 1, TBL_BLOCK, smem, s, J, blocks_h);
+  G16_LAUNCH((k_tbl_msm<Fq, TBL_BLOCK>), dim3(blocks_h, 1, count), TBL_BLOCK, smem, s, J, (const Fr*)nullptr);
+  G16_LAUNCH((k_tbl_final<Fq, TBL_BLOCK>), dim3(1, count), TBL_BLOCK, smem, s, J, blocks_h);
 }
 
 }  // namespace g16

@@ -150,10 +150,14 @@ struct SpmvMats {
 };
 
 // medium rows: one group of SPMV_G lanes per row
+// Batches (grid.y = vector index z): vector z reads x + z x_stride, writes out.at(z) and partial + z p_stride;
+// Out::at(z) is the output of vector z (Out types never launched with more than one vector return *this).
 template <int NM, class Out>
-__global__ void __launch_bounds__(256) k_spmv_medium(SpmvMats<NM> M, const Fr* __restrict__ x,
+__global__ void __launch_bounds__(256) k_spmv_medium(SpmvMats<NM> M, const Fr* __restrict__ x, size_t x_stride,
                                                      const uint32_t* __restrict__ med_rows, uint32_t n_med,
                                                      Out out) {
+  x += blockIdx.y * x_stride;
+  out = out.at(blockIdx.y);
   const uint32_t g = (blockIdx.x * blockDim.x + threadIdx.x) / SPMV_G;
   const bool live = g < n_med;  // dead groups still take part in the shuffles
   const uint32_t i = live ? med_rows[g] : 0u;
@@ -171,9 +175,11 @@ __global__ void __launch_bounds__(256) k_spmv_medium(SpmvMats<NM> M, const Fr* _
 
 // huge rows, stage 1: one group per task of <= SPMV_TASK_TERMS terms
 template <int NM>
-__global__ void __launch_bounds__(256) k_spmv_tasks(SpmvMats<NM> M, const Fr* __restrict__ x,
+__global__ void __launch_bounds__(256) k_spmv_tasks(SpmvMats<NM> M, const Fr* __restrict__ x, size_t x_stride,
                                                     const SpmvTask* __restrict__ tasks, uint32_t n_tasks,
-                                                    int32_t* __restrict__ partial) {
+                                                    int32_t* __restrict__ partial, size_t p_stride) {
+  x += blockIdx.y * x_stride;
+  partial += blockIdx.y * p_stride;
   const uint32_t g = (blockIdx.x * blockDim.x + threadIdx.x) / SPMV_G;
   const bool live = g < n_tasks;
   const SpmvTask t = live ? tasks[g] : SpmvTask{0u, 0u};
@@ -193,7 +199,9 @@ __global__ void __launch_bounds__(256) k_spmv_tasks(SpmvMats<NM> M, const Fr* __
 template <int NM, class Out>
 __global__ void __launch_bounds__(64) k_spmv_huge(const uint32_t* __restrict__ huge_rows,
                                                   const uint32_t* __restrict__ task_off, uint32_t n_huge,
-                                                  const int32_t* __restrict__ partial, Out out) {
+                                                  const int32_t* __restrict__ partial, size_t p_stride, Out out) {
+  partial += blockIdx.y * p_stride;
+  out = out.at(blockIdx.y);
   const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= n_huge) return;
   Fr29 v[NM];
@@ -217,17 +225,22 @@ __global__ void __launch_bounds__(64) k_spmv_huge(const uint32_t* __restrict__ h
 }
 
 // launches the medium and huge stages of a plan (the caller's own kernel covers the short rows and
-// whatever lies outside the matrices)
+// whatever lies outside the matrices).  batch > 1: vectors x + z x_stride, outputs out.at(z), task partials
+// in `partial` ([batch][n_tasks][9]; nullptr = the plan's own, batch 1 only)
 template <int NM, class Out>
-void spmv_run_long(const SpmvPlan& P, const SpmvMats<NM>& M, const Fr* x, Out out, hipStream_t stream) {
+void spmv_run_long(const SpmvPlan& P, const SpmvMats<NM>& M, const Fr* x, Out out, hipStream_t stream,
+                   uint32_t batch = 1, size_t x_stride = 0, int32_t* partial = nullptr) {
+  if (!partial) partial = P.partial.p;
+  const size_t p_stride = (size_t)P.n_tasks * f29::N;
   if (P.n_med)
-    G16_LAUNCH((k_spmv_medium<NM, Out>), ceil_div((uint64_t)P.n_med * SPMV_G, 256), 256, 0, stream, M, x,
-               (const uint32_t*)P.med_rows.p, P.n_med, out);
+    G16_LAUNCH((k_spmv_medium<NM, Out>), dim3(ceil_div((uint64_t)P.n_med * SPMV_G, 256), batch), 256, 0, stream, M,
+               x, x_stride, (const uint32_t*)P.med_rows.p, P.n_med, out);
   if (P.n_huge) {
-    G16_LAUNCH((k_spmv_tasks<NM>), ceil_div((uint64_t)P.n_tasks * SPMV_G, 256), 256, 0, stream, M, x,
-               (const SpmvTask*)P.tasks.p, P.n_tasks, P.partial.p);
-    G16_LAUNCH((k_spmv_huge<NM, Out>), ceil_div(P.n_huge, 64), 64, 0, stream, (const uint32_t*)P.huge_rows.p,
-               (const uint32_t*)P.task_off.p, P.n_huge, (const int32_t*)P.partial.p, out);
+    G16_LAUNCH((k_spmv_tasks<NM>), dim3(ceil_div((uint64_t)P.n_tasks * SPMV_G, 256), batch), 256, 0, stream, M, x,
+               x_stride, (const SpmvTask*)P.tasks.p, P.n_tasks, partial, p_stride);
+    G16_LAUNCH((k_spmv_huge<NM, Out>), dim3(ceil_div(P.n_huge, 64), batch), 64, 0, stream,
+               (const uint32_t*)P.huge_rows.p, (const uint32_t*)P.task_off.p, P.n_huge, (const int32_t*)partial,
+               p_stride, out);
   }
 }
 

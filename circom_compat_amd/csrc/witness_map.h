@@ -39,6 +39,13 @@ struct WitnessMap {
   //                     consumes; h_mont (optional): h in the storage form (Montgomery), the value
   //                     CircomReduction::witness_map_from_matrices returns.
   void run(const Fr* w_dev, U256* h_canon, Fr* h_mont, hipStream_t stream);
+  // `count` assignments at w_dev + z w_stride in one pass: abc_b = [count][3][9][n] int32 planes, partial =
+  // [count][spmv.n_tasks][9] int32, h_* + z n.  run() is the count = 1 case on the ctx's own abc / partial.
+  void run_batch(const Fr* w_dev, size_t w_stride, uint32_t count, int32_t* abc_b, int32_t* partial, U256* h_canon,
+                 Fr* h_mont, hipStream_t stream);
+  size_t batch_bytes_per_witness() const {  // abc planes, h (either form), SpMV task partials
+    return (size_t)3 * NTT29_LIMBS * n * 4 + (size_t)n * 32 + (size_t)spmv.n_tasks * 9 * 4;
+  }
 };
 
 // first row i with (A_i.w)(B_i.w) != C_i.w, or -1 (host pointers; uploads, checks, frees)

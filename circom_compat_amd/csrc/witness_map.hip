@@ -39,12 +39,17 @@ struct AbcOut {
     store_planes(abc + vs, n, i, v[1]);
     store_planes(abc + 2 * vs, n, i, v[0] * v[1]);
   }
+  // witness z of a batch: its three vectors follow those of witness z - 1
+  __device__ __forceinline__ AbcOut at(uint32_t z) const { return AbcOut{abc + (size_t)z * 3 * NTT29_LIMBS * n, n}; }
 };
 
 // Short rows (<= SPMV_SHORT terms in A and in B: what a chain of products or wire copies consists
 // of) and the rows past the matrices; medium and huge rows belong to spmv_run_long (spmv.h).
-__global__ void __launch_bounds__(256) k_spmv_abc(SpmvDev A, SpmvDev B, const Fr* w, uint32_t m,
+// grid.y = witness z of a batch (w + z w_stride -> out.at(z))
+__global__ void __launch_bounds__(256) k_spmv_abc(SpmvDev A, SpmvDev B, const Fr* w, size_t w_stride, uint32_t m,
                                                   uint32_t num_inputs, uint32_t n, AbcOut out) {
+  w += blockIdx.y * w_stride;
+  out = out.at(blockIdx.y);
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   Fr29 v[2] = {Fr29::zero(), Fr29::zero()};
@@ -58,12 +63,16 @@ __global__ void __launch_bounds__(256) k_spmv_abc(SpmvDev A, SpmvDev B, const Fr
   out.put(i, v);
 }
 
-// h = a * b - c (qap.rs:75,83-85), written as canonical integers and / or in the storage form
+// h = a * b - c (qap.rs:75,83-85), written as canonical integers and / or in the storage form.
+// grid.y = witness z of a batch: planes abc + 3 z vs, results h + z n
 __global__ void __launch_bounds__(256) k_mul_sub(const int32_t* abc, U256* h_canon, Fr* h_mont,
                                                  uint32_t n) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const size_t vs = (size_t)NTT29_LIMBS * n;
+  abc += blockIdx.y * 3 * vs;
+  if (h_canon) h_canon += (size_t)blockIdx.y * n;
+  if (h_mont) h_mont += (size_t)blockIdx.y * n;
   const Fr29 one = Fr29::one();
   const Fr29 a = load_planes(abc, n, i) * one;  // forward-NTT outputs are < 24 r: bring one factor below 2 r
   const Fr29 b = load_planes(abc + vs, n, i);
@@ -87,6 +96,7 @@ __global__ void __launch_bounds__(256) k_libsnark_quotient(int32_t* abc, Fr z_in
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const size_t vs = (size_t)NTT29_LIMBS * n;
+  abc += blockIdx.y * 3 * vs;
   const Fr29 one = Fr29::one();
   const Fr29 a = load_planes(abc, n, i) * one;
   const Fr29 b = load_planes(abc + vs, n, i);
@@ -100,6 +110,9 @@ __global__ void __launch_bounds__(256) k_libsnark_finish(const int32_t* planes, 
                                                          Fr* h_mont, uint32_t n) {
   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
+  planes += blockIdx.y * 3 * NTT29_LIMBS * (size_t)n;
+  if (h_canon) h_canon += (size_t)blockIdx.y * n;
+  if (h_mont) h_mont += (size_t)blockIdx.y * n;
   const uint32_t pos = k ? (__brev(j) >> (32 - k)) : 0u;
   const Fr29 h = load_planes(planes, n, pos);
   if (h_mont) h_mont[j] = h.to_mont256();
@@ -201,25 +214,31 @@ void WitnessMap::init(const CsrHost& A, const CsrHost& B, uint32_t m_, uint32_t 
 }
 
 void WitnessMap::run(const Fr* w_dev, U256* h_canon, Fr* h_mont, hipStream_t stream) {
+  run_batch(w_dev, 0, 1, abc.p, spmv.partial.p, h_canon, h_mont, stream);
+}
+
+void WitnessMap::run_batch(const Fr* w_dev, size_t w_stride, uint32_t count, int32_t* abc_b, int32_t* partial,
+                           U256* h_canon, Fr* h_mont, hipStream_t stream) {
   const SpmvMats<2> M{{SpmvDev{dA.rowptr.p, dA.col.p, dA.val.p}, SpmvDev{dB.rowptr.p, dB.col.p, dB.val.p}}};
   const size_t vs = (size_t)NTT29_LIMBS * n;
-  const AbcOut out{abc.p, n};
-  G16_LAUNCH(k_spmv_abc, ceil_div(n, 256), 256, 0, stream, M.m[0], M.m[1], w_dev, m, num_inputs, n, out);
-  spmv_run_long<2, AbcOut>(spmv, M, w_dev, out, stream);
+  const AbcOut out{abc_b, n};
+  const dim3 grid(ceil_div(n, 256), count);
+  G16_LAUNCH(k_spmv_abc, grid, 256, 0, stream, M.m[0], M.m[1], w_dev, w_stride, m, num_inputs, n, out);
+  spmv_run_long<2, AbcOut>(spmv, M, w_dev, out, stream, count, w_stride, partial);
+  // the NTTs: the 3 count vectors of the batch are contiguous (witness z: vectors 3 z .. 3 z + 2)
   if (reduction == 1) {
     // LibsnarkReduction::witness_map_from_matrices (ark-groth16; call sites reference
     // tests/groth16.rs:25-35): ifft, coset fft with g = 5, (a b - c) / Z, inverse coset fft
-    ntt29_dif(plan, abc.p, vs, 3, /*inverse=*/true, NTT_FUSE_TWIST_SCALE, stream, cs_lo.p, cs_hi.p);
-    ntt29_dit(plan, abc.p, vs, 3, stream);
-    G16_LAUNCH(k_libsnark_quotient, ceil_div(n, 256), 256, 0, stream, abc.p, z_inv_packed, n);
-    ntt29_dif(plan, abc.p, vs, 1, /*inverse=*/true, NTT_FUSE_TWIST_SCALE, stream, ci_lo.p, ci_hi.p);
-    G16_LAUNCH(k_libsnark_finish, ceil_div(n, 256), 256, 0, stream, (const int32_t*)abc.p, plan.base.k,
-               h_canon, h_mont, n);
+    ntt29_dif(plan, abc_b, vs, 3 * (int)count, /*inverse=*/true, NTT_FUSE_TWIST_SCALE, stream, cs_lo.p, cs_hi.p);
+    ntt29_dit(plan, abc_b, vs, 3 * (int)count, stream);
+    G16_LAUNCH(k_libsnark_quotient, grid, 256, 0, stream, abc_b, z_inv_packed, n);
+    ntt29_dif(plan, abc_b, 3 * vs, (int)count, /*inverse=*/true, NTT_FUSE_TWIST_SCALE, stream, ci_lo.p, ci_hi.p);
+    G16_LAUNCH(k_libsnark_finish, grid, 256, 0, stream, (const int32_t*)abc_b, plan.base.k, h_canon, h_mont, n);
     return;
   }
-  ntt29_dif(plan, abc.p, vs, 3, /*inverse=*/true, NTT_FUSE_TWIST_SCALE, stream);
-  ntt29_dit(plan, abc.p, vs, 3, stream);
-  G16_LAUNCH(k_mul_sub, ceil_div(n, 256), 256, 0, stream, (const int32_t*)abc.p, h_canon, h_mont, n);
+  ntt29_dif(plan, abc_b, vs, 3 * (int)count, /*inverse=*/true, NTT_FUSE_TWIST_SCALE, stream);
+  ntt29_dit(plan, abc_b, vs, 3 * (int)count, stream);
+  G16_LAUNCH(k_mul_sub, grid, 256, 0, stream, (const int32_t*)abc_b, h_canon, h_mont, n);
 }
 
 }  // namespace g16

@@ -34,6 +34,7 @@ struct DistAbcOut {
     store_planes(bufA + ((size_t)1 * G.c2 + i2l) * vs, G.n1, i1, v[1]);
     store_planes(bufA + ((size_t)2 * G.c2 + i2l) * vs, G.n1, i1, v[0] * v[1]);
   }
+  __device__ __forceinline__ DistAbcOut at(uint32_t) const { return *this; }  // one vector per launch
 };
 
 // short rows of this rank and its rows past the matrices (the longer ones: spmv_run_long, spmv.h)

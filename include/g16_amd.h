@@ -197,6 +197,26 @@ g16_status g16_prove(g16_ctx* ctx, const uint64_t r[4], const uint64_t s[4], con
 g16_status g16_prove_dev(g16_ctx* ctx, const uint64_t r[4], const uint64_t s[4], const void* w_dev,
                          size_t n_vars, uint8_t proof_out[G16_PROOF_BYTES]);
 
+/* Batched proving: count proofs under the ctx's key.  Proof i equals, byte for byte, what
+ * g16_prove(ctx, r + 4*i, s + 4*i, w + i*n_vars*4, n_vars, out) returns.
+ * r, s: count x 4 u64 (Montgomery).  w: count x n_vars x 4 u64.  proofs_out: count x 256 bytes.
+ * count == 0: G16_OK, nothing written.  On an error, proofs_out is unspecified.  Argument rules are those
+ * of g16_prove_dev (world == 1; not on a dist_wm ctx).
+ * On a ctx with fixed-base tables (g16_ctx_info out[15] bit 0) a chunk of proofs goes through every kernel
+ * in ONE pass; the chunk is the largest that fits a quarter of the device memory free at the call (at most
+ * 256), larger counts loop over chunks, and the workspace stays with the ctx until g16_ctx_destroy.  On
+ * bucket-path ctxs and g16_ctx_create_multi ctxs the call loops over the single-proof path: a correct
+ * fallback, not a faster one.                                                                       */
+g16_status g16_prove_batch(g16_ctx* ctx, size_t count, const uint64_t* r, const uint64_t* s,
+                           const uint64_t* w, size_t n_vars, uint8_t* proofs_out);
+/* the same, with the witnesses resident in HBM: w_dev = count x n_vars x 32 bytes, contiguous       */
+g16_status g16_prove_batch_dev(g16_ctx* ctx, size_t count, const uint64_t* r, const uint64_t* s,
+                               const void* w_dev, size_t n_vars, uint8_t* proofs_out);
+/* witness_map_from_matrices for count assignments in one pass (also on a witness-map-only ctx; not on
+ * multi-device or dist_wm ctxs): h_out = count x domain_size x 4 u64, entry i == g16_witness_map(ctx, w_i) */
+g16_status g16_witness_map_batch(g16_ctx* ctx, size_t count, const uint64_t* w, size_t n_vars,
+                                 uint64_t* h_out);
+
 /* Multi-GPU (one process per GPU): every rank computes the sums of ITS point range -- and, while
  * its remaining MSMs run, the two products s*A_rank and r*B1_rank the finalisation is linear in --
  * the host framework all-gathers the G16_PARTIAL_BYTES records (RCCL all_gather; EC addition is

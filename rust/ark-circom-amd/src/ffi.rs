@@ -168,6 +168,9 @@ extern "C" {
     pub fn g16_msm_g2_dev(ctx: *mut g16_ctx, scalars_dev: *const c_void, len: usize, out: *mut u8) -> g16_status;
     pub fn g16_prove(ctx: *mut g16_ctx, r: *const u64, s: *const u64, w: *const u64, n_vars: usize, proof_out: *mut u8) -> g16_status;
     pub fn g16_prove_dev(ctx: *mut g16_ctx, r: *const u64, s: *const u64, w_dev: *const c_void, n_vars: usize, proof_out: *mut u8) -> g16_status;
+    pub fn g16_prove_batch(ctx: *mut g16_ctx, count: usize, r: *const u64, s: *const u64, w: *const u64, n_vars: usize, proofs_out: *mut u8) -> g16_status;
+    pub fn g16_prove_batch_dev(ctx: *mut g16_ctx, count: usize, r: *const u64, s: *const u64, w_dev: *const c_void, n_vars: usize, proofs_out: *mut u8) -> g16_status;
+    pub fn g16_witness_map_batch(ctx: *mut g16_ctx, count: usize, w: *const u64, n_vars: usize, h_out: *mut u64) -> g16_status;
     pub fn g16_prove_partial(ctx: *mut g16_ctx, r: *const u64, s: *const u64, w: *const u64, n_vars: usize, partial_out: *mut u8) -> g16_status;
     pub fn g16_prove_partial_dev(ctx: *mut g16_ctx, r: *const u64, s: *const u64, w_dev: *const c_void, n_vars: usize, partial_out: *mut u8) -> g16_status;
     pub fn g16_prove_finish(ctx: *mut g16_ctx, r: *const u64, s: *const u64, partials: *const u8, world: c_int, proof_out: *mut u8) -> g16_status;

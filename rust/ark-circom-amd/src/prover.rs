@@ -254,6 +254,39 @@ impl GpuProver {
         Ok(pack::unpack_proof(&raw))
     }
 
+    /// Many proofs under this key in one call (`g16_prove_batch`): proof `i` is
+    /// `create_proof(rs[i].0, rs[i].1, &witnesses[i])`, byte for byte.  On a ctx with fixed-base tables the
+    /// library proves a chunk of witnesses in one pass; elsewhere it loops over the single-proof path.
+    pub fn prove_batch(&mut self, rs: &[(Fr, Fr)], witnesses: &[Vec<Fr>]) -> Result<Vec<Proof<Bn254>>, GpuError> {
+        if rs.len() != witnesses.len() || witnesses.iter().any(|w| w.len() != self.n_vars) {
+            return Err(GpuError::Synthesis(SynthesisError::MalformedVerifyingKey));
+        }
+        let count = rs.len();
+        if count == 0 {
+            return Ok(Vec::new());
+        }
+        let mut r = Vec::with_capacity(4 * count);
+        let mut s = Vec::with_capacity(4 * count);
+        for (ri, si) in rs {
+            r.extend_from_slice(&pack::fr_words(ri));
+            s.extend_from_slice(&pack::fr_words(si));
+        }
+        let mut w = Vec::with_capacity(4 * self.n_vars * count);
+        for wi in witnesses {
+            w.extend(pack::fr_vec_words(wi));
+        }
+        let mut raw = vec![0u8; ffi::G16_PROOF_BYTES * count];
+        let st = unsafe {
+            ffi::g16_prove_batch(self.ctx, count, r.as_ptr(), s.as_ptr(), w.as_ptr(), self.n_vars, raw.as_mut_ptr())
+        };
+        check(self.ctx, st)?;
+        Ok(raw.chunks_exact(ffi::G16_PROOF_BYTES).map(|p| {
+            let mut one = [0u8; ffi::G16_PROOF_BYTES];
+            one.copy_from_slice(p);
+            pack::unpack_proof(&one)
+        }).collect())
+    }
+
     /// `SNARK::prove(&pk, circuit, rng)` shape (src/zkey.rs:866): r, s from the rng.
     pub fn prove_with_rng<R: Rng>(&mut self, full_assignment: &[Fr], rng: &mut R) -> Result<Proof<Bn254>, GpuError> {
         let r = Fr::rand(rng);
