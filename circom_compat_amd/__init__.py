@@ -700,6 +700,7 @@ class Prover:
         d = dict(zip(keys, list(out)))
         d["shard_mode"] = {0: "none", 1: "points", 2: "buckets"}.get(d["shard_mode"], "?")
         d["sparse_b"] = (d["fixed_tables"] >> 1) & 1       # out[15]: bit 0 = fixed-base tables, bit 1 = filtered B view
+        d["batched"] = (d["fixed_tables"] >> 2) & 1        # bit 2 = a chunk of prove_batch is enqueued once
         d["fixed_tables"] &= 1
         return d
 

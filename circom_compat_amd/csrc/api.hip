@@ -143,34 +143,67 @@ void collect_times(g16_ctx* c) {
   if (c->timer.enabled) c->timer.collect(c->st_ms, c->st_cnt);
 }
 
+// The MSM state of a chunk of bucket-path proofs: the ctx's own for g16_prove and the sharded provers (count = 1),
+// the batch workspace's (g16_ctx::BatchWs) for g16_prove_batch.  Proof z: witness w + z w_stride, its h at
+// h + z wm.n, its sums at sums[z].  The sorts hold every proof of the chunk (MsmSort: proof-major bucket ids), so
+// one accumulation and one reduction per MSM serve the whole chunk.
+struct BucketChunk {
+  uint32_t count;
+  const Fr* w;
+  size_t w_stride;
+  int32_t *abc, *spmv;
+  U256* h;
+  ProofSums* sums;
+  MsmSort *sort_w, *sort_h, *sort_b;
+  MsmWork<Fq> *work1, *workH;
+  MsmWork<Fq2>* work2;
+  // finalisation (single-device provers): (r, s) at rs[2 z], uploaded from rs_host + 64 z; scratch scr[z]; A | B
+  // (affine) at rec + z rec_stride, C's XYZZ at proj + z FIN_PROJ_BYTES + FIN_PROJ_C.  rec == proj (a chunk): the
+  // records leave in one copy to proj_host; otherwise A | B go to rec_host and C to proj_host (g16_prove)
+  Fr* rs;
+  const uint8_t* rs_host;
+  FinScratch* scr;
+  uint8_t *rec, *proj;
+  uint32_t rec_stride;
+  uint8_t *rec_host, *proj_host;
+  const MsmSort& sort_for_b(const g16_ctx* c) const { return c->sparse_b ? *sort_b : *sort_w; }
+};
+
+BucketChunk own_chunk(g16_ctx* c, const Fr* w_dev) {
+  return BucketChunk{1,           w_dev,       c->N,        c->wm.abc.p, c->wm.spmv.partial.p, c->h_canon.p, c->sums_dev.p,
+                     &c->sort_w,  &c->sort_h,  &c->sort_b,  &c->work1,   &c->workH,            &c->work2,
+                     c->rs_dev.p, c->pin_io,   c->fin_scr.p, c->out_dev.p, c->part_dev(), (uint32_t)G16_PROOF_BYTES,
+                     c->pin_io + 64, c->pin_io + 64 + G16_PROOF_BYTES};
+}
+
 // A and B1 accumulations into work1 slots 0 and 1: one launch over the interleaved pair, or two
-void accumulate_ab(g16_ctx* c, hipStream_t s, StageTimer* tm, bool fixup = true) {
+void accumulate_ab(g16_ctx* c, const BucketChunk& ch, hipStream_t s, StageTimer* tm, bool fixup = true) {
   if (c->ptsA.stride == 2) {
-    msm_accumulate_pair<Fq>(c->sort_w, c->ptsA, c->ptsB1, c->work1, 0, s, tm, fixup);
+    msm_accumulate_pair<Fq>(*ch.sort_w, c->ptsA, c->ptsB1, *ch.work1, 0, s, tm, fixup);
   } else {
-    msm_accumulate<Fq>(c->sort_w, c->ptsA, 0, c->work1, 0, s, tm, fixup);
-    msm_accumulate<Fq>(c->sort_w, c->ptsB1, 0, c->work1, 1, s, tm, fixup);
+    msm_accumulate<Fq>(*ch.sort_w, c->ptsA, 0, *ch.work1, 0, s, tm, fixup);
+    msm_accumulate<Fq>(*ch.sort_w, c->ptsB1, 0, *ch.work1, 1, s, tm, fixup);
   }
 }
 // the deferred exact additions of accumulate_ab(fixup = false), on the stream that reduces A and B1
-void fixup_ab(g16_ctx* c, hipStream_t q) {
+void fixup_ab(g16_ctx* c, const BucketChunk& ch, hipStream_t q) {
   StageTimer* tm = c->timer.enabled ? &c->timer : nullptr;
   if (c->ptsA.stride == 2) {
-    msm_fixup_pair<Fq>(c->sort_w, c->ptsA, c->ptsB1, c->work1, 0, q, tm);
+    msm_fixup_pair<Fq>(*ch.sort_w, c->ptsA, c->ptsB1, *ch.work1, 0, q, tm);
   } else {
-    msm_fixup<Fq>(c->sort_w, c->ptsA, 0, c->work1, 0, q, tm);
-    msm_fixup<Fq>(c->sort_w, c->ptsB1, 0, c->work1, 1, q, tm);
+    msm_fixup<Fq>(*ch.sort_w, c->ptsA, 0, *ch.work1, 0, q, tm);
+    msm_fixup<Fq>(*ch.sort_w, c->ptsB1, 0, *ch.work1, 1, q, tm);
   }
 }
 
 // main stream: witness-scalar sort, then the A, B1, L, B2 MSMs (ALU bound).  `after_ab` is called
 // once the A and B1 sums are enqueued: the provers fork the variable-base part of the
 // finalisation onto the side stream there.
-void enqueue_witness_sort(g16_ctx* c, const Fr* w_dev) {
+void enqueue_witness_sort(g16_ctx* c, const BucketChunk& ch) {
   hipStream_t s = c->stream;
   StageTimer* tm = c->timer.enabled ? &c->timer : nullptr;
   int id = tm ? tm->begin(ST_MSM_SORT, s) : -1;
-  c->sort_w.run(w_dev + 1 + c->w_lo, c->w_hi - c->w_lo, /*mont=*/true, s);
+  ch.sort_w->run(ch.w + 1 + c->w_lo, c->w_hi - c->w_lo, /*mont=*/true, s, ch.count, ch.w_stride);
   if (tm) tm->end(id, s);
   if (c->sparse_b) {
     // the filtered view is built beside the A | B1 accumulation (which reads the full sort): on the `red`
@@ -179,7 +212,7 @@ void enqueue_witness_sort(g16_ctx* c, const Fr* w_dev) {
     G16_HIP(hipEventRecord(c->ev_view, s));
     G16_HIP(hipStreamWaitEvent(v, c->ev_view, 0));
     id = tm ? tm->begin(ST_MSM_SORT, v) : -1;
-    c->sort_b.run_view(c->sort_w, c->keep_b, v);
+    ch.sort_b->run_view(*ch.sort_w, c->keep_b, v);
     if (tm) tm->end(id, v);
     G16_HIP(hipEventRecord(c->ev_view, v));
   }
@@ -190,13 +223,18 @@ void wait_for_b_view(g16_ctx* c, hipStream_t s) {
 }
 
 template <class Hook, class Hook2>
-void enqueue_witness_msms(g16_ctx* c, const Fr* w_dev, Hook after_ab, Hook2 after_b2, bool sorted = false) {
+void enqueue_witness_msms(g16_ctx* c, const BucketChunk& ch, Hook after_ab, Hook2 after_b2, bool sorted = false) {
   hipStream_t s = c->stream;
   StageTimer* tm = c->timer.enabled ? &c->timer : nullptr;
-  ProofSums* S = c->sums_dev.p;
-  if (!sorted) enqueue_witness_sort(c, w_dev);
-  // buckets this ctx reduces per MSM: 1/world of the set under bucket-range sharding
-  const uint32_t nb_eff = c->cfg_w.nb() / (c->shard_buckets ? (uint32_t)c->world : 1u);
+  ProofSums* S = ch.sums;
+  const size_t ps = sizeof(ProofSums);  // proof z's sums: S + z (a chunk)
+  if (!sorted) enqueue_witness_sort(c, ch);
+  // buckets this ctx reduces per MSM: 1/world of the set under bucket-range sharding.  A chunk of proofs is ONE
+  // bucket set of count x nb buckets (world = 1): its reductions are launches of that size -- as long a chain per
+  // thread, as many issue slots taken from what they hide under, as a single proof with that many buckets -- so
+  // the placement below is chosen from the chunk's bucket count exactly as it is for such a proof.  count = 1 is
+  // g16_prove's placement.
+  const uint32_t nb_eff = ch.count * c->cfg_w.nb() / (c->shard_buckets ? (uint32_t)c->world : 1u);
   const bool small = nb_eff < (1u << 18);
   const uint32_t b2_limit = c->world > 1 ? (1u << 18) : (1u << 16);
   const bool b2_off = c->overlap && nb_eff < b2_limit;
@@ -208,7 +246,7 @@ void enqueue_witness_msms(g16_ctx* c, const Fr* w_dev, Hook after_ab, Hook2 afte
   // one batched reduction of A, B1, L instead: 22.0 ms.
   const bool sharded = c->world > 1 || c->dist_wm;
   const bool mid = (nb_eff >= (1u << 15) && small) || (sharded && nb_eff >= (1u << 15));
-  if (mid && c->overlap && c->work1.batch >= 3) {
+  if (mid && c->overlap && ch.work1->batch >= 3) {
     // Mid-sized bucket sets (2^15..2^17: 2^18..2^20-constraint proofs, ranks of a sharded 2^22
     // one): every reduction is a latency-bound chain long enough to matter and short enough to
     // hide, so none stays on the main stream -- it only accumulates (A, B1, B2, L, then H) and the
@@ -224,17 +262,17 @@ void enqueue_witness_msms(g16_ctx* c, const Fr* w_dev, Hook after_ab, Hook2 afte
     // reducing stream: 2^20 proof 11.6-11.8 / 11.4 ms, one point-sharded rank of 8 at 2^22 7.9-8.0 / 7.8 ms
     // (round 3, same box).
     hipStream_t q = c->red;
-    accumulate_ab(c, s, tm, /*fixup=*/false);
+    accumulate_ab(c, ch, s, tm, /*fixup=*/false);
     G16_HIP(hipEventRecord(c->ev_acc[0], s));
     G16_HIP(hipStreamWaitEvent(q, c->ev_acc[0], 0));
-    fixup_ab(c, q);
-    msm_reduce<Fq>(c->sort_w, c->work1, 0, 2, &S->A, q, tm, /*hidden=*/true);
+    fixup_ab(c, ch, q);
+    msm_reduce<Fq>(*ch.sort_w, *ch.work1, 0, 2, &S->A, q, tm, /*hidden=*/true, ps);
     after_ab(q);
     wait_for_b_view(c, s);
-    msm_accumulate<Fq2>(c->sort_for_b(), c->ptsB2, 0, c->work2, 0, s, tm);
+    msm_accumulate<Fq2>(ch.sort_for_b(c), c->ptsB2, 0, *ch.work2, 0, s, tm);
     G16_HIP(hipEventRecord(c->ev_acc[1], s));
     G16_HIP(hipStreamWaitEvent(q, c->ev_acc[1], 0));
-    msm_reduce<Fq2>(c->sort_for_b(), c->work2, 0, 1, &S->B2, q, tm, /*hidden=*/true);
+    msm_reduce<Fq2>(ch.sort_for_b(c), *ch.work2, 0, 1, &S->B2, q, tm, /*hidden=*/true, ps);
     // Round 6 (2^20 timeline, profiles/r06_timeline_k20.txt): B's assembly (fin_b, 0.25 ms on one lane) used to
     // queue on `red` BEHIND the L reduction and ended 0.3 ms after the last reduction of the proof -- fin_final
     // waited for it.  Now it follows the B2 reduction at once and the L reduction takes the side stream (idle
@@ -242,37 +280,37 @@ void enqueue_witness_msms(g16_ctx* c, const Fr* w_dev, Hook after_ab, Hook2 afte
     const bool r5 = sched_r5();
     hipStream_t ql = r5 ? q : c->side;
     if (!r5) after_b2();
-    msm_accumulate<Fq>(c->sort_w, c->ptsL, c->l_idx_min, c->work1, 2, s, tm, /*fixup=*/false);
+    msm_accumulate<Fq>(*ch.sort_w, c->ptsL, c->l_idx_min, *ch.work1, 2, s, tm, /*fixup=*/false);
     G16_HIP(hipEventRecord(c->ev_acc[2], s));
     G16_HIP(hipStreamWaitEvent(ql, c->ev_acc[2], 0));
-    msm_fixup<Fq>(c->sort_w, c->ptsL, c->l_idx_min, c->work1, 2, ql, tm);
-    msm_reduce<Fq>(c->sort_w, c->work1, 2, 1, &S->L, ql, tm, /*hidden=*/true);
+    msm_fixup<Fq>(*ch.sort_w, c->ptsL, c->l_idx_min, *ch.work1, 2, ql, tm);
+    msm_reduce<Fq>(*ch.sort_w, *ch.work1, 2, 1, &S->L, ql, tm, /*hidden=*/true, ps);
     if (r5) after_b2();
     G16_HIP(hipEventRecord(c->ev_b2, q));
     G16_HIP(hipStreamWaitEvent(c->side, c->ev_b2, 0));  // the side stream joins: one event to wait on
     G16_HIP(hipEventRecord(c->ev_side, c->side));
     return;
   }
-  if (small && c->work1.batch >= 3) {
+  if (small && ch.work1->batch >= 3) {
     // A, B1, L share the witness sort: three accumulations, ONE batched bucket reduction.  With
     // few buckets the reduction is pure latency (~0.4 ms of dependent EC additions whatever the
     // size): paying it once instead of three times is worth 20 % of a 2^16 proof and of a rank's
     // share of a sharded 2^22 proof.  ProofSums keeps A, B1, L adjacent.
-    accumulate_ab(c, s, tm);
-    msm_accumulate<Fq>(c->sort_w, c->ptsL, c->l_idx_min, c->work1, 2, s, tm);
-    msm_reduce<Fq>(c->sort_w, c->work1, 0, 3, &S->A, s, tm);
+    accumulate_ab(c, ch, s, tm);
+    msm_accumulate<Fq>(*ch.sort_w, c->ptsL, c->l_idx_min, *ch.work1, 2, s, tm);
+    msm_reduce<Fq>(*ch.sort_w, *ch.work1, 0, 3, &S->A, s, tm, false, ps);
     after_ab(s);
   } else {
     // large bucket sets: the reduction is throughput bound, and reducing A and B1 at once lets
     // the variable-base part of the finalisation start ~10 ms earlier (measured at 2^22: 41.3 vs
     // 43.0 ms per proof)
-    accumulate_ab(c, s, tm);
-    msm_reduce<Fq>(c->sort_w, c->work1, 0, 2, &S->A, s, tm);  // ProofSums keeps A, B1 adjacent
+    accumulate_ab(c, ch, s, tm);
+    msm_reduce<Fq>(*ch.sort_w, *ch.work1, 0, 2, &S->A, s, tm, false, ps);  // ProofSums keeps A, B1 adjacent
     after_ab(s);
     // (round 4, VERDICT r3 item 5: taking the L reduction off the main stream -- beside the H
     // accumulation, or beside the H reduction -- was built and measured: 37.67 / 37.50 ms shipped vs
     // 37.56 / 37.59 and 37.77 / 37.46, same box; profiles/r04_defer_l_reduction_ab.txt.  Not kept.)
-    msm_run<Fq>(c->sort_w, c->ptsL, c->l_idx_min, c->work1, &S->L, s, tm);
+    msm_run<Fq>(*ch.sort_w, c->ptsL, c->l_idx_min, *ch.work1, &S->L, s, tm, ps);
   }
   // B2: accumulate here; with small bucket sets its reduction (a latency-bound chain of Fq2 point
   // additions) runs on its own stream underneath the H MSM -- with large ones it only takes VALU
@@ -280,13 +318,13 @@ void enqueue_witness_msms(g16_ctx* c, const Fr* w_dev, Hook after_ab, Hook2 afte
   //   2^14: 4.60 ms neither, 3.84 batched, 3.64 both;  2^18: 6.74 / 5.61 / 5.23;
   //   2^20: 13.56 / 13.05 / 13.21;  2^22: 40.1 / 41.9 / -.   ev_side = "everything forked is done".
   wait_for_b_view(c, s);
-  msm_accumulate<Fq2>(c->sort_for_b(), c->ptsB2, 0, c->work2, 0, s, tm);
+  msm_accumulate<Fq2>(ch.sort_for_b(c), c->ptsB2, 0, *ch.work2, 0, s, tm);
   // sharded ranks: the main stream is the critical path (the witness-map phases and exchanges hide
   // under it), so the B2 reduction leaves it whenever the bucket set is small
   hipStream_t rs = b2_off ? c->red : s;
   G16_HIP(hipEventRecord(c->ev_b2, s));
   G16_HIP(hipStreamWaitEvent(rs, c->ev_b2, 0));
-  msm_reduce<Fq2>(c->sort_for_b(), c->work2, 0, 1, &S->B2, rs, tm);
+  msm_reduce<Fq2>(ch.sort_for_b(c), *ch.work2, 0, 1, &S->B2, rs, tm, false, ps);
   // what only needs the B2 sum continues on the `red` stream (never on the main stream: it is a
   // single-lane chain)
   G16_HIP(hipEventRecord(c->ev_b2, rs));
@@ -300,18 +338,18 @@ void enqueue_witness_msms(g16_ctx* c, const Fr* w_dev, Hook after_ab, Hook2 afte
 // main stream: H MSM once the aux stream has produced (and sorted) this rank's h scalars.
 // (Keeping the whole H chain on the aux stream, in parallel with the witness-scalar chain, was
 // measured on one box at 2^14..2^22: 1-5 % slower at small sizes, neutral at large ones.)
-void enqueue_h_msm(g16_ctx* c) {
+void enqueue_h_msm(g16_ctx* c, const BucketChunk& ch) {
   hipStream_t s = c->stream;
   StageTimer* tm = c->timer.enabled ? &c->timer : nullptr;
   G16_HIP(hipStreamWaitEvent(s, c->ev_h, 0));
-  msm_run<Fq>(c->sort_h, c->ptsH, 0, c->workH, &c->sums_dev.p->H, s, tm);
+  msm_run<Fq>(*ch.sort_h, c->ptsH, 0, *ch.workH, &ch.sums->H, s, tm, sizeof(ProofSums));
 }
 
 // MSMs of one proof on this ctx's shard; results left in sums_dev.
 // aux stream: witness map (integer-ALU bound) then the H-query sort (atomics/HBM bound), beside
 // the main stream's work.
 template <class Hook, class Hook2>
-void run_msms(g16_ctx* c, const Fr* w_dev, Hook after_ab, Hook2 after_b2) {
+void run_msms(g16_ctx* c, const BucketChunk& ch, Hook after_ab, Hook2 after_b2) {
   hipStream_t s = c->stream, x = c->overlap ? c->aux : c->stream;
   StageTimer* tm = c->timer.enabled ? &c->timer : nullptr;
   // Round 6: with LARGE bucket sets (>= 2^18: 2^21-constraint proofs and up, the reductions stay on the main
@@ -321,27 +359,27 @@ void run_msms(g16_ctx* c, const Fr* w_dev, Hook after_ab, Hook2 after_b2) {
   // 35.79, 36.11 ms; 2^21 equal.  Mid-sized proofs keep the map first: behind the sort it runs wholly under the
   // accumulations and costs them more than the earlier start returns (2^19 6.6 / 6.9, 2^20 11.2 / 11.4, Poseidon
   // 2^20 10.9 / 11.2 ms).
-  const uint32_t nb_eff = c->cfg_w.nb() / (c->shard_buckets ? (uint32_t)c->world : 1u);
+  const uint32_t nb_eff = ch.count * c->cfg_w.nb() / (c->shard_buckets ? (uint32_t)c->world : 1u);  // (a chunk: enqueue_witness_msms)
   // Up to 2^24: above, the witness map is what the H MSM waits for and must not start later
   // (2^25: 265.3 ms map first, 267.8 sort first; 2^23 / 2^24 equal: profiles/r06_schedule_ab.txt block 5).
   const bool sort_first = !sched_r5() && c->overlap && c->world == 1 && nb_eff >= (1u << 18) && c->n <= (1u << 24);
-  if (sort_first) enqueue_witness_sort(c, w_dev);
+  if (sort_first) enqueue_witness_sort(c, ch);
   G16_HIP(hipEventRecord(c->ev_w, s));  // w is resident (upload enqueued on the main stream) [and sorted]
   G16_HIP(hipStreamWaitEvent(x, c->ev_w, 0));
   int id = tm ? tm->begin(ST_WITNESS_MAP, x) : -1;
-  c->wm.run(w_dev, c->h_canon.p, nullptr, x);
+  c->wm.run_batch(ch.w, ch.w_stride, ch.count, ch.abc, ch.spmv, ch.h, nullptr, x);
   if (tm) tm->end(id, x);
   id = tm ? tm->begin(ST_MSM_SORT, x) : -1;
-  c->sort_h.run(c->h_canon.p + c->h_lo, c->h_hi - c->h_lo, /*mont=*/false, x);
+  ch.sort_h->run(ch.h + c->h_lo, c->h_hi - c->h_lo, /*mont=*/false, x, ch.count, c->wm.n);
   if (tm) tm->end(id, x);
   G16_HIP(hipEventRecord(c->ev_h, x));
-  enqueue_witness_msms(c, w_dev, after_ab, after_b2, /*sorted=*/sort_first);
-  enqueue_h_msm(c);
+  enqueue_witness_msms(c, ch, after_ab, after_b2, /*sorted=*/sort_first);
+  enqueue_h_msm(c, ch);
 }
 
 template <class Hook>
-void run_msms(g16_ctx* c, const Fr* w_dev, Hook after_ab) {
-  run_msms(c, w_dev, after_ab, [] {});
+void run_msms(g16_ctx* c, const BucketChunk& ch, Hook after_ab) {
+  run_msms(c, ch, after_ab, [] {});
 }
 
 // sharded provers: upload (r, s) and start the r/s-only fixed-base sums on the side stream
@@ -456,37 +494,48 @@ static void proof_from_pin(g16_ctx* c, uint8_t* proof_out) {
   }
 }
 
-// one whole single-device proof, enqueue only: (r, s) from and the proof to the ctx's pinned buffer
-static void enqueue_prove(g16_ctx* c, const Fr* w_dev) {
-  if (c->tbl.active) return enqueue_prove_tables(c, w_dev);
+// a chunk of single-device bucket-path proofs, enqueue only: every stage is one launch for the whole chunk (the
+// sorts, accumulations and reductions through the chunk's MsmSort / MsmWork, the finalisation kernels on
+// grid.y).  g16_prove is the count = 1 case on the ctx's own buffers (own_chunk).
+static void enqueue_prove_buckets(g16_ctx* c, const BucketChunk& ch) {
   hipStream_t s = c->stream;
-  G16_HIP(hipMemcpyAsync(c->rs_dev.p, c->pin_io, 64, hipMemcpyHostToDevice, s));
+  const uint32_t n = ch.count;
+  G16_HIP(hipMemcpyAsync(ch.rs, ch.rs_host, (size_t)64 * n, hipMemcpyHostToDevice, s));
   // fork: the (r, s)-only part of the finalisation runs beside the witness map / MSMs
   G16_HIP(hipEventRecord(c->ev_start, s));
   G16_HIP(hipStreamWaitEvent(c->side, c->ev_start, 0));
-  fin_fixed(c->fin_tab.p, c->rs_dev.p, c->fin_scr.p, c->side);
+  fin_fixed(c->fin_tab.p, ch.rs, ch.scr, c->side, n);
   G16_HIP(hipEventRecord(c->ev_fixed, c->side));
   run_msms(
-      c, w_dev,
+      c, ch,
       [&](hipStream_t from) {
         // A and B1 are enqueued: g_a, g1_b and the two variable-base products overlap L / B2 / H
         G16_HIP(hipEventRecord(c->ev_ab, from));
         G16_HIP(hipStreamWaitEvent(c->side, c->ev_ab, 0));
-        fin_var(c->key_dev.p, c->sums_dev.p, c->rs_dev.p, c->fin_scr.p, c->out_dev.p, c->side);
+        fin_var(c->key_dev.p, ch.sums, ch.rs, ch.scr, ch.rec, c->side, n, ch.rec_stride);
       },
       [&] {
         // the B2 sum is there: B (assembly + Fq2 inversion) hides under the H MSM
         G16_HIP(hipStreamWaitEvent(c->red, c->ev_fixed, 0));
-        fin_b(c->key_dev.p, c->sums_dev.p, c->fin_scr.p, c->out_dev.p, c->red);
+        fin_b(c->key_dev.p, ch.sums, ch.scr, ch.rec, c->red, n, ch.rec_stride);
       });
   G16_HIP(hipStreamWaitEvent(s, c->ev_side, 0));  // join
   int id = c->timer.enabled ? c->timer.begin(ST_FINALIZE, s) : -1;
   // C leaves the device in XYZZ form (the partial-record slot of out_dev is free on a world = 1 ctx): the host divides
-  fin_final_proj(c->key_dev.p, c->sums_dev.p, c->fin_scr.p, c->part_dev(), s);
+  fin_final_proj(c->key_dev.p, ch.sums, ch.scr, ch.proj, s, n, FIN_PROJ_BYTES);
   c->timer.end(id, s);
-  G16_HIP(hipMemcpyAsync(c->pin_io + 64, c->out_dev.p, G16_PROOF_BYTES, hipMemcpyDeviceToHost, s));
-  G16_HIP(hipMemcpyAsync(c->pin_io + 64 + G16_PROOF_BYTES + FIN_PROJ_C, c->part_dev() + FIN_PROJ_C, sizeof(XYZZ<Fq>),
-                         hipMemcpyDeviceToHost, s));
+  if (ch.rec == ch.proj) {
+    G16_HIP(hipMemcpyAsync(ch.proj_host, ch.proj, (size_t)FIN_PROJ_BYTES * n, hipMemcpyDeviceToHost, s));
+  } else {
+    G16_HIP(hipMemcpyAsync(ch.rec_host, ch.rec, G16_PROOF_BYTES, hipMemcpyDeviceToHost, s));
+    G16_HIP(hipMemcpyAsync(ch.proj_host + FIN_PROJ_C, ch.proj + FIN_PROJ_C, sizeof(XYZZ<Fq>), hipMemcpyDeviceToHost, s));
+  }
+}
+
+// one whole single-device proof, enqueue only: (r, s) from and the proof to the ctx's pinned buffer
+static void enqueue_prove(g16_ctx* c, const Fr* w_dev) {
+  if (c->tbl.active) return enqueue_prove_tables(c, w_dev);
+  enqueue_prove_buckets(c, own_chunk(c, w_dev));
 }
 
 // this rank's r*A-side products: s*A and r*B1 (variable-base, one wave each) overlap its L / B2 / H MSMs
@@ -500,7 +549,7 @@ void rank_partial_enqueue(g16_ctx* c, const uint64_t r[4], const uint64_t s_[4],
   G16_HIP(hipSetDevice(c->device));
   hipStream_t s = c->stream;
   begin_sharded(c, r, s_);
-  run_msms(c, w_dev, [&](hipStream_t from) { fork_partial_var(c, from); });
+  run_msms(c, own_chunk(c, w_dev), [&](hipStream_t from) { fork_partial_var(c, from); });
   G16_HIP(hipStreamWaitEvent(s, c->ev_side, 0));
   sums_to_partial(c->sums_dev.p, c->part_dev(), s);
   G16_HIP(hipEventRecord(c->ev_part, s));
@@ -520,7 +569,7 @@ void rank_phase1_enqueue(g16_ctx* c, const uint64_t r[4], const uint64_t s_[4], 
   // rounds retires, so phases 2-3 stretch fourfold underneath (profiles/r03_rank8_timeline_*).
   // (Holding the first accumulation back until phase 2 is through was measured in round 3 -- 7.98 vs
   // 7.76 ms per rank at 2^22 / 8, equal at 2^24, profiles/r03_rank_schedule_ab.txt -- and removed.)
-  enqueue_witness_msms(c, w_dev, [&](hipStream_t from) { fork_partial_var(c, from); }, [] {});
+  enqueue_witness_msms(c, own_chunk(c, w_dev), [&](hipStream_t from) { fork_partial_var(c, from); }, [] {});
 }
 
 void rank_phase2_enqueue(g16_ctx* c, const int32_t* recv_dev, int32_t* send_dev) {
@@ -535,7 +584,7 @@ void rank_phase3_enqueue(g16_ctx* c, const int32_t* recv_dev) {
   c->wd.phase3(recv_dev, c->h_canon.p, x);
   c->sort_h.run(c->h_canon.p, c->h_hi - c->h_lo, /*mont=*/false, x);
   G16_HIP(hipEventRecord(c->ev_h, x));
-  enqueue_h_msm(c);
+  enqueue_h_msm(c, own_chunk(c, nullptr));
   G16_HIP(hipStreamWaitEvent(s, c->ev_side, 0));
   sums_to_partial(c->sums_dev.p, c->part_dev(), s);
   G16_HIP(hipEventRecord(c->ev_part, s));
@@ -945,6 +994,7 @@ g16_status g16_ctx_create_sibling(g16_ctx* donor, const g16_key_desc* key, const
 // stays until the last borrower is destroyed (round 5; rounds 3-4 printed a warning and freed anyway).
 static std::mutex g_lend_mu;
 static void batch_release(g16_ctx* c);  // the batch workspace (below)
+static bool bucket_batching(const g16_ctx* c);  // (below)
 
 void g16_ctx_destroy(g16_ctx* c) {
   if (!c) return;
@@ -1340,6 +1390,7 @@ g16_status g16_ctx_info(const g16_ctx* c, uint32_t out[16]) {
     g16_status st = g16_ctx_info(multi_child(const_cast<g16_ctx*>(c), 0), out);
     out[12] = (uint32_t)multi_size(c);
     out[14] = c->peer_state;
+    out[15] &= ~4u;  // a multi-device ctx loops over sharded proofs
     return st;
   }
   memset(out, 0, 16 * sizeof(uint32_t));
@@ -1351,7 +1402,9 @@ g16_status g16_ctx_info(const g16_ctx* c, uint32_t out[16]) {
   out[10] = c->w_hi - c->w_lo;
   out[11] = c->h_hi - c->h_lo;
   out[13] = c->world > 1 ? (c->shard_buckets ? G16_SHARD_BUCKETS : G16_SHARD_POINTS) : 0;
-  out[15] = (c->tbl.active ? 1u : 0u) | (c->sparse_b ? 2u : 0u);
+  // bit 2: a chunk of g16_prove_batch is enqueued once (table path, or the bucket path below its size threshold)
+  out[15] = (c->tbl.active ? 1u : 0u) | (c->sparse_b ? 2u : 0u) |
+            ((c->has_key && (c->tbl.active || bucket_batching(c))) ? 4u : 0u);
   return G16_OK;
 }
 
@@ -1371,20 +1424,63 @@ void* g16_witness_buffer(g16_ctx* c) {
 
 // ---- batches: many witnesses under one key --------------------------------------------------------
 // Chunk rule: the largest B whose workspace (batch_bytes_per_proof x B) fits a quarter of the device memory
-// free at the call, at most G16_BATCH_CAP, at least 1; a larger count loops over chunks.
+// free at the call, at most G16_BATCH_CAP, at least 1; a larger count loops over chunks.  Bucket-path ctxs
+// (no tables) also keep B x nb buckets -- the chunk's bucket ids -- within what the sort's 2^MSM_PART_BITS_MAX
+// level-1 partitions hold at 4096 buckets each (msm.h, msm_part_bits: beyond it level 2 falls back to one
+// global atomic per entry), and B x (entries of one proof) below 2^32 (32-bit positions); and they batch only
+// up to G16_BATCH_BUCKET_MAX_N (below).
 static constexpr uint32_t G16_BATCH_CAP = 256;
+// Bucket-path ctxs whose domain (g16_ctx_info out[8], Prover.info()["domain_size"]) exceeds this prove a batch
+// one proof after the other (chunks of one).  A chunk saves latency, not work: measured on one MI355X against the
+// prove_dev loop at B = 64 (profiles/batch_bucket_bench.jsonl), chains of 2^15 / 2^16 / 2^17 / 2^18 / 2^20
+// constraints ran 6.5x / 4.2x / 2.8x / 1.8x / 1.2x -- the gain falls towards 1x as the MSMs become throughput
+// bound, while the chunk's sorts and workspaces grow with the key.  Batching stops at the largest size measured.
+static constexpr uint32_t G16_BATCH_BUCKET_MAX_N = 1u << 20;
 
-static size_t batch_bytes_per_proof(const g16_ctx* c) {
+// G16_BATCH_BUCKET_MAX_N (measurement only: scripts/bench_batch.py --force-chunks) replaces the threshold, so that
+// chunks can be timed where the product proves one at a time
+static uint32_t batch_bucket_max_n() {
+  static const uint32_t v = [] {
+    const char* e = getenv("G16_BATCH_BUCKET_MAX_N");
+    return e ? (uint32_t)strtoul(e, nullptr, 0) : G16_BATCH_BUCKET_MAX_N;
+  }();
+  return v;
+}
+
+// a bucket-path ctx that enqueues a chunk once (g16_ctx_info out[15] bit 2)
+static bool bucket_batching(const g16_ctx* c) {
+  return c->has_key && !c->multi && !c->tbl.active && c->world == 1 && !c->dist_wm && c->n <= batch_bucket_max_n();
+}
+
+static size_t batch_bytes_per_proof(const g16_ctx* c, bool prove) {
   size_t b = (size_t)c->N * sizeof(Fr) + 2 * sizeof(Fr) + sizeof(ProofSums) + sizeof(FinScratch) + FIN_PROJ_BYTES;
   b += c->wm.batch_bytes_per_witness();
   if (c->tbl.active) b += c->tbl.batch_bytes_per_proof();
+  if (prove && bucket_batching(c)) {
+    // a proof's share of the chunk's sorts and workspaces: pairs, counts / offsets, entries, hot-bucket lists;
+    // partial-sum slots (three G1 sets and one G2 set over the witness sort, one over the h sort) and at most as
+    // many reduction contributions as buckets
+    const uint32_t lw = c->w_hi - c->w_lo, lh = c->h_hi - c->h_lo;
+    b += MsmSort::bytes_for(lw, c->cfg_w) + MsmSort::bytes_for(lh, c->cfg_h);
+    if (c->sparse_b) b += MsmSort::view_bytes_for(lw, c->cfg_w);
+    b += 2 * ((size_t)c->cfg_w.nb() * (3 * sizeof(MsmAcc<Fq>) + sizeof(MsmAcc<Fq2>)) +
+              (size_t)c->cfg_h.nb() * sizeof(MsmAcc<Fq>));
+  }
   return b;
 }
 
-static uint32_t batch_chunk(const g16_ctx* c, size_t count) {
+// prove: a chunk of g16_prove_batch (false: g16_witness_map_batch)
+static uint32_t batch_chunk(const g16_ctx* c, size_t count, bool prove) {
   size_t fr = 0, tot = 0;
   G16_HIP(hipMemGetInfo(&fr, &tot));
-  const size_t fit = fr / 4 / batch_bytes_per_proof(c);
+  size_t fit = fr / 4 / batch_bytes_per_proof(c, prove);
+  if (prove && !c->tbl.active) {
+    if (!bucket_batching(c)) return 1;
+    const uint64_t part_cap = (uint64_t)4096 << MSM_PART_BITS_MAX;
+    const uint64_t nb = std::max(c->cfg_w.nb(), c->cfg_h.nb());
+    const uint64_t ent = std::max<uint64_t>((uint64_t)(c->w_hi - c->w_lo) * c->cfg_w.W, (uint64_t)(c->h_hi - c->h_lo) * c->cfg_h.W);
+    fit = std::min<size_t>({fit, (size_t)(part_cap / nb), (size_t)((((uint64_t)1 << 32) - 1) / std::max<uint64_t>(ent, 1))});
+  }
   return (uint32_t)std::max<size_t>(1, std::min<size_t>({fit, (size_t)G16_BATCH_CAP, count}));
 }
 
@@ -1392,15 +1488,40 @@ static void batch_release(g16_ctx* c) {
   auto& b = c->bw;
   b.w.release(); b.rs.release(); b.abc.release(); b.spmv.release(); b.h.release();
   b.sums.release(); b.scr.release(); b.part1.release(); b.partH.release(); b.part2.release(); b.proj.release();
+  b.bk.reset();
   if (b.pin) (void)hipHostFree(b.pin);
   b.pin = nullptr;
   b.cap = 0;
 }
 
-// the workspace for chunks of up to B proofs (the ctx's streams are idle between calls)
-static void batch_reserve(g16_ctx* c, uint32_t B) {
+// what every batch call needs, for chunks of up to B proofs
+static void batch_reserve_common(g16_ctx* c, uint32_t B);
+
+// the workspace for chunks of up to B proofs (the ctx's streams are idle between calls); buckets: also the
+// bucket path's sorts and partial-sum workspaces (g16_prove_batch on a ctx without tables)
+static void batch_reserve(g16_ctx* c, uint32_t B, bool buckets) {
   auto& b = c->bw;
-  if (b.cap >= B) return;
+  if (b.cap < B) batch_reserve_common(c, B);
+  if (buckets && (!b.bk || b.bk->cap < B)) {
+    // the chunk's sorts and workspaces (as ctx_create_impl sizes the ctx's own for one proof)
+    b.bk.reset();
+    b.bk.reset(new g16_ctx::BatchWs::Buckets);
+    auto& k = *b.bk;
+    const uint32_t lw = c->w_hi - c->w_lo, lh = c->h_hi - c->h_lo;
+    k.sort_w.init(lw, c->cfg_w, B);
+    if (c->sparse_b) k.sort_b.init_view(lw, c->cfg_w, B);
+    k.sort_h.init(lh, c->cfg_h, B);
+    const uint32_t slots_w = B * c->cfg_w.nb() + c->cfg_w.max_lanes(), slots_h = B * c->cfg_h.nb() + c->cfg_h.max_lanes();
+    const uint32_t nc_w = msm_contrib_cap(c->cfg_w, B), nc_h = msm_contrib_cap(c->cfg_h, B);
+    k.work1.init(slots_w, nc_w, (int)B * c->cfg_w.D, 3);
+    k.workH.init(slots_h, nc_h, (int)B * c->cfg_h.D, 1);
+    k.work2.init(slots_w, nc_w, (int)B * c->cfg_w.D);
+    k.cap = B;
+  }
+}
+
+static void batch_reserve_common(g16_ctx* c, uint32_t B) {
+  auto& b = c->bw;
   batch_release(c);
   b.w.alloc((size_t)B * c->N);
   b.rs.alloc((size_t)B * 2);
@@ -1442,8 +1563,10 @@ static g16_status prove_batch(g16_ctx* c, size_t count, const uint64_t* r, const
   if (c->dist_wm) return fail(c, G16_ERR_INVALID, "dist_wm ctx: use the g16_prove_dist_phase* calls");
   return guarded(c, [&]() -> g16_status {
     hipStream_t s = c->stream;
-    if (!c->tbl.active) {
-      // bucket path: the single-proof enqueue once per proof (a correct fallback, not a faster one)
+    // (one bucket-path proof: the single-proof enqueue, without asking the runtime for its free memory)
+    const uint32_t B = (!c->tbl.active && count == 1) ? 1u : batch_chunk(c, count, /*prove=*/true);
+    if (!c->tbl.active && B == 1) {
+      // chunks of one (a large key, little free memory, a single proof): the single-proof enqueue once per proof
       for (size_t i = 0; i < count; ++i) {
         const Fr* wi = (const Fr*)((const uint8_t*)w + i * wb);
         if (!w_on_device) {
@@ -1459,8 +1582,7 @@ static g16_status prove_batch(g16_ctx* c, size_t count, const uint64_t* r, const
       collect_times(c);
       return G16_OK;
     }
-    const uint32_t B = batch_chunk(c, count);
-    batch_reserve(c, B);
+    batch_reserve(c, B, /*buckets=*/!c->tbl.active);
     auto& bw = c->bw;
     uint8_t* rs_host = bw.pin;
     uint8_t* proj_host = bw.pin + (size_t)bw.cap * 64;
@@ -1474,6 +1596,17 @@ static g16_status prove_batch(g16_ctx* c, size_t count, const uint64_t* r, const
       if (!w_on_device) {
         G16_HIP(hipMemcpyAsync(bw.w.p, wz, (size_t)n * wb, hipMemcpyHostToDevice, s));
         wz = bw.w.p;
+      }
+      if (!c->tbl.active) {
+        auto& k = *bw.bk;
+        const BucketChunk ch{n,          wz,          c->N,       bw.abc.p,  bw.spmv.p, bw.h.p,   bw.sums.p,
+                             &k.sort_w,  &k.sort_h,   &k.sort_b,  &k.work1,  &k.workH,  &k.work2,
+                             bw.rs.p,    rs_host,     bw.scr.p,   bw.proj.p, bw.proj.p, (uint32_t)FIN_PROJ_BYTES,
+                             proj_host,  proj_host};
+        enqueue_prove_buckets(c, ch);
+        G16_HIP(hipStreamSynchronize(s));
+        fin_host_affine_c_batch(proj_host, n, proofs_out + done * G16_PROOF_BYTES);
+        continue;
       }
       const TabChunk ch{n,         wz,        c->N,       bw.rs.p,    rs_host,    bw.abc.p,  bw.spmv.p, bw.h.p,
                         bw.sums.p, bw.scr.p,  bw.part1.p, bw.partH.p, bw.part2.p, bw.proj.p, proj_host};
@@ -1505,8 +1638,8 @@ g16_status g16_witness_map_batch(g16_ctx* c, size_t count, const uint64_t* w, si
   if (check_w(c, n_vars) != G16_OK) return G16_ERR_INVALID;
   return guarded(c, [&]() -> g16_status {
     hipStream_t s = c->stream;
-    const uint32_t B = batch_chunk(c, count);
-    batch_reserve(c, B);
+    const uint32_t B = batch_chunk(c, count, /*prove=*/false);
+    batch_reserve(c, B, /*buckets=*/false);
     auto& bw = c->bw;
     const size_t wn = (size_t)c->N * 4, hn = (size_t)c->n * 4;  // u64 words of one witness / one h
     for (size_t done = 0; done < count; done += B) {

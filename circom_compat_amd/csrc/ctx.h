@@ -104,6 +104,15 @@ struct g16_ctx {
     g16::DevBuf<g16::G2XYZZ29> part2;         // [cap][blocks_w2]
     g16::DevBuf<uint8_t> proj;                // [cap][FIN_PROJ_BYTES]
     uint8_t* pin = nullptr;                   // page-locked: [cap][64] (r, s) | [cap][FIN_PROJ_BYTES] records
+    // bucket path (no tables): the chunk's sorts (cap proofs each: pairs, counts / offsets, entries, hot-bucket
+    // lists) and partial-sum workspaces (slots, contributions, set sums for cap x nb buckets)
+    struct Buckets {
+      uint32_t cap = 0;
+      g16::MsmSort sort_w, sort_h, sort_b;
+      g16::MsmWork<g16::Fq> work1, workH;
+      g16::MsmWork<g16::Fq2> work2;
+    };
+    std::unique_ptr<Buckets> bk;
   } bw;
 
   g16::StageTimer timer;

@@ -51,18 +51,24 @@ struct FinScratch {  // per proof
 };
 
 void fin_build_tables(const KeyHeaderDev* key, FinTables* tab, hipStream_t stream);
-void fin_fixed(const FinTables* tab, const Fr* rs_dev, FinScratch* scr, hipStream_t stream);
+// fin_fixed / fin_var / fin_b / fin_final_proj, count > 1: one launch for the proofs z < count of a chunk --
+// (r, s) at rs_dev + 2 z, sums[z], scr[z], proof z's record rec_stride bytes after proof z - 1's (A at +0, B at
+// +64 as in the proof; C's XYZZ at +FIN_PROJ_C)
+void fin_fixed(const FinTables* tab, const Fr* rs_dev, FinScratch* scr, hipStream_t stream, uint32_t count = 1);
 void fin_var(const KeyHeaderDev* key, const ProofSums* sums, const Fr* rs_dev, FinScratch* scr,
-             uint8_t* proof_dev, hipStream_t stream);
+             uint8_t* proof_dev, hipStream_t stream, uint32_t count = 1, uint32_t rec_stride = 0);
 void fin_b(const KeyHeaderDev* key, const ProofSums* sums, const FinScratch* scr, uint8_t* proof_dev,
-           hipStream_t stream);
+           hipStream_t stream, uint32_t count = 1, uint32_t rec_stride = 0);
 void fin_final(const KeyHeaderDev* key, const ProofSums* sums, const FinScratch* scr,
                uint8_t* proof_dev, hipStream_t stream);
 // fin_final with C left in XYZZ form at proj_dev + FIN_PROJ_C (below); fin_host_affine_c divides on the host and
 // writes proof[192, 256): the single-device prover's tail (g16_prove / g16_prove_dev)
 void fin_final_proj(const KeyHeaderDev* key, const ProofSums* sums, const FinScratch* scr, uint8_t* proj_dev,
-                    hipStream_t stream);
+                    hipStream_t stream, uint32_t count = 1, uint32_t rec_stride = 0);
 void fin_host_affine_c(const uint8_t* proj_host, uint8_t* proof_out);
+// count records FIN_PROJ_BYTES apart -> A, B (copied) and C of count proofs 256 bytes apart, one field inversion
+// for the chunk (same bytes as fin_host_affine_c)
+void fin_host_affine_c_batch(const uint8_t* proj_host, size_t count, uint8_t* proofs_out);
 
 // ---- sharded provers (one process per GPU) ----------------------------------------------------
 // The variable-base products of the finalisation are linear in the MSM sums, so every rank

@@ -68,9 +68,12 @@ __global__ void k_fin_tables(const KeyHeaderDev* key, FinTables* tab) {
 __device__ __forceinline__ bool bit_of(const U256& k, int i) { return (k.v[i >> 5] >> (i & 31)) & 1u; }
 
 // blocks 0..2: k * delta1 for k = r, s, rs; block 3: s * delta2.  Thread t owns bits t and t+128.
+// grid.y = proof z of a chunk: (r, s) = rs[2 z], rs[2 z + 1] -> scr[z]
 __global__ void __launch_bounds__(FIN_T) k_fin_fixed(const FinTables* tab, const Fr* rs,
                                                      FinScratch* scr) {
   G16_DYN_SMEM(smem_raw);
+  rs += 2 * blockIdx.y;
+  scr += blockIdx.y;
   const int t = threadIdx.x;
   const Fr r = rs[0], s = rs[1];
   const int b = blockIdx.x;
@@ -234,10 +237,16 @@ __device__ G1XYZZ29 var_mul(const G1XYZZ29& P, const U256& k, G1XYZZ29* tbl) {
 }
 
 // block 0: g_a, A, s*g_a      block 1: g1_b, r*g1_b
+// (k_fin_var, k_fin_b, k_fin_final_proj: grid.y = proof z of a chunk -- sums[z], rs[2 z], scr[z], its record
+// rec_stride bytes after proof z - 1's)
 __global__ void __launch_bounds__(64) k_fin_var(const KeyHeaderDev* key, const ProofSums* sums,
-                                                const Fr* rs, FinScratch* scr, uint8_t* proof) {
+                                                const Fr* rs, FinScratch* scr, uint8_t* proof, uint32_t rec_stride) {
   __shared__ G1XYZZ29 tbl[16];
   if (threadIdx.x != 0) return;
+  sums += blockIdx.y;
+  rs += 2 * blockIdx.y;
+  scr += blockIdx.y;
+  proof += (size_t)blockIdx.y * rec_stride;
   const int b = blockIdx.x;
   G1XYZZ29 g = b == 0 ? scr->rd1 : scr->sd1;
   g.madd(affine_from_mont256<Fq>(b == 0 ? key->a0 : key->b1_0));
@@ -264,8 +273,11 @@ __global__ void __launch_bounds__(64) k_fin_final(const KeyHeaderDev* key, const
 // conversion is 0.2 ms on one GPU lane -- on the critical path of EVERY proof, behind the last reduction -- and ~5 us
 // on the host, which waits for these bytes anyway (round 6; the table path has done so since round 5).
 __global__ void __launch_bounds__(64) k_fin_final_proj(const KeyHeaderDev* key, const ProofSums* sums,
-                                                       const FinScratch* scr, uint8_t* proj) {
+                                                       const FinScratch* scr, uint8_t* proj, uint32_t rec_stride) {
   if (threadIdx.x != 0) return;
+  sums += blockIdx.y;
+  scr += blockIdx.y;
+  proj += (size_t)blockIdx.y * rec_stride;
   G1XYZZ29 c = scr->sga;
   c.add(scr->rgb);
   c.add(scr->rsd1.neg());
@@ -277,8 +289,11 @@ __global__ void __launch_bounds__(64) k_fin_final_proj(const KeyHeaderDev* key, 
 // g2_b -> B (needs only s * delta2 and the B2 sum: runs as soon as the B2 reduction is done,
 // underneath the H MSM)
 __global__ void __launch_bounds__(64) k_fin_b(const KeyHeaderDev* key, const ProofSums* sums,
-                                              const FinScratch* scr, uint8_t* proof) {
+                                              const FinScratch* scr, uint8_t* proof, uint32_t rec_stride) {
   if (threadIdx.x != 0) return;
+  sums += blockIdx.y;
+  scr += blockIdx.y;
+  proof += (size_t)blockIdx.y * rec_stride;
   G2XYZZ29 b = scr->sd2;
   b.madd(affine_from_mont256<Fq2>(key->b2_0));
   b.add(sums->B2);
@@ -517,24 +532,24 @@ __global__ void __launch_bounds__(64) k_partials_to_sums(const uint8_t* parts, i
 void fin_build_tables(const KeyHeaderDev* key, FinTables* tab, hipStream_t stream) {
   G16_LAUNCH(k_fin_tables, 4, 64, 0, stream, key, tab);
 }
-void fin_fixed(const FinTables* tab, const Fr* rs_dev, FinScratch* scr, hipStream_t stream) {
-  G16_LAUNCH(k_fin_fixed, 4, FIN_T, FIN_T * sizeof(G2XYZZ29), stream, tab, rs_dev, scr);
+void fin_fixed(const FinTables* tab, const Fr* rs_dev, FinScratch* scr, hipStream_t stream, uint32_t count) {
+  G16_LAUNCH(k_fin_fixed, dim3(4, count), FIN_T, FIN_T * sizeof(G2XYZZ29), stream, tab, rs_dev, scr);
 }
 void fin_var(const KeyHeaderDev* key, const ProofSums* sums, const Fr* rs_dev, FinScratch* scr,
-             uint8_t* proof_dev, hipStream_t stream) {
-  G16_LAUNCH(k_fin_var, 2, 64, 0, stream, key, sums, rs_dev, scr, proof_dev);
+             uint8_t* proof_dev, hipStream_t stream, uint32_t count, uint32_t rec_stride) {
+  G16_LAUNCH(k_fin_var, dim3(2, count), 64, 0, stream, key, sums, rs_dev, scr, proof_dev, rec_stride);
 }
 void fin_final(const KeyHeaderDev* key, const ProofSums* sums, const FinScratch* scr,
                uint8_t* proof_dev, hipStream_t stream) {
   G16_LAUNCH(k_fin_final, 1, 64, 0, stream, key, sums, scr, proof_dev);
 }
 void fin_final_proj(const KeyHeaderDev* key, const ProofSums* sums, const FinScratch* scr, uint8_t* proj_dev,
-                    hipStream_t stream) {
-  G16_LAUNCH(k_fin_final_proj, 1, 64, 0, stream, key, sums, scr, proj_dev);
+                    hipStream_t stream, uint32_t count, uint32_t rec_stride) {
+  G16_LAUNCH(k_fin_final_proj, dim3(1, count), 64, 0, stream, key, sums, scr, proj_dev, rec_stride);
 }
 void fin_b(const KeyHeaderDev* key, const ProofSums* sums, const FinScratch* scr, uint8_t* proof_dev,
-           hipStream_t stream) {
-  G16_LAUNCH(k_fin_b, 1, 64, 0, stream, key, sums, scr, proof_dev);
+           hipStream_t stream, uint32_t count, uint32_t rec_stride) {
+  G16_LAUNCH(k_fin_b, dim3(1, count), 64, 0, stream, key, sums, scr, proof_dev, rec_stride);
 }
 void fin_partial_var(ProofSums* sums, const Fr* rs_dev, hipStream_t stream) {
   G16_LAUNCH(k_fin_partial_var, 2, 64, 0, stream, sums, rs_dev);
@@ -711,6 +726,39 @@ void fin_host_affine_c(const uint8_t* proj, uint8_t* proof) {
   memcpy((void*)&c, proj + FIN_PROJ_C, sizeof c);
   const G1Affine pc = host_affine<Fq>(c);
   memcpy(proof + 192, (const void*)&pc, 64);
+}
+
+// A, B and C of a chunk, C with one inversion (Montgomery's trick, as fin_tab_host_affine_batch): points at infinity and zero
+// denominators stay out of the product, so every inverse is the one host_inv returns -- the same bytes
+void fin_host_affine_c_batch(const uint8_t* proj, size_t count, uint8_t* proofs) {
+  std::vector<XYZZ<Fq>> c(count);
+  std::vector<Fq> pre(count + 1), inv(count);
+  std::vector<uint8_t> live(count);
+  const Fq zero = Fq::zero();
+  pre[0] = Fq::one();
+  for (size_t z = 0; z < count; ++z) {
+    memcpy((void*)&c[z], proj + z * FIN_PROJ_BYTES + FIN_PROJ_C, sizeof c[z]);
+    live[z] = !c[z].is_inf() && !(c[z].zzz == zero);
+    pre[z + 1] = live[z] ? pre[z] * c[z].zzz : pre[z];
+  }
+  Fq t = host_inv(pre[count]);
+  for (size_t z = count; z-- > 0;) {
+    if (!live[z]) {
+      inv[z] = zero;
+      continue;
+    }
+    inv[z] = t * pre[z];
+    t = t * c[z].zzz;
+  }
+  for (size_t z = 0; z < count; ++z) {
+    G1Affine pc = G1Affine::infinity();
+    if (!c[z].is_inf()) {
+      const Fq iz2 = inv[z].sqr() * c[z].zz.sqr();
+      pc = G1Affine{c[z].x * iz2, c[z].y * inv[z]};
+    }
+    memcpy(proofs + z * 256, proj + z * FIN_PROJ_BYTES, 192);  // A | B, affine on the device (fin_var, fin_b)
+    memcpy(proofs + z * 256 + 192, (const void*)&pc, 64);
+  }
 }
 
 void fin_tab_pre(const KeyHeaderDev* key, FinScratch* scr, hipStream_t stream, uint32_t count) {

@@ -131,10 +131,15 @@ G16_HD uint32_t msm_seg_len(uint32_t M, uint32_t lanes) {
   return S < (uint32_t)MSM_MIN_SEG ? (uint32_t)MSM_MIN_SEG : S;
 }
 
-// Sorted (bucket -> entries) view of one scalar vector.  entry = idx | plane << cfg.idx_bits | neg << 31.
+// Sorted (bucket -> entries) view of one scalar vector -- or of a CHUNK of `nproof` vectors of the same
+// length (batched proving: one sort, one accumulation, one reduction for every proof of the chunk).  entry =
+// idx | plane << cfg.idx_bits | neg << 31 names a point of the key whatever the proof; proof z's buckets are
+// z nb + set B + digit (proof-major), so the chunk is one MSM problem with nproof D bucket sets of B buckets.
 struct MsmSort {
   MsmConfig cfg;
   uint32_t cap = 0, len = 0;
+  uint32_t nproof = 1, nproof_cap = 1;  // proofs of the last run / proofs init() sized the buffers for
+  uint32_t nbt() const { return nproof * cfg.nb(); }  // buckets of the last run
   DevBuf<MsmPair> part;  // level-1 output: (entry, bucket) pairs ordered by partition
   // multi_l / meta: hot buckets of the G1 segmentation (cfg.lanes), multi_l2 / meta2: of the G2 one; meta[1] = their number
   DevBuf<uint32_t> count, offset, cursor, entries, multi_l, meta, multi_l2, meta2, scan_tmp;
@@ -153,28 +158,29 @@ struct MsmSort {
   DevBuf<uint32_t> range;
   const uint32_t* range_dev() const { return world > 1 ? range.p : nullptr; }
 
-  void init(uint32_t capacity, const MsmConfig& cfg);
+  void init(uint32_t capacity, const MsmConfig& cfg, uint32_t nproof_cap = 1);
   void set_shard(int rank, int world);
-  // scalars: `n` field elements (Montgomery Fr when mont, else canonical U256) in device memory
-  void run(const void* scalars, uint32_t n, bool mont, hipStream_t stream);
+  // scalars: `n` field elements (Montgomery Fr when mont, else canonical U256) in device memory; a chunk:
+  // proof z's n scalars at scalars + z stride (in elements), z < nproof (<= nproof_cap, unsharded only)
+  void run(const void* scalars, uint32_t n, bool mont, hipStream_t stream, uint32_t nproof = 1, size_t stride = 0);
   // A filtered VIEW of another (unsharded) sort over the same scalars: level 2 re-run over src's level-1
   // pairs without the points whose bit in keep_bits is clear (msm_sort.hip).  The B queries of a real
   // circom key hold the point at infinity for every wire that appears in no B row: a third of the wires
   // of a Poseidon chain; the shared witness sort would spend a full G2 mixed addition on each.
-  void init_view(uint32_t capacity, const MsmConfig& cfg);
+  void init_view(uint32_t capacity, const MsmConfig& cfg, uint32_t nproof_cap = 1);
   void release_view() {  // a view whose allocation failed half way: back to the empty state
     count.release(); offset.release(); cursor.release(); entries.release(); multi_l.release();
     meta.release(); multi_l2.release(); meta2.release(); scan_tmp.release();
     cap = len = 0;
   }
   void run_view(const MsmSort& src, const uint32_t* keep_bits, hipStream_t stream);
-  static size_t view_bytes_for(uint32_t capacity, const MsmConfig& cfg) {
-    const uint64_t M = (uint64_t)capacity * cfg.W;
-    return (size_t)(M * 4 + 3 * ((uint64_t)cfg.nb() + 1) * 4 + 2 * (M / ((uint64_t)MSM_MIN_SEG * MSM_SMALL_MULTI) + 2) * 4 + 4096);
+  static size_t view_bytes_for(uint32_t capacity, const MsmConfig& cfg, uint32_t nproof = 1) {
+    const uint64_t M = (uint64_t)nproof * capacity * cfg.W;
+    return (size_t)(M * 4 + 3 * ((uint64_t)nproof * cfg.nb() + 1) * 4 + 2 * (M / ((uint64_t)MSM_MIN_SEG * MSM_SMALL_MULTI) + 2) * 4 + 4096);
   }
   size_t device_bytes() const;
-  // what init(capacity, cfg) allocates (the memory plan of g16_ctx_create: api.hip, plan_msm_configs)
-  static size_t bytes_for(uint32_t capacity, const MsmConfig& cfg);
+  // what init(capacity, cfg, nproof) allocates (the memory plan of g16_ctx_create: api.hip, plan_msm_configs)
+  static size_t bytes_for(uint32_t capacity, const MsmConfig& cfg, uint32_t nproof = 1);
 };
 
 // accumulator type of the kernels: XYZZ over the lazy 9 x 29-bit limbs (field29.h / ec29.h)
@@ -244,9 +250,10 @@ inline size_t msm_work_bytes(uint32_t n_slots, uint32_t n_contrib, int max_sets,
 
 // out_dev[0] = sum_i scalar_i * P_{i - idx_min} over the entries of `s` with idx >= idx_min
 // (lazy internal form; finalize.hip converts to the storage form when it writes the proof).
+// (a chunk sort: proof z's sum at out_dev + z out_stride bytes, msm_reduce)
 template <class F>
 void msm_run(const MsmSort& s, const MsmPoints<F>& pts, uint32_t idx_min, MsmWork<F>& work,
-             MsmAcc<F>* out_dev, hipStream_t stream, StageTimer* tm = nullptr);
+             MsmAcc<F>* out_dev, hipStream_t stream, StageTimer* tm = nullptr, size_t out_stride = 0);
 // The two halves of msm_run, for MSMs that share a sort (A, B1, L over the witness scalars): their
 // accumulations go into different workspace slots and ONE batched reduction finishes all of them.
 // fixup = false (G1 only): just the optimistic kernel; the caller runs msm_fixup on the stream that
@@ -269,9 +276,22 @@ void msm_accumulate_pair(const MsmSort& s, const MsmPoints<F>& a, const MsmPoint
 template <class F>
 void msm_fixup_pair(const MsmSort& s, const MsmPoints<F>& a, const MsmPoints<F>& b, MsmWork<F>& work,
                     int slot, hipStream_t stream, StageTimer* tm = nullptr);
+// A chunk sort (s.nproof > 1): proof z's nbatch sums go to out_dev + z out_stride BYTES (sizeof(ProofSums)).
 template <class F>
 void msm_reduce(const MsmSort& s, MsmWork<F>& work, int first_slot, int nbatch, MsmAcc<F>* out_dev,
-                hipStream_t stream, StageTimer* tm = nullptr, bool hidden = false);
+                hipStream_t stream, StageTimer* tm = nullptr, bool hidden = false, size_t out_stride = 0);
+// contributions (MsmWork::ncontrib) that msm_reduce needs for any chunk of <= nproof_cap proofs and <= 3 MSMs
+inline uint32_t msm_contrib_cap(const MsmConfig& cfg, uint32_t nproof_cap) {
+  uint32_t m = 1;
+  for (uint32_t z = 1; z <= nproof_cap; ++z)
+    for (uint32_t nbatch = 1; nbatch <= 3; ++nbatch)
+      for (int hidden = 0; hidden < 2; ++hidden) {
+        const uint32_t rc = msm_red_chunk(cfg, nbatch * z, 1, hidden != 0);
+        const uint32_t v = (uint32_t)(((uint64_t)cfg.B + rc - 1) / rc) * (uint32_t)cfg.D * z;
+        if (v > m) m = v;
+      }
+  return m;
+}
 
 
 

@@ -473,11 +473,13 @@ __global__ void __launch_bounds__(SUM_THREADS)
 }
 
 // total = sum_d 2^(c*d) wsum[d]   (D == 1: plain copy)
+// grid.x = MSM of the batch, grid.y = proof z of a chunk sort: its D sets follow proof z - 1's, its sums are
+// out_stride bytes after proof z - 1's
 template <class F>
-__global__ void k_horner(const MsmAcc<F>* wsum, int stride, int D, int c, MsmAcc<F>* out) {
+__global__ void k_horner(const MsmAcc<F>* wsum, int stride, int D, int c, MsmAcc<F>* out, size_t out_stride) {
   if (threadIdx.x != 0) return;
-  wsum += (size_t)blockIdx.x * stride;  // one block per MSM of the batch
-  out += blockIdx.x;
+  wsum += (size_t)blockIdx.x * stride + (size_t)blockIdx.y * D;
+  out = reinterpret_cast<MsmAcc<F>*>(reinterpret_cast<char*>(out) + (size_t)blockIdx.y * out_stride) + blockIdx.x;
   MsmAcc<F> t = wsum[D - 1];
   for (int d = D - 2; d >= 0; --d) {
     for (int s = 0; s < c; ++s) t.dbl_in_place();
@@ -555,7 +557,7 @@ template <class F>
 void msm_accumulate(const MsmSort& s, const MsmPoints<F>& P, uint32_t idx_min, MsmWork<F>& work,
                     int slot, hipStream_t stream, StageTimer* tm, bool fixup) {
   const MsmConfig& cfg = s.cfg;
-  const uint32_t nb = cfg.nb();
+  const uint32_t nb = s.nbt();  // a chunk sort: the buckets of every proof
   const int acc_stage = sizeof(F) == sizeof(Fq) ? ST_MSM_ACC_G1 : ST_MSM_ACC_G2;
   if (slot < 0 || slot >= work.batch) throw std::runtime_error("msm_accumulate: bad workspace slot");
   // persistent grid: `lanes` lanes, each owning an equal segment of the sorted entry list
@@ -608,7 +610,7 @@ void msm_fixup(const MsmSort& s, const MsmPoints<F>& P, uint32_t idx_min, MsmWor
   if (!acc_fast()) return;
   const int tid = tm ? tm->begin(ST_MSM_FIXUP, stream) : -1;
   const MsmConfig& cfg = s.cfg;
-  const uint32_t nb = cfg.nb();
+  const uint32_t nb = s.nbt();  // a chunk sort: the buckets of every proof
   const uint32_t lanes = s.lanes_of(sizeof(F) != sizeof(Fq));
   const uint32_t grid = lanes / ACC_THREADS;
   MsmAcc<F>* out = work.partial.p + (size_t)slot * work.slots;
@@ -640,7 +642,7 @@ template <class F>
 void msm_accumulate_pair(const MsmSort& s, const MsmPoints<F>& A, const MsmPoints<F>& B,
                          MsmWork<F>& work, int slot, hipStream_t stream, StageTimer* tm, bool fixup) {
   const MsmConfig& cfg = s.cfg;
-  const uint32_t nb = cfg.nb();
+  const uint32_t nb = s.nbt();  // a chunk sort: the buckets of every proof
   const int acc_stage = ST_MSM_ACC_G1_PAIR;
   if (slot < 0 || slot + 2 > work.batch) throw std::runtime_error("msm_accumulate_pair: bad workspace slot");
   if (A.stride != 2 || B.stride != 2 || A.data() != B.data() || A.off != 0 || B.off != 1 ||
@@ -674,7 +676,7 @@ void msm_fixup_pair(const MsmSort& s, const MsmPoints<F>& A, const MsmPoints<F>&
     if (!acc_fast()) return;
     const int tid = tm ? tm->begin(ST_MSM_FIXUP, stream) : -1;
     const MsmConfig& cfg = s.cfg;
-    const uint32_t nb = cfg.nb();
+    const uint32_t nb = s.nbt();  // a chunk sort: the buckets of every proof
     const uint32_t grid = cfg.lanes / (ACC_THREADS / 2);
     MsmAcc<F>* out = work.partial.p + (size_t)slot * work.slots;
     MsmFixList* fix = work.fix.p + slot;
@@ -690,11 +692,14 @@ void msm_fixup_pair(const MsmSort& s, const MsmPoints<F>& A, const MsmPoints<F>&
 // Bucket reduction of `nbatch` MSMs (workspace slots first_slot ...) that were accumulated over
 // the SAME sort: the reduction is a chain of dependent EC additions (~0.3-0.5 ms of latency
 // whatever the size), so MSMs sharing a sort pay it once.  out_dev: nbatch consecutive sums.
+// A chunk sort (s.nproof proofs) is reduced as nproof D bucket sets -- proof z's sets are z D .. z D + D - 1
+// (MsmSort: bucket z nb + set B + digit) -- and k_horner folds each proof's D sets into out_dev + z out_stride.
 template <class F>
 void msm_reduce(const MsmSort& s, MsmWork<F>& work, int first_slot, int nbatch, MsmAcc<F>* out_dev,
-                hipStream_t stream, StageTimer* tm, bool hidden) {
+                hipStream_t stream, StageTimer* tm, bool hidden, size_t out_stride) {
   const MsmConfig& cfg = s.cfg;
-  const uint32_t nb = cfg.nb();
+  const uint32_t nb = s.nbt();  // a chunk sort: the buckets of every proof
+  const uint32_t sets = (uint32_t)cfg.D * s.nproof;
   if (first_slot < 0 || nbatch < 1 || first_slot + nbatch > work.batch)
     throw std::runtime_error("msm_reduce: bad workspace slots");
   MsmAcc<F>* partial = work.partial.p + (size_t)first_slot * work.slots;
@@ -707,10 +712,11 @@ void msm_reduce(const MsmSort& s, MsmWork<F>& work, int first_slot, int nbatch, 
   // buckets per thread: the running sums are a dependent chain of EC additions (~10 us each on
   // one lane): see msm_red_chunk for the thread count this aims at
   const uint32_t* rng = s.range_dev();  // bucket-range sharding: this rank's run of the bucket set
-  const uint32_t red_chunk = msm_red_chunk(cfg, (uint32_t)nbatch, (uint32_t)s.world, hidden);
+  const uint32_t red_chunk = msm_red_chunk(cfg, (uint32_t)nbatch * s.nproof, (uint32_t)s.world, hidden);
   const uint32_t cps = ceil_div(cfg.B, red_chunk);
-  const uint32_t nchunks = cps * (uint32_t)cfg.D;
+  const uint32_t nchunks = cps * sets;
   if (nchunks > work.ncontrib) throw std::runtime_error("msm_reduce: contribution buffer too small");
+  if ((int)sets > work.sets) throw std::runtime_error("msm_reduce: more bucket sets than the workspace holds");
   // the scratch of slot k starts at k * (its per-slot size): reductions of DIFFERENT slots may run on different
   // streams at the same time (round 6: the L reduction of a mid-sized proof runs on the side stream)
   MsmAcc<F>* contrib = work.contrib.p + (size_t)first_slot * work.ncontrib;
@@ -723,22 +729,22 @@ void msm_reduce(const MsmSort& s, MsmWork<F>& work, int first_slot, int nbatch, 
   uint32_t nblk = ceil_div(cps / (uint32_t)s.world, SUM_THREADS * 2);
   if (nblk > 256) nblk = 256;
   if (nblk < 1) nblk = 1;
-  G16_LAUNCH((k_set_sum<F>), dim3((uint32_t)cfg.D * nblk, nbatch), SUM_THREADS,
+  G16_LAUNCH((k_set_sum<F>), dim3(sets * nblk, nbatch), SUM_THREADS,
              SUM_THREADS * sizeof(MsmAcc<F>), stream, (const MsmAcc<F>*)contrib, cps, nblk,
              bsum, (size_t)nchunks, (size_t)256 * work.sets, rng, red_chunk);
-  G16_LAUNCH((k_set_sum<F>), dim3((uint32_t)cfg.D, nbatch), SUM_THREADS,
+  G16_LAUNCH((k_set_sum<F>), dim3(sets, nbatch), SUM_THREADS,
              SUM_THREADS * sizeof(MsmAcc<F>), stream, (const MsmAcc<F>*)bsum, nblk, 1u,
              wsum, (size_t)256 * work.sets, (size_t)work.sets, (const uint32_t*)nullptr, 1u);
-  G16_LAUNCH((k_horner<F>), nbatch, 64, 0, stream, (const MsmAcc<F>*)wsum, work.sets, cfg.D,
-             cfg.c, out_dev);
+  G16_LAUNCH((k_horner<F>), dim3(nbatch, s.nproof), 64, 0, stream, (const MsmAcc<F>*)wsum, work.sets, cfg.D,
+             cfg.c, out_dev, out_stride);
   if (tm) tm->end(id, stream);
 }
 
 template <class F>
 void msm_run(const MsmSort& s, const MsmPoints<F>& P, uint32_t idx_min, MsmWork<F>& work,
-             MsmAcc<F>* out_dev, hipStream_t stream, StageTimer* tm) {
+             MsmAcc<F>* out_dev, hipStream_t stream, StageTimer* tm, size_t out_stride) {
   msm_accumulate<F>(s, P, idx_min, work, 0, stream, tm);
-  msm_reduce<F>(s, work, 0, 1, out_dev, stream, tm);
+  msm_reduce<F>(s, work, 0, 1, out_dev, stream, tm, false, out_stride);
 }
 
 }  // namespace g16

@@ -165,10 +165,29 @@ struct SortGeom {
   uint32_t idx_bits;  // MsmConfig::idx_bits
   int sh;          // partition = bucket >> sh
   uint32_t bins1;  // number of partitions
+  // a chunk of nproof scalar vectors (MsmSort::run): n1 scalars each, proof z's at z stride, buckets + z nb1
+  uint32_t nproof, n1, nb1;
+  uint64_t stride;
 };
 
+// scalar i of the walk (i < nproof n1): its point index *li, where it is stored (*at), its bucket offset.
+// CHUNK = false (one proof): the identity, so that the single-proof kernels are the instructions they were
+template <bool CHUNK>
+__device__ __forceinline__ void chunk_pos(const SortGeom& G, uint32_t i, uint32_t* li, uint64_t* at, uint32_t* gofs) {
+  if (CHUNK) {
+    const uint32_t z = i / G.n1;
+    *li = i - z * G.n1;
+    *at = (uint64_t)z * G.stride + *li;
+    *gofs = z * G.nb1;
+  } else {
+    *li = i;
+    *at = i;
+    *gofs = 0;
+  }
+}
+
 template <bool MONT>
-__device__ __forceinline__ U256 load_scalar(const void* scalars, uint32_t i) {
+__device__ __forceinline__ U256 load_scalar(const void* scalars, uint64_t i) {
   if (MONT) return reinterpret_cast<const Fr*>(scalars)[i].to_canonical();  // ark-ff into_bigint
   return reinterpret_cast<const U256*>(scalars)[i];
 }
@@ -179,7 +198,7 @@ __device__ __forceinline__ U256 load_scalar(const void* scalars, uint32_t i) {
 // the earlier scheme reserved runs with one global atomic per (tile, partition), i.e. ~2000 atomics
 // WITH return on each of <= 1024 addresses, which the L2 serialises (0.3 ms of a 0.34 ms kernel at
 // 2^22 whether a rank kept all digits or an eighth of them).
-template <bool MONT>
+template <bool MONT, bool CHUNK>
 __global__ void __launch_bounds__(P1_THREADS) k_part_count(const void* scalars, uint32_t n,
                                                            SortGeom G, uint32_t* blk_hist) {
   __shared__ uint32_t h[P1_MAX_BINS];
@@ -191,8 +210,11 @@ __global__ void __launch_bounds__(P1_THREADS) k_part_count(const void* scalars, 
     for (int k = 0; k < P1_PER_THREAD; ++k) {
       const uint32_t i = tile * P1_TILE + k * P1_THREADS + tid;
       if (i >= n) continue;
-      const U256 sc = load_scalar<MONT>(scalars, i);
-      for_each_digit(sc, i, G.c, G.W, G.D, G.B, G.idx_bits, [&](uint32_t g, uint32_t) { atomicAdd(&h[g >> G.sh], 1u); });
+      uint32_t li, go;
+      uint64_t at;
+      chunk_pos<CHUNK>(G, i, &li, &at, &go);
+      const U256 sc = load_scalar<MONT>(scalars, at);
+      for_each_digit(sc, li, G.c, G.W, G.D, G.B, G.idx_bits, [&](uint32_t g, uint32_t) { atomicAdd(&h[(CHUNK ? g + go : g) >> G.sh], 1u); });
     }
   }
   __syncthreads();
@@ -256,7 +278,7 @@ __global__ void __launch_bounds__(64) k_pick_range(const uint32_t* __restrict__ 
 // starts at blk_off[p][block] (LDS copy) and a digit's rank is one LDS atomic -- a single digit walk,
 // no global atomics.  range != nullptr (bucket-range sharding): only the pairs of partitions
 // [range[0], range[1]) are kept, written at their position minus range[2].
-template <bool MONT>
+template <bool MONT, bool CHUNK>
 __global__ void __launch_bounds__(P1_THREADS) k_part_scatter(const void* scalars, uint32_t n,
                                                              SortGeom G,
                                                              const uint32_t* __restrict__ blk_off,
@@ -272,13 +294,15 @@ __global__ void __launch_bounds__(P1_THREADS) k_part_scatter(const void* scalars
   __syncthreads();
   for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     U256 sc[P1_PER_THREAD];
-    uint32_t idx[P1_PER_THREAD];
+    uint32_t idx[P1_PER_THREAD], go[P1_PER_THREAD];
     bool live[P1_PER_THREAD];
 #pragma unroll
     for (int k = 0; k < P1_PER_THREAD; ++k) {
-      idx[k] = tile * P1_TILE + (uint32_t)k * P1_THREADS + tid;
-      live[k] = idx[k] < n;
-      if (live[k]) sc[k] = load_scalar<MONT>(scalars, idx[k]);
+      const uint32_t i = tile * P1_TILE + (uint32_t)k * P1_THREADS + tid;
+      uint64_t at;
+      chunk_pos<CHUNK>(G, i, &idx[k], &at, &go[k]);
+      live[k] = i < n;
+      if (live[k]) sc[k] = load_scalar<MONT>(scalars, at);
       else sc[k] = U256{};
     }
     // four scalars advance window by window together: their four LDS ranks are issued back to
@@ -301,6 +325,7 @@ __global__ void __launch_bounds__(P1_THREADS) k_part_scatter(const void* scalars
             for (int u = 0; u < U; ++u) {
               v[u] = wk[u].take(w, idx[k0 + u], G.c, G.D, G.B, G.idx_bits, &g[u], &e[u]) && live[k0 + u];
               if (v[u]) {
+                if (CHUNK) g[u] += go[k0 + u];
                 const uint32_t pb = g[u] >> G.sh;
                 v[u] = pb >= p_lo && pb < p_hi;
                 if (v[u]) pos[u] = atomicAdd(&h[pb], 1u);
@@ -557,15 +582,18 @@ void MsmSort::set_shard(int rank_, int world_) {
   if (world > 1) range.alloc(8);
 }
 
-void MsmSort::init(uint32_t capacity, const MsmConfig& c) {
+void MsmSort::init(uint32_t capacity, const MsmConfig& c, uint32_t nproof_cap_) {
   cfg = c;
   cap = capacity;
+  nproof_cap = nproof_cap_ ? nproof_cap_ : 1;
+  nproof = 1;
   // an entry holds idx_bits index bits and 31 - idx_bits plane bits (msm.h); 2^27 points is also the
   // largest domain the reference accepts (witness_map.hip: PolynomialDegreeTooLarge above it)
   if (capacity > cfg.max_points() || (uint32_t)cfg.Pn > (1u << (31 - cfg.idx_bits)))
     throw std::runtime_error("MSM slice does not fit the sort entry (2^27 points x 16 planes, or 2^26 x 32)");
-  const uint32_t nb = cfg.nb();
-  const uint64_t M = (uint64_t)cap * cfg.W;
+  if ((uint64_t)nproof_cap * cfg.nb() >= ((uint64_t)1 << 32)) throw std::runtime_error("MSM bucket count exceeds 2^32");
+  const uint32_t nb = nproof_cap * cfg.nb();  // every bucket of the largest chunk
+  const uint64_t M = (uint64_t)nproof_cap * cap * cfg.W;
   if (M >= ((uint64_t)1 << 32)) throw std::runtime_error("MSM entry count exceeds 2^32");
   part.alloc(M ? M : 1);
   const size_t bins1 = (size_t)1 << msm_part_bits(nb);
@@ -585,9 +613,9 @@ void MsmSort::init(uint32_t capacity, const MsmConfig& c) {
   scan_tmp.alloc(ceil_div(scan_len, SCAN_TILE) + 1);
 }
 
-size_t MsmSort::bytes_for(uint32_t capacity, const MsmConfig& cfg) {
-  const uint64_t M = std::max<uint64_t>((uint64_t)capacity * cfg.W, 1);
-  const uint64_t nb = cfg.nb();
+size_t MsmSort::bytes_for(uint32_t capacity, const MsmConfig& cfg, uint32_t nproof) {
+  const uint64_t M = std::max<uint64_t>((uint64_t)nproof * capacity * cfg.W, 1);
+  const uint64_t nb = (uint64_t)nproof * cfg.nb();
   const uint64_t bins1 = (uint64_t)1 << msm_part_bits((uint32_t)nb);
   const uint64_t hist = bins1 * sort_grid_cap() + 1;
   const uint64_t large = M / ((uint64_t)MSM_MIN_SEG * MSM_SMALL_MULTI) + 2;
@@ -600,11 +628,19 @@ size_t MsmSort::device_bytes() const {
          multi_l.bytes();
 }
 
-void MsmSort::run(const void* scalars, uint32_t n, bool mont, hipStream_t s) {
-  if (n > cap) throw std::runtime_error("MsmSort::run: more scalars than capacity");
-  len = n;
-  const uint32_t nb = cfg.nb();
+void MsmSort::run(const void* scalars, uint32_t n1, bool mont, hipStream_t s, uint32_t nproof_, size_t stride) {
+  if (n1 > cap) throw std::runtime_error("MsmSort::run: more scalars than capacity");
+  if (nproof_ < 1 || nproof_ > nproof_cap) throw std::runtime_error("MsmSort::run: more proofs than the chunk capacity");
+  if (nproof_ > 1 && world > 1) throw std::runtime_error("MsmSort::run: a sharded sort takes one proof");
+  len = n1;
+  nproof = nproof_;
+  const uint32_t nb = nbt();
+  const uint32_t n = nproof * n1;  // scalars walked: the whole chunk
   SortGeom G;
+  G.nproof = nproof;
+  G.n1 = n1;
+  G.nb1 = cfg.nb();
+  G.stride = stride;
   G.c = cfg.c;
   G.W = cfg.W;
   G.D = cfg.D;
@@ -624,8 +660,12 @@ void MsmSort::run(const void* scalars, uint32_t n, bool mont, hipStream_t s) {
   if (grid2 < 1) grid2 = 1;
   // level 1: per-block partition histograms -> scan (= every block's write positions) -> partition
   const uint32_t L1 = G.bins1 * grid1;
-  if (mont) G16_LAUNCH((k_part_count<true>), grid1, P1_THREADS, 0, s, scalars, n, G, blk_hist.p);
-  else G16_LAUNCH((k_part_count<false>), grid1, P1_THREADS, 0, s, scalars, n, G, blk_hist.p);
+  // (a chunk: the kernels that split the walk into proofs; one proof: the single-proof kernels)
+  const bool chunk = nproof > 1;
+  if (mont && chunk) G16_LAUNCH((k_part_count<true, true>), grid1, P1_THREADS, 0, s, scalars, n, G, blk_hist.p);
+  else if (mont) G16_LAUNCH((k_part_count<true, false>), grid1, P1_THREADS, 0, s, scalars, n, G, blk_hist.p);
+  else if (chunk) G16_LAUNCH((k_part_count<false, true>), grid1, P1_THREADS, 0, s, scalars, n, G, blk_hist.p);
+  else G16_LAUNCH((k_part_count<false, false>), grid1, P1_THREADS, 0, s, scalars, n, G, blk_hist.p);
   scan_exclusive(blk_hist.p, L1, 0, blk_off.p, nullptr, scan_tmp.p, s);
   G16_LAUNCH(k_part_offsets, ceil_div(G.bins1 + 1, 256), 256, 0, s, (const uint32_t*)blk_off.p, grid1,
              G.bins1, part_off.p);
@@ -633,11 +673,17 @@ void MsmSort::run(const void* scalars, uint32_t n, bool mont, hipStream_t s) {
   if (rng)
     G16_LAUNCH(k_pick_range, 1, 64, 0, s, (const uint32_t*)part_off.p, G.bins1, G.sh, nb, rank, world,
                range.p);
-  if (mont)
-    G16_LAUNCH((k_part_scatter<true>), grid1, P1_THREADS, 0, s, scalars, n, G, (const uint32_t*)blk_off.p,
+  if (mont && chunk)
+    G16_LAUNCH((k_part_scatter<true, true>), grid1, P1_THREADS, 0, s, scalars, n, G, (const uint32_t*)blk_off.p,
+               part.p, rng);
+  else if (mont)
+    G16_LAUNCH((k_part_scatter<true, false>), grid1, P1_THREADS, 0, s, scalars, n, G, (const uint32_t*)blk_off.p,
+               part.p, rng);
+  else if (chunk)
+    G16_LAUNCH((k_part_scatter<false, true>), grid1, P1_THREADS, 0, s, scalars, n, G, (const uint32_t*)blk_off.p,
                part.p, rng);
   else
-    G16_LAUNCH((k_part_scatter<false>), grid1, P1_THREADS, 0, s, scalars, n, G, (const uint32_t*)blk_off.p,
+    G16_LAUNCH((k_part_scatter<false, false>), grid1, P1_THREADS, 0, s, scalars, n, G, (const uint32_t*)blk_off.p,
                part.p, rng);
   // level 2: bucket sizes, offsets, final placement (over this rank's pairs only when sharded)
   const uint32_t* total = rng ? rng + 3 : part_off.p + G.bins1;
@@ -658,11 +704,13 @@ void MsmSort::run(const void* scalars, uint32_t n, bool mont, hipStream_t s) {
 // ---- a filtered view of another sort: level 2 again over `src`'s level-1 pairs, leaving out the
 // points whose bit in `keep` is clear.  Same bucket ids, same configuration, own offsets / entries /
 // hot-bucket lists: everything the accumulation and reduction kernels read from an MsmSort.
-void MsmSort::init_view(uint32_t capacity, const MsmConfig& c) {
+void MsmSort::init_view(uint32_t capacity, const MsmConfig& c, uint32_t nproof_cap_) {
   cfg = c;
   cap = capacity;
-  const uint32_t nb = cfg.nb();
-  const uint64_t M = (uint64_t)cap * cfg.W;
+  nproof_cap = nproof_cap_ ? nproof_cap_ : 1;
+  nproof = 1;
+  const uint32_t nb = nproof_cap * cfg.nb();
+  const uint64_t M = (uint64_t)nproof_cap * cap * cfg.W;
   count.alloc((size_t)nb + 1);
   offset.alloc((size_t)nb + 1);
   cursor.alloc((size_t)nb + 1);
@@ -676,8 +724,10 @@ void MsmSort::init_view(uint32_t capacity, const MsmConfig& c) {
 
 void MsmSort::run_view(const MsmSort& src, const uint32_t* keep_bits, hipStream_t s) {
   if (src.world > 1) throw std::runtime_error("MsmSort::run_view: the source sort is sharded");
+  if (src.nproof > nproof_cap) throw std::runtime_error("MsmSort::run_view: more proofs than the chunk capacity");
   len = src.len;
-  const uint32_t nb = cfg.nb(), n = src.len;
+  nproof = src.nproof;
+  const uint32_t nb = nbt(), n = nproof * src.len;
   const int sh = msm_part_shift(nb);
   const uint32_t bins1 = ((nb - 1) >> sh) + 1;
   const uint32_t idx_mask = (1u << cfg.idx_bits) - 1u;

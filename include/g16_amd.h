@@ -202,11 +202,12 @@ g16_status g16_prove_dev(g16_ctx* ctx, const uint64_t r[4], const uint64_t s[4],
  * r, s: count x 4 u64 (Montgomery).  w: count x n_vars x 4 u64.  proofs_out: count x 256 bytes.
  * count == 0: G16_OK, nothing written.  On an error, proofs_out is unspecified.  Argument rules are those
  * of g16_prove_dev (world == 1; not on a dist_wm ctx).
- * On a ctx with fixed-base tables (g16_ctx_info out[15] bit 0) a chunk of proofs goes through every kernel
- * in ONE pass; the chunk is the largest that fits a quarter of the device memory free at the call (at most
- * 256), larger counts loop over chunks, and the workspace stays with the ctx until g16_ctx_destroy.  On
- * bucket-path ctxs and g16_ctx_create_multi ctxs the call loops over the single-proof path: a correct
- * fallback, not a faster one.                                                                       */
+ * Where g16_ctx_info out[15] bit 2 is set -- ctxs with fixed-base tables, and single-device bucket-path
+ * ctxs up to a domain of 2^20 -- a chunk of proofs goes through every kernel in ONE pass (the bucket path:
+ * one sort, accumulation and reduction per MSM for the whole chunk); the chunk is the largest that fits a
+ * quarter of the device memory free at the call (at most 256; bucket path: also at most 2^24 buckets), larger
+ * counts loop over chunks, and the workspace stays with the ctx until g16_ctx_destroy.  Larger bucket-path
+ * keys and g16_ctx_create_multi ctxs loop over the single-proof path (same bytes).                  */
 g16_status g16_prove_batch(g16_ctx* ctx, size_t count, const uint64_t* r, const uint64_t* s,
                            const uint64_t* w, size_t n_vars, uint8_t* proofs_out);
 /* the same, with the witnesses resident in HBM: w_dev = count x n_vars x 32 bytes, contiguous       */
@@ -278,7 +279,8 @@ const char* g16_stage_name(int stage);
  * pair of its devices has direct peer access, 2 when some exchanges are staged by the runtime,
  * out[15] = bit 0: g16_prove goes through the fixed-base tables (g16_options.fixed_tables); bit 1: the
  * B2 (G2) MSM runs over a filtered view of the witness sort (>= 1/8 of b_g1_query / b_g2_query is the
- * point at infinity: wires that appear in no B row of a real circom circuit)                        */
+ * point at infinity: wires that appear in no B row of a real circom circuit); bit 2: a chunk of
+ * g16_prove_batch is enqueued once (table ctxs; single-device bucket ctxs up to a domain of 2^20)      */
 g16_status g16_ctx_info(const g16_ctx* ctx, uint32_t out[16]);
 /* Multi-device ctx (g16_ctx_create_multi with a distributed witness map): what every ordered (source,
  * destination) pair of its ranks delivered at create time, measured with the copies a proof makes --

@@ -2,7 +2,11 @@
 
 For each circuit -- the reference bench family at 1000 x 1000 and 1000 x 10^4 (bench.complex_shape_circuit),
 the reference bench's own circuit (bench.complex_circuit) and the squaring chain 2^14 -- with a trapdoor key
-minted on the GPU and the library's automatic table rule (tables=0), and for each batch size B, one JSON line:
+minted on the GPU and the library's automatic table rule (tables=0), and for each batch size B, one JSON line.
+Bucket-path circuits: bchain15 .. bchain20 = squaring chains of 2^15 .. 2^20 constraints with tables=-1 (no
+fixed-base tables: the sort / bucket MSMs); for them only the device-resident legs are timed unless --full.
+--force-chunks: batch the bucket path above its size threshold as well (G16_BATCH_BUCKET_MAX_N, measurement
+only) -- the data the threshold is read from.
   batch_dev / batch_host   ms per batch call and proofs/s, witnesses resident in HBM / from host memory
   loop                     prove_dev over the same resident inputs, one call per proof
   siblings                 two ctxs sharing the tables (g16_ctx_create_sibling), one host thread each
@@ -43,6 +47,8 @@ def circuit(name):
         return bench.complex_circuit(cc)
     if name == "chain14":
         return bench.chain_circuit(cc, 14)
+    if name.startswith("bchain"):
+        return bench.chain_circuit(cc, int(name[6:]))
     raise SystemExit(f"unknown circuit {name}")
 
 
@@ -53,7 +59,7 @@ def witnesses(name, n_vars, count, distinct=8):
         r1cs = cc.R1CS.from_file(os.path.join(ROOT, "tests", "golden", "complex-circuit-10000-10000.r1cs"))
         base = [cc.fr_from_ints(bench.solve_r1cs_forward(r1cs, {0: 1, 2: 3 + i})) for i in range(distinct)]
     else:
-        m = n_vars - 2 if name == "chain14" else 1000
+        m = n_vars - 2 if "chain" in name else 1000
         base = [cc.fr_from_ints(chain_witness(3 + i, m)) for i in range(distinct)]
     return np.ascontiguousarray(np.stack([base[i % distinct] for i in range(count)]))
 
@@ -74,6 +80,8 @@ def main():
     ap.add_argument("--sizes", default="1,8,64,256,1024")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--circuits", default="1000x1000,1000x10000,reference,chain14")
+    ap.add_argument("--full", action="store_true", help="bucket circuits: also the host-witness and sibling legs")
+    ap.add_argument("--force-chunks", action="store_true", help="bucket circuits: chunks above the size threshold too")
     args = ap.parse_args()
     sizes = [int(x) for x in args.sizes.split(",")]
     for name in args.circuits.split(","):
@@ -81,8 +89,11 @@ def main():
         mats, (A, B, Cm), _, n_vars = circuit(name)
         rng = random.Random(len(name))
         pk = cc.trapdoor_setup(A, B, Cm, n_vars, 1, [rng.randrange(1, R) for _ in range(5)])
-        pr = cc.Prover(pk, mats, tables=0)
-        sib = cc.Prover(pk, mats, tables=0, sibling_of=pr)
+        bucket = name.startswith("bchain")
+        tables = -1 if bucket else 0
+        lean = bucket and not args.full
+        pr = cc.Prover(pk, mats, tables=tables)
+        sib = cc.Prover(pk, mats, tables=tables, sibling_of=pr)
         info = pr.info()
         wall = witnesses(name, n_vars, max(sizes))
         w_dev = torch.from_numpy(wall.view(np.int64)).to("cuda:0")
@@ -90,11 +101,12 @@ def main():
         wb = n_vars * 32
         base = w_dev.data_ptr()
         line = dict(circuit=name, n_vars=n_vars, num_constraints=mats.num_constraints,
-                    fixed_tables=info["fixed_tables"], setup_s=round(time.perf_counter() - t0, 2), rows=[])
+                    fixed_tables=info["fixed_tables"], batched=info["batched"], c_w=info["c_w"], D_w=info["D_w"],
+                    setup_s=round(time.perf_counter() - t0, 2), rows=[])
         for count in sizes:
             rs = [tuple(v) for v in cc.fr_from_ints([rng.randrange(R) for _ in range(2 * count)]).reshape(count, 2, 4)]
             t_dev, got = timed(lambda: pr.prove_batch_dev(rs, base, count), args.reps)
-            t_host, got_h = timed(lambda: pr.prove_batch(rs, wall[:count]), args.reps)
+            t_host, got_h = (t_dev, got) if lean else timed(lambda: pr.prove_batch(rs, wall[:count]), args.reps)
             t_loop, loop = timed(lambda: [pr.prove_dev(r, s, base + i * wb) for i, (r, s) in enumerate(rs)], args.reps)
 
             def two():
@@ -109,7 +121,7 @@ def main():
                 run(pr, 0, half)
                 th.join()
                 return res
-            t_sib, sib_out = timed(two, args.reps)
+            t_sib, sib_out = (t_loop, loop) if lean else timed(two, args.reps)
             ok = ([p.raw for p in got] == [p.raw for p in loop] and [p.raw for p in got_h] == [p.raw for p in loop]
                   and [p.raw for p in sib_out] == [p.raw for p in loop])
             row = dict(B=count,
@@ -119,6 +131,10 @@ def main():
                        siblings_ms=round(t_sib * 1e3, 3), siblings_proofs_per_s=round(count / t_sib, 1),
                        batch_over_loop=round(t_loop / t_dev, 2), batch_over_siblings=round(t_sib / t_dev, 2),
                        bytes_equal=ok)
+            if lean:  # not timed
+                for k in ("batch_host_ms", "batch_host_proofs_per_s", "siblings_ms", "siblings_proofs_per_s",
+                          "batch_over_siblings"):
+                    row.pop(k)
             line["rows"].append(row)
             print(json.dumps(dict(circuit=name, **row)), file=sys.stderr, flush=True)
         print(json.dumps(line), flush=True)
@@ -128,4 +144,6 @@ def main():
 
 
 if __name__ == "__main__":
+    if "--force-chunks" in sys.argv:
+        os.environ["G16_BATCH_BUCKET_MAX_N"] = str(1 << 27)  # read once, when the first batch call is made
     main()
