@@ -36,7 +36,8 @@ from ._binding import G16Error, SerializationError, SynthesisError  # noqa: F401
 __all__ = ["read_zkey", "R1CSFile", "R1CS", "CircomCircuit", "CircomBuilder", "CircomReduction", "LibsnarkReduction", "Groth16",
            "Prover", "ProvingKey", "VerifyingKey", "ConstraintMatrices", "Proof", "G16Error",
            "SynthesisError", "SerializationError", "fr_from_ints", "fr_to_ints", "read_wtns",
-           "trapdoor_setup", "Csr", "write_zkey", "device_tensor", "verify_batch"]
+           "trapdoor_setup", "Csr", "write_zkey", "device_tensor", "verify_batch", "verify_aggregate",
+           "verify_batch_fast"]
 
 FR_MODULUS = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 
@@ -767,12 +768,8 @@ def trapdoor_setup(a: Csr, b: Csr, c: Csr, n_vars: int, n_public: int, toxic: Se
                       view(kd.h_query, kd.domain_size, 64), keepalive=handle)
 
 
-def verify_batch(vk: "VerifyingKey", proofs, public_inputs, device=0, lib: Optional[B.Library] = None):
-    """Groth16::process_vk + verify_with_processed_vk (reference src/zkey.rs:868-870,914-916) for a
-    batch under one key on the GPU (g16_verify_batch).  proofs: Proof objects or 256-byte strings;
-    public_inputs: one sequence of n_public values (ints or Montgomery rows) per proof.  Returns a
-    list of bools."""
-    lib = lib or B.load()
+def _verify_args(vk, proofs, public_inputs, lib):
+    """(vk descriptor, proof bytes, Montgomery public inputs, n, keepalive) as the verify entry points take them"""
     raw = b"".join(p.raw if isinstance(p, Proof) else bytes(p) for p in proofs)
     n = len(raw) // B.G16_PROOF_BYTES
     ic = np.ascontiguousarray(vk.gamma_abc_g1, dtype=np.uint8).reshape(-1, 64)
@@ -793,11 +790,72 @@ def verify_batch(vk: "VerifyingKey", proofs, public_inputs, device=0, lib: Optio
     C.memmove(d.delta_g2, bytes(vk.delta_g2), 128)
     d.ic, d.ic_count = ic.ctypes.data, ic.shape[0]
     buf = np.frombuffer(raw, dtype=np.uint8)
+    return d, buf, pubs, n, ic
+
+
+def verify_batch(vk: "VerifyingKey", proofs, public_inputs, device=0, lib: Optional[B.Library] = None):
+    """Groth16::process_vk + verify_with_processed_vk (reference src/zkey.rs:868-870,914-916) for a
+    batch under one key on the GPU (g16_verify_batch).  proofs: Proof objects or 256-byte strings;
+    public_inputs: one sequence of n_public values (ints or Montgomery rows) per proof.  Returns a
+    list of bools."""
+    lib = lib or B.load()
+    d, buf, pubs, n, _ic = _verify_args(vk, proofs, public_inputs, lib)
     ok = np.zeros(max(n, 1), dtype=np.uint8)
     st = lib.g16_verify_batch(device, C.byref(d), _np_ptr(buf), _np_ptr(pubs), n, _np_ptr(ok))
     if st != B.G16_OK:
         raise G16Error(st, "g16_verify_batch failed")
     return [bool(x) for x in ok[:n]]
+
+
+def verify_aggregate(vk: "VerifyingKey", proofs, public_inputs, rho=None, device=0,
+                     lib: Optional[B.Library] = None, return_structural=False):
+    """All proofs of a batch under one key in ONE combined pairing check (g16_verify_aggregate, the
+    small-exponent batch test): True iff every proof is well formed and
+      prod_i e(rho_i A_i, B_i) = e((sum rho_i) alpha, beta) e(sum rho_i X_i, gamma) e(sum rho_i C_i, delta).
+    Inputs as verify_batch takes them.  rho: None (the library draws 128-bit coefficients from the
+    operating system's CSPRNG) or one int in [1, 2^128) per proof -- which must be unpredictable to
+    whoever made the proofs: a batch with an invalid proof passes with probability <= 2^-127 only then.
+    return_structural=True returns (verdict, [proof i is well formed])."""
+    lib = lib or B.load()
+    d, buf, pubs, n, _ic = _verify_args(vk, proofs, public_inputs, lib)
+    rho_arr = None
+    if rho is not None:
+        rho = [int(x) for x in rho]
+        if len(rho) != n:
+            raise G16Error(B.G16_ERR_INVALID, "one coefficient per proof")
+        if any(not 0 <= x < 1 << 128 for x in rho):
+            raise G16Error(B.G16_ERR_INVALID, "coefficients are integers in [1, 2^128)")
+        rho_arr = np.array([[x & 0xFFFFFFFFFFFFFFFF, x >> 64] for x in rho], dtype=np.uint64).reshape(n, 2)
+    ok = np.zeros(1, dtype=np.uint8)
+    structural = np.zeros(max(n, 1), dtype=np.uint8)
+    st = lib.g16_verify_aggregate(device, C.byref(d), _np_ptr(buf), _np_ptr(pubs), n,
+                                  _np_ptr(rho_arr) if rho_arr is not None and n else None, _np_ptr(ok),
+                                  _np_ptr(structural))
+    if st != B.G16_OK:
+        raise G16Error(st, "g16_verify_aggregate failed")
+    if return_structural:
+        return bool(ok[0]), [bool(x) for x in structural[:n]]
+    return bool(ok[0])
+
+
+def verify_batch_fast(vk: "VerifyingKey", proofs, public_inputs, device=0, lib: Optional[B.Library] = None):
+    """verify_batch's list at the cost of one aggregate check when every proof is valid (the common
+    case): verify_aggregate with fresh coefficients first; if it rejects, the malformed proofs are
+    False and the well-formed remainder goes through verify_batch.  Equal to verify_batch's result up
+    to the 2^-127 soundness error of the aggregate check."""
+    lib = lib or B.load()
+    proofs = list(proofs)
+    public_inputs = list(public_inputs)
+    ok, structural = verify_aggregate(vk, proofs, public_inputs, device=device, lib=lib, return_structural=True)
+    if ok:
+        return [True] * len(structural)
+    rest = [i for i, s in enumerate(structural) if s]
+    out = [False] * len(structural)
+    if rest:
+        for i, v in zip(rest, verify_batch(vk, [proofs[i] for i in rest], [public_inputs[i] for i in rest],
+                                           device=device, lib=lib)):
+            out[i] = v
+    return out
 
 
 class _Reduction:

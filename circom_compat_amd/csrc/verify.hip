@@ -19,7 +19,9 @@
 // not a latency win over one CPU core for a single proof.
 #include "../../include/g16_amd.h"
 
+#include <errno.h>
 #include <string.h>
+#include <sys/random.h>
 
 #include <memory>
 #include <mutex>
@@ -317,6 +319,220 @@ __global__ void __launch_bounds__(64) k_verify_batch(const VkDev* vk, const G1Af
   ok[i] = final_exp_is_one(&f, vk) ? 1 : 0;
 }
 
+// ---- aggregate verification: n proofs under one key in ONE combined pairing check ---------------
+// With coefficients rho_i (128-bit, unknown to whoever made the proofs) the n per-proof equations
+// fold into
+//   prod_i ML(B_i, rho_i A_i) * ML(beta, -(sum rho_i) alpha) * ML(gamma, -sum rho_i X_i)
+//       * ML(delta, -sum rho_i C_i)   --final exponentiation-->   1,
+//   sum_i rho_i X_i = (sum_i rho_i) IC_0 + sum_j (sum_i rho_i pub_ij) IC_{j+1}
+// (the small-exponent batch test).  Per proof that is one Miller loop, two 128-bit G1
+// multiplications and the structural checks; the key-side Miller loops and the final
+// exponentiation are paid once per batch.  The long serial pieces sit in separate lanes:
+//   k_agg_front   blockIdx.y = 0: structural checks (incl. the 254-bit subgroup multiplication)
+//                 blockIdx.y = 1: P_i = rho_i A_i (affine)
+//                 blockIdx.y = 2: rho_i C_i and rho_i pub_ij, summed per block through LDS
+//   k_agg_sums    one block per sum over the per-block partials: -sum rho_i C_i, the columns
+//                 s_j = sum_i rho_i pub_ij, and one lane for -(sum rho) alpha
+//   k_agg_x       -((sum rho) IC_0 + sum_j s_j IC_{j+1}), one lane per term, LDS sum
+//   k_agg_miller  n + 3 lanes, one Miller loop each; per-block product through LDS
+//   k_agg_tail    product of the per-block products, AND of the structural flags, final
+//                 exponentiation in one lane
+// No atomics: every reduction is a fixed tree, so the result does not depend on scheduling.
+constexpr uint32_t AGG_BLOCK = 64;
+
+struct AggKey {
+  G1Affine p[3];  // G1 sides paired with beta, gamma, delta
+};
+
+G16_HD U256 rho_u256(const uint64_t* rho, uint32_t i) {
+  U256 k;
+  k.v[0] = (uint32_t)rho[2 * (size_t)i];
+  k.v[1] = (uint32_t)(rho[2 * (size_t)i] >> 32);
+  k.v[2] = (uint32_t)rho[2 * (size_t)i + 1];
+  k.v[3] = (uint32_t)(rho[2 * (size_t)i + 1] >> 32);
+  k.v[4] = k.v[5] = k.v[6] = k.v[7] = 0;
+  return k;
+}
+G16_HD bool g1_well_formed(const G1Affine& p) {
+  return fq_words_canonical(p.x) && fq_words_canonical(p.y) && on_curve_g1(p);
+}
+// sh[0] <- sum of sh[0 .. AGG_BLOCK): every lane of the block calls it, v = the lane's own term
+__device__ __forceinline__ void block_sum_g1(G1XYZZ* sh, G1XYZZ v) {
+  const uint32_t t = threadIdx.x;
+  sh[t] = v;
+#pragma unroll 1
+  for (uint32_t s = AGG_BLOCK / 2; s > 0; s >>= 1) {
+    __syncthreads();  // lanes < s read the upper half [s, 2s) and write the lower: one barrier per round
+    if (t < s) {
+      v.add(sh[t + s]);
+      sh[t] = v;
+    }
+  }
+  __syncthreads();
+}
+
+__global__ void __launch_bounds__(AGG_BLOCK) k_agg_front(const VkDev* vk, uint32_t n_pub, const uint8_t* proofs,
+                                                         const Fr* pubs, const uint64_t* rho, uint32_t n,
+                                                         uint8_t* structural, G1Affine* P, G1XYZZ* c_part,
+                                                         Fr* s_part) {
+  __shared__ G1XYZZ sh_c[AGG_BLOCK];
+  __shared__ Fr sh_s[AGG_BLOCK];
+  const uint32_t t = threadIdx.x, i = blockIdx.x * AGG_BLOCK + t;
+  const bool live = i < n;
+  const uint8_t* proof = proofs + (size_t)(live ? i : 0) * G16_PROOF_BYTES;
+  if (blockIdx.y == 0) {  // what g16_verify_batch checks before it pairs
+    if (!live) return;
+    G1Affine A, C;
+    G2Affine B;
+    memcpy(&A, proof, 64);
+    memcpy(&B, proof + 64, 128);
+    memcpy(&C, proof + 192, 64);
+    const bool canonical = fq_words_canonical(B.x.c0) && fq_words_canonical(B.x.c1) &&
+                           fq_words_canonical(B.y.c0) && fq_words_canonical(B.y.c1);
+    structural[i] = (canonical && g1_well_formed(A) && g1_well_formed(C) && on_curve_g2(B, vk) && g2_in_subgroup(B)) ? 1 : 0;
+    return;
+  }
+  if (blockIdx.y == 1) {  // a malformed A is never paired (k_agg_miller skips the proof): any value will do
+    if (!live) return;
+    G1Affine A;
+    memcpy(&A, proof, 64);
+    P[i] = g1_well_formed(A) ? G1XYZZ::from_affine(A).mul(rho_u256(rho, i)).to_affine() : G1Affine::infinity();
+    return;
+  }
+  // a malformed proof makes the verdict 0 whatever the sums are: a malformed C is left out of them
+  G1XYZZ acc = G1XYZZ::infinity();
+  Fr rf = Fr::zero();
+  if (live) {
+    G1Affine C;
+    memcpy(&C, proof + 192, 64);
+    const U256 k = rho_u256(rho, i);
+    if (g1_well_formed(C)) acc = G1XYZZ::from_affine(C).mul(k);
+    rf = Fr::from_canonical(k);
+  }
+  block_sum_g1(sh_c, acc);
+  if (t == 0) c_part[blockIdx.x] = sh_c[0];
+#pragma unroll 1
+  for (uint32_t j = 0; j < n_pub; ++j) {
+    Fr v = live ? rf * pubs[(size_t)i * n_pub + j] : Fr::zero();
+    sh_s[t] = v;
+#pragma unroll 1
+    for (uint32_t s = AGG_BLOCK / 2; s > 0; s >>= 1) {
+      __syncthreads();
+      if (t < s) {
+        v = v + sh_s[t + s];
+        sh_s[t] = v;
+      }
+    }
+    if (t == 0) s_part[(size_t)j * gridDim.x + blockIdx.x] = v;
+    __syncthreads();
+  }
+}
+
+// block 0: -sum rho_i C_i; block 1 + j: s_j (canonical, the scalar of IC_{j+1}); block n_pub + 1: -(sum rho) alpha
+__global__ void __launch_bounds__(AGG_BLOCK) k_agg_sums(const VkDev* vk, uint32_t n_pub, uint32_t nb,
+                                                        const G1XYZZ* c_part, const Fr* s_part, U256 rho_sum,
+                                                        AggKey* key, U256* scal) {
+  __shared__ G1XYZZ sh_c[AGG_BLOCK];
+  __shared__ Fr sh_s[AGG_BLOCK];
+  const uint32_t t = threadIdx.x, b = blockIdx.x;
+  if (b == 0) {
+    G1XYZZ acc = G1XYZZ::infinity();
+#pragma unroll 1
+    for (uint32_t k = t; k < nb; k += AGG_BLOCK) acc.add(c_part[k]);
+    block_sum_g1(sh_c, acc);
+    if (t == 0) key->p[2] = sh_c[0].to_affine().neg();
+  } else if (b <= n_pub) {
+    Fr v = Fr::zero();
+#pragma unroll 1
+    for (uint32_t k = t; k < nb; k += AGG_BLOCK) v = v + s_part[(size_t)(b - 1) * nb + k];
+    sh_s[t] = v;
+#pragma unroll 1
+    for (uint32_t s = AGG_BLOCK / 2; s > 0; s >>= 1) {
+      __syncthreads();
+      if (t < s) {
+        v = v + sh_s[t + s];
+        sh_s[t] = v;
+      }
+    }
+    if (t == 0) scal[b] = v.to_canonical();
+  } else if (t == 0) {
+    key->p[0] = G1XYZZ::from_affine(vk->alpha_neg).mul(rho_sum).to_affine();
+    scal[0] = rho_sum;  // the scalar of IC_0
+  }
+}
+
+// -(sum_j scal_j IC_j), j = 0 .. n_pub
+__global__ void __launch_bounds__(AGG_BLOCK) k_agg_x(const G1Affine* ic, uint32_t n_pub, const U256* scal,
+                                                     AggKey* key) {
+  __shared__ G1XYZZ sh_c[AGG_BLOCK];
+  const uint32_t t = threadIdx.x;
+  G1XYZZ acc = G1XYZZ::infinity();
+#pragma unroll 1
+  for (uint32_t j = t; j <= n_pub; j += AGG_BLOCK) acc.add(G1XYZZ::from_affine(ic[j]).mul(scal[j]));
+  block_sum_g1(sh_c, acc);
+  if (t == 0) key->p[1] = sh_c[0].to_affine().neg();
+}
+
+// lane i < n: ML(B_i, P_i), or 1 for a malformed proof; lanes n, n + 1, n + 2: the key side.
+// f_part[block] = product of the block's lanes
+__global__ void __launch_bounds__(AGG_BLOCK) k_agg_miller(const VkDev* vk, const uint8_t* proofs, const G1Affine* P,
+                                                          const uint8_t* structural, const AggKey* key, uint32_t n,
+                                                          F12* f_part) {
+  __shared__ F12 sh[AGG_BLOCK];
+  const uint32_t t = threadIdx.x;
+  const uint64_t i = (uint64_t)blockIdx.x * AGG_BLOCK + t;
+  G2Affine Q = G2Affine::infinity();
+  G1Affine p = G1Affine::infinity();
+  if (i < n) {
+    if (structural[i]) {
+      memcpy(&Q, proofs + (size_t)i * G16_PROOF_BYTES + 64, 128);
+      p = P[i];
+    }
+  } else if (i < (uint64_t)n + 3) {
+    const uint32_t k = (uint32_t)(i - n);
+    Q = k == 0 ? vk->beta : k == 1 ? vk->gamma : vk->delta;
+    p = key->p[k];
+  }
+  F12 f = f12_one();
+  miller_mul(&f, &Q, &p, vk);  // one call site for proof and key lanes: no divergent copies of the loop
+  sh[t] = f;
+#pragma unroll 1
+  for (uint32_t s = AGG_BLOCK / 2; s > 0; s >>= 1) {
+    __syncthreads();
+    if (t < s) {
+      f12_mul(&f, &f, &sh[t + s]);
+      sh[t] = f;
+    }
+  }
+  if (t == 0) f_part[blockIdx.x] = f;
+}
+
+__global__ void __launch_bounds__(AGG_BLOCK) k_agg_tail(const VkDev* vk, const F12* f_part, uint32_t nb,
+                                                        const uint8_t* structural, uint32_t n, uint8_t* ok) {
+  __shared__ F12 sh[AGG_BLOCK];
+  __shared__ uint32_t sh_ok[AGG_BLOCK];
+  const uint32_t t = threadIdx.x;
+  F12 f = f12_one();
+#pragma unroll 1
+  for (uint32_t k = t; k < nb; k += AGG_BLOCK) f12_mul(&f, &f, &f_part[k]);
+  uint32_t sound = 1;
+#pragma unroll 1
+  for (uint32_t k = t; k < n; k += AGG_BLOCK) sound &= structural[k];
+  sh[t] = f;
+  sh_ok[t] = sound;
+#pragma unroll 1
+  for (uint32_t s = AGG_BLOCK / 2; s > 0; s >>= 1) {
+    __syncthreads();
+    if (t < s) {
+      f12_mul(&f, &f, &sh[t + s]);
+      sh[t] = f;
+      sound &= sh_ok[t + s];
+      sh_ok[t] = sound;
+    }
+  }
+  if (t == 0) *ok = (sound && final_exp_is_one(&f, vk)) ? 1 : 0;
+}
+
 // ---- host-side constants (the same field classes compile for the host) ------------------------
 void words_of_modulus(uint32_t (&w)[8]) {
   for (int i = 0; i < 8; ++i) w[i] = FqParams::MOD[i];
@@ -436,6 +652,139 @@ extern "C" g16_status g16_verify_batch(int device, const g16_vk_desc* vk, const 
                dok.p);
     G16_HIP(hipDeviceSynchronize());
     G16_HIP(hipMemcpy(ok_out, dok.p, n_proofs, hipMemcpyDeviceToHost));
+    return G16_OK;
+  } catch (const HipError&) {
+    return G16_ERR_HIP;
+  } catch (const std::exception&) {
+    return G16_ERR_INTERNAL;
+  }
+}
+
+namespace {
+// operating-system CSPRNG; false when neither source delivers (never a fixed fallback)
+bool os_random(void* buf, size_t len) {
+  uint8_t* p = (uint8_t*)buf;
+  while (len) {
+    const ssize_t r = getrandom(p, len, 0);
+    if (r < 0) {
+      if (errno == EINTR) continue;
+      break;
+    }
+    p += r;
+    len -= (size_t)r;
+  }
+  if (!len) return true;
+  FILE* f = fopen("/dev/urandom", "rb");
+  if (!f) return false;
+  const size_t got = fread(p, 1, len, f);
+  fclose(f);
+  return got == len;
+}
+}  // namespace
+
+extern "C" g16_status g16_verify_aggregate(int device, const g16_vk_desc* vk, const uint8_t* proofs,
+                                           const uint64_t* public_inputs, uint32_t n_proofs,
+                                           const uint64_t* rho, uint8_t* ok_out, uint8_t* structural_out) {
+  if (!vk || !vk->ic || vk->ic_count < 1 || !ok_out || (n_proofs && !proofs)) return G16_ERR_INVALID;
+  const uint32_t n_pub = vk->ic_count - 1;
+  if (n_proofs && n_pub && !public_inputs) return G16_ERR_INVALID;
+  if (rho)
+    for (uint32_t i = 0; i < n_proofs; ++i)
+      if (!(rho[2 * (size_t)i] | rho[2 * (size_t)i + 1])) return G16_ERR_INVALID;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return G16_ERR_NO_DEVICE;
+  if (device < 0 || device >= ndev) return G16_ERR_INVALID;
+  if (!n_proofs) {
+    *ok_out = 1;
+    return G16_OK;
+  }
+  try {
+    std::vector<uint64_t> drawn;
+    if (!rho) {
+      drawn.resize(2 * (size_t)n_proofs);
+      if (!os_random(drawn.data(), drawn.size() * 8)) return G16_ERR_INTERNAL;
+      for (uint32_t i = 0; i < n_proofs; ++i)
+        while (!(drawn[2 * (size_t)i] | drawn[2 * (size_t)i + 1]))  // probability 2^-128 per entry
+          if (!os_random(&drawn[2 * (size_t)i], 16)) return G16_ERR_INTERNAL;
+      rho = drawn.data();
+    }
+    // sum of the coefficients as an integer: < 2^160, far below r, so it is its own residue
+    U256 rho_sum;
+    {
+      unsigned __int128 lo = 0;
+      uint64_t hi = 0;
+      uint64_t w0 = 0, w1 = 0;
+      for (uint32_t i = 0; i < n_proofs; ++i) {
+        lo = (unsigned __int128)w0 + rho[2 * (size_t)i];
+        w0 = (uint64_t)lo;
+        lo = (lo >> 64) + w1 + rho[2 * (size_t)i + 1];
+        w1 = (uint64_t)lo;
+        hi += (uint64_t)(lo >> 64);
+      }
+      const uint64_t w[4] = {w0, w1, hi, 0};
+      for (int k = 0; k < 4; ++k) {
+        rho_sum.v[2 * k] = (uint32_t)w[k];
+        rho_sum.v[2 * k + 1] = (uint32_t)(w[k] >> 32);
+      }
+    }
+    G16_HIP(hipSetDevice(device));
+    const HostConsts& H = host_consts();
+    std::unique_ptr<VkDev> hv(new VkDev());
+    G1Affine alpha;
+    memcpy(&alpha, vk->alpha_g1, 64);
+    hv->alpha_neg = alpha.neg();
+    memcpy(&hv->beta, vk->beta_g2, 128);
+    memcpy(&hv->gamma, vk->gamma_g2, 128);
+    memcpy(&hv->delta, vk->delta_g2, 128);
+    hv->frob_x = H.frob_x;
+    hv->frob_y = H.frob_y;
+    hv->b_twist = H.b_twist;
+    memcpy(hv->frob, H.frob, sizeof H.frob);
+    hv->ml_alpha_beta = f12_one();  // not used on this path (alpha is scaled by the sum of the coefficients)
+    const uint32_t nb = ceil_div(n_proofs, AGG_BLOCK);                 // blocks of the per-proof front
+    const uint32_t nbm = ceil_div((uint64_t)n_proofs + 3, AGG_BLOCK);  // blocks of the n + 3 Miller lanes
+    DevBuf<VkDev> dvk;
+    DevBuf<G1Affine> dic, dP;
+    DevBuf<uint8_t> dproofs, dstruct, dok;
+    DevBuf<Fr> dpub, dspart;
+    DevBuf<uint64_t> drho;
+    DevBuf<G1XYZZ> dcpart;
+    DevBuf<U256> dscal;
+    DevBuf<AggKey> dkey;
+    DevBuf<F12> dfpart;
+    dvk.alloc(1);
+    dic.alloc(vk->ic_count);
+    dP.alloc(n_proofs);
+    dproofs.alloc((size_t)n_proofs * G16_PROOF_BYTES);
+    dstruct.alloc(n_proofs);
+    dok.alloc(1);
+    dpub.alloc((size_t)n_proofs * (n_pub ? n_pub : 1));
+    dspart.alloc((size_t)nb * (n_pub ? n_pub : 1));
+    drho.alloc(2 * (size_t)n_proofs);
+    dcpart.alloc(nb);
+    dscal.alloc((size_t)n_pub + 1);
+    dkey.alloc(1);
+    dfpart.alloc(nbm);
+    G16_HIP(hipMemcpy(dvk.p, hv.get(), sizeof(VkDev), hipMemcpyHostToDevice));
+    G16_HIP(hipMemcpy(dic.p, vk->ic, (size_t)vk->ic_count * 64, hipMemcpyHostToDevice));
+    G16_HIP(hipMemcpy(dproofs.p, proofs, (size_t)n_proofs * G16_PROOF_BYTES, hipMemcpyHostToDevice));
+    G16_HIP(hipMemcpy(drho.p, rho, (size_t)n_proofs * 16, hipMemcpyHostToDevice));
+    if (n_pub)
+      G16_HIP(hipMemcpy(dpub.p, public_inputs, (size_t)n_proofs * n_pub * 32, hipMemcpyHostToDevice));
+    G16_LAUNCH(k_agg_front, dim3(nb, 3), AGG_BLOCK, 0, nullptr, (const VkDev*)dvk.p, n_pub,
+               (const uint8_t*)dproofs.p, (const Fr*)dpub.p, (const uint64_t*)drho.p, n_proofs, dstruct.p, dP.p,
+               dcpart.p, dspart.p);
+    G16_LAUNCH(k_agg_sums, n_pub + 2, AGG_BLOCK, 0, nullptr, (const VkDev*)dvk.p, n_pub, nb,
+               (const G1XYZZ*)dcpart.p, (const Fr*)dspart.p, rho_sum, dkey.p, dscal.p);
+    G16_LAUNCH(k_agg_x, 1, AGG_BLOCK, 0, nullptr, (const G1Affine*)dic.p, n_pub, (const U256*)dscal.p, dkey.p);
+    G16_LAUNCH(k_agg_miller, nbm, AGG_BLOCK, 0, nullptr, (const VkDev*)dvk.p, (const uint8_t*)dproofs.p,
+               (const G1Affine*)dP.p, (const uint8_t*)dstruct.p, (const AggKey*)dkey.p, n_proofs, dfpart.p);
+    G16_LAUNCH(k_agg_tail, 1, AGG_BLOCK, 0, nullptr, (const VkDev*)dvk.p, (const F12*)dfpart.p, nbm,
+               (const uint8_t*)dstruct.p, n_proofs, dok.p);
+    G16_HIP(hipGetLastError());
+    G16_HIP(hipDeviceSynchronize());
+    G16_HIP(hipMemcpy(ok_out, dok.p, 1, hipMemcpyDeviceToHost));
+    if (structural_out) G16_HIP(hipMemcpy(structural_out, dstruct.p, n_proofs, hipMemcpyDeviceToHost));
     return G16_OK;
   } catch (const HipError&) {
     return G16_ERR_HIP;

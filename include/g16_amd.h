@@ -330,6 +330,32 @@ typedef struct {
 g16_status g16_verify_batch(int device, const g16_vk_desc* vk, const uint8_t* proofs,
                             const uint64_t* public_inputs, uint32_t n_proofs, uint8_t* ok_out);
 
+/* All n_proofs proofs under one key in ONE combined pairing check (the small-exponent batch test):
+ *   prod_i ML(B_i, rho_i A_i) * ML(beta, -(sum_i rho_i) alpha) * ML(gamma, -sum_i rho_i X_i)
+ *       * ML(delta, -sum_i rho_i C_i)   --final exponentiation-->   1,
+ *   X_i = IC_0 + sum_j pub_ij IC_{j+1},  sum_i rho_i X_i = (sum_i rho_i) IC_0 + sum_j (sum_i rho_i pub_ij) IC_{j+1}
+ * i.e. per proof one Miller loop and two 128-bit G1 multiplications; the three key-side Miller
+ * loops and the final exponentiation are paid once per batch.
+ * *ok_out = 1 iff every proof passes the structural checks g16_verify_batch applies (canonical
+ * coordinates, A and C on the curve, B on the twist and in the prime-order subgroup) AND the
+ * combined equation holds.  A batch that contains an invalid proof passes with probability at most
+ * 2^-127 PROVIDED the rho_i are unpredictable to whoever made the proofs.  They must be: a prover
+ * who knows rho forges a pair of individually invalid proofs that cancel in the sum
+ * (C_0' = C_0 + rho_1 D, C_1' = C_1 - rho_0 D for any D in G1), and the batch passes.
+ * rho: n_proofs x 2 u64 (little-endian 128-bit integers, NOT Montgomery), every one non-zero, or
+ *      NULL: the library then draws them from the operating system's CSPRNG (getrandom, else
+ *      /dev/urandom; a failure to get randomness is G16_ERR_INTERNAL, never a fixed fallback).  A
+ *      caller passes rho to derive it from its own transcript hash (one that covers the proofs), or
+ *      to be reproducible in a test.
+ * structural_out: NULL, or n_proofs bytes: 1 where proof i passed the structural checks (a caller
+ *      learns which proofs were malformed without a second call).
+ * proofs, public_inputs, vk and the treatment of infinity (a pair with an infinite side contributes
+ * 1) are those of g16_verify_batch, so the verdict on a batch of one proof is g16_verify_batch's.
+ * n_proofs == 0: G16_OK, *ok_out = 1.  A zero rho entry: G16_ERR_INVALID.                          */
+g16_status g16_verify_aggregate(int device, const g16_vk_desc* vk, const uint8_t* proofs,
+                                const uint64_t* public_inputs, uint32_t n_proofs,
+                                const uint64_t* rho, uint8_t* ok_out, uint8_t* structural_out);
+
 /* ---- RCCL inside the library (north_star: "a final RCCL all-reduce of partial bucket sums over xGMI") ---- */
 /* A host that is not PyTorch (the Rust shim) creates one per-rank ctx per process (g16_options.rank / world,
  * dist_wm = 1) and ONE ncclComm_t over the same ranks with its own RCCL (ncclGetUniqueId / ncclCommInitRank),

@@ -192,6 +192,7 @@ extern "C" {
     pub fn g16_witness_host_buffer(ctx: *mut g16_ctx) -> *mut c_void;
     pub fn g16_check_satisfied(device: c_int, a: *const g16_csr, b: *const g16_csr, c: *const g16_csr, num_constraints: u32, w: *const u64, n_vars: usize, first_unsatisfied: *mut i64) -> g16_status;
     pub fn g16_verify_batch(device: c_int, vk: *const g16_vk_desc, proofs: *const u8, public_inputs: *const u64, n_proofs: u32, ok_out: *mut u8) -> g16_status;
+    pub fn g16_verify_aggregate(device: c_int, vk: *const g16_vk_desc, proofs: *const u8, public_inputs: *const u64, n_proofs: u32, rho: *const u64, ok_out: *mut u8, structural_out: *mut u8) -> g16_status;
     pub fn g16_dist_attach_rccl(ctx: *mut g16_ctx, nccl_comm: *mut c_void) -> g16_status;
     pub fn g16_dist_rccl_ranks(ctx: *const g16_ctx) -> c_int;
     pub fn g16_prove_dist(ctx: *mut g16_ctx, r: *const u64, s: *const u64, w_dev: *const c_void, n_vars: usize, proof_out: *mut u8) -> g16_status;

@@ -26,7 +26,7 @@ mod verify;
 pub use ark_circom::{circom, read_zkey, CircomBuilder, CircomCircuit, CircomConfig, CircomReduction, Wasm, WitnessCalculator};
 pub use prover::{GpuError, GpuProver, Reduction, Shard};
 pub use reduction::GpuCircomReduction;
-pub use verify::verify_batch;
+pub use verify::{verify_aggregate, verify_batch};
 
 use ark_bn254::{Bn254, Fr};
 use ark_groth16::Proof;

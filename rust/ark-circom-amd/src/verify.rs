@@ -1,7 +1,8 @@
 //! Batch verification on the GPU: `Groth16::<Bn254>::process_vk` + `verify_with_processed_vk`
-//! (reference call sites src/zkey.rs:868-870,914-916) for many proofs under one key
-//! (`g16_verify_batch`, one GPU lane per proof).  The CPU call keeps working unchanged; this is for
-//! batches.
+//! (reference call sites src/zkey.rs:868-870,914-916) for many proofs under one key:
+//! `verify_batch` (`g16_verify_batch`, one GPU lane and one full pairing check per proof) and
+//! `verify_aggregate` (`g16_verify_aggregate`, ONE combined check for the whole batch).  The CPU
+//! call keeps working unchanged; these are for batches.
 use ark_bn254::{Bn254, Fr};
 use ark_groth16::{Proof, VerifyingKey};
 
@@ -9,13 +10,15 @@ use crate::ffi;
 use crate::pack;
 use crate::prover::GpuError;
 
-/// `out[i]` = `verify_with_processed_vk(&process_vk(vk), &public_inputs[i], &proofs[i])`
-pub fn verify_batch(
-    vk: &VerifyingKey<Bn254>,
-    public_inputs: &[Vec<Fr>],
-    proofs: &[Proof<Bn254>],
-    device: i32,
-) -> Result<Vec<bool>, GpuError> {
+/// The packed forms the C ABI takes; `ic` backs the pointer inside `desc`.
+struct Packed {
+    desc: ffi::g16_vk_desc,
+    _ic: Vec<u8>,
+    raw: Vec<u8>,
+    pubs: Vec<u64>,
+}
+
+fn pack_batch(vk: &VerifyingKey<Bn254>, public_inputs: &[Vec<Fr>], proofs: &[Proof<Bn254>]) -> Result<Packed, GpuError> {
     let n = proofs.len();
     let n_pub = vk.gamma_abc_g1.len() - 1;
     if public_inputs.len() != n || public_inputs.iter().any(|p| p.len() != n_pub) {
@@ -45,10 +48,53 @@ pub fn verify_batch(
     for v in public_inputs {
         pubs.extend_from_slice(&pack::fr_vec_words(v));
     }
+    Ok(Packed { desc, _ic: ic, raw, pubs })
+}
+
+/// `out[i]` = `verify_with_processed_vk(&process_vk(vk), &public_inputs[i], &proofs[i])`
+pub fn verify_batch(
+    vk: &VerifyingKey<Bn254>,
+    public_inputs: &[Vec<Fr>],
+    proofs: &[Proof<Bn254>],
+    device: i32,
+) -> Result<Vec<bool>, GpuError> {
+    let n = proofs.len();
+    let p = pack_batch(vk, public_inputs, proofs)?;
     let mut ok = vec![0u8; n];
-    let st = unsafe { ffi::g16_verify_batch(device, &desc, raw.as_ptr(), pubs.as_ptr(), n as u32, ok.as_mut_ptr()) };
+    let st = unsafe { ffi::g16_verify_batch(device, &p.desc, p.raw.as_ptr(), p.pubs.as_ptr(), n as u32, ok.as_mut_ptr()) };
     if st != ffi::G16_OK {
         return Err(GpuError::Library(st, "g16_verify_batch failed".into()));
     }
     Ok(ok.into_iter().map(|b| b != 0).collect())
+}
+
+/// All proofs in ONE combined pairing check (the small-exponent batch test): `true` iff every
+/// `verify_with_processed_vk(.., &public_inputs[i], &proofs[i])` is, up to a soundness error of
+/// 2^-127.  `rho`: `None` (the library draws 128-bit coefficients from the operating system's
+/// CSPRNG) or one non-zero coefficient per proof -- derived from a transcript hash that covers the
+/// proofs, never known to whoever made them: a prover who knows `rho` can forge a passing batch of
+/// invalid proofs.
+pub fn verify_aggregate(
+    vk: &VerifyingKey<Bn254>,
+    public_inputs: &[Vec<Fr>],
+    proofs: &[Proof<Bn254>],
+    rho: Option<&[u128]>,
+    device: i32,
+) -> Result<bool, GpuError> {
+    let n = proofs.len();
+    let p = pack_batch(vk, public_inputs, proofs)?;
+    let words: Option<Vec<u64>> = match rho {
+        Some(r) if r.len() != n => return Err(GpuError::Library(ffi::G16_ERR_INVALID, "one coefficient per proof".into())),
+        Some(r) => Some(r.iter().flat_map(|x| [*x as u64, (*x >> 64) as u64]).collect()),
+        None => None,
+    };
+    let rho_ptr = words.as_ref().map_or(std::ptr::null(), |w| w.as_ptr());
+    let mut ok = 0u8;
+    let st = unsafe {
+        ffi::g16_verify_aggregate(device, &p.desc, p.raw.as_ptr(), p.pubs.as_ptr(), n as u32, rho_ptr, &mut ok, std::ptr::null_mut())
+    };
+    if st != ffi::G16_OK {
+        return Err(GpuError::Library(st, "g16_verify_aggregate failed".into()));
+    }
+    Ok(ok != 0)
 }
