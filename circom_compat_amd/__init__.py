@@ -37,7 +37,7 @@ __all__ = ["read_zkey", "R1CSFile", "R1CS", "CircomCircuit", "CircomBuilder", "C
            "Prover", "ProvingKey", "VerifyingKey", "ConstraintMatrices", "Proof", "G16Error",
            "SynthesisError", "SerializationError", "fr_from_ints", "fr_to_ints", "read_wtns",
            "trapdoor_setup", "Csr", "write_zkey", "device_tensor", "verify_batch", "verify_aggregate",
-           "verify_batch_fast"]
+           "verify_batch_fast", "check_key", "KeyReport"]
 
 FR_MODULUS = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 
@@ -187,8 +187,10 @@ class _Handle:
         self.ptr = None
 
 
-def read_zkey(src, lib: Optional[B.Library] = None) -> Tuple[ProvingKey, ConstraintMatrices]:
-    """read_zkey (reference src/zkey.rs:53-60): snarkjs .zkey -> (ProvingKey, ConstraintMatrices)."""
+def read_zkey(src, lib: Optional[B.Library] = None, validate=False) -> Tuple[ProvingKey, ConstraintMatrices]:
+    """read_zkey (reference src/zkey.rs:53-60): snarkjs .zkey -> (ProvingKey, ConstraintMatrices).
+    validate=True runs check_key on the loaded key (on the GPU) and raises G16Error naming the first bad
+    (query, index, reason) or the failed relation; the default, like the reference, looks at no point."""
     lib = lib or B.load()
     h = C.c_void_p()
     if isinstance(src, (bytes, bytearray, memoryview)):
@@ -221,6 +223,10 @@ def read_zkey(src, lib: Optional[B.Library] = None) -> Tuple[ProvingKey, Constra
     lib.check(lib.g16_zkey_matrices(h, C.byref(m)), loader=True)
     mats = ConstraintMatrices(m.num_instance_variables, m.num_witness_variables, m.num_constraints,
                               Csr.from_c(m.a, m.num_constraints), Csr.from_c(m.b, m.num_constraints))
+    if validate:
+        rep = check_key(pk, lib=lib)
+        if not rep.ok:
+            raise G16Error(B.G16_ERR_INVALID, "zkey failed validation: " + rep.describe())
     return pk, mats
 
 
@@ -791,6 +797,87 @@ def _verify_args(vk, proofs, public_inputs, lib):
     d.ic, d.ic_count = ic.ctypes.data, ic.shape[0]
     buf = np.frombuffer(raw, dtype=np.uint8)
     return d, buf, pubs, n, ic
+
+
+class KeyReport:
+    """g16_key_report + the bad-point list of g16_key_check.  ok: no bad point and no failed relation;
+    relations_checked: False when a structural failure made the pairing relations meaningless;
+    relations_failed: KEY_PAIR_BETA | KEY_PAIR_DELTA | KEY_PAIR_B | KEY_VK_MISMATCH bits (_binding);
+    n_points / n_bad / n_infinity: dicts by query name (_binding.KEY_QUERIES);
+    bad: [(query_name, index, reason_bits)] in ascending (query, index) order, at most max_listed."""
+    RELATIONS = ((B.KEY_PAIR_BETA, "e(beta_g1, g2) != e(g1, beta_g2)"),
+                 (B.KEY_PAIR_DELTA, "e(delta_g1, g2) != e(g1, delta_g2)"),
+                 (B.KEY_PAIR_B, "b_g1_query and b_g2_query do not hold the same scalars"),
+                 (B.KEY_VK_MISMATCH, "the verifying key differs from the proving key"))
+    REASONS = ((B.KEY_BAD_NONCANONICAL, "non-canonical coordinate"), (B.KEY_BAD_OFF_CURVE, "off the curve"),
+               (B.KEY_BAD_SUBGROUP, "outside the prime-order subgroup"))
+
+    def __init__(self, rep: B.KeyReportC, bad):
+        self.ok = bool(rep.ok)
+        self.relations_checked = bool(rep.relations_checked)
+        self.relations_failed = int(rep.relations_failed)
+        self.n_points = {q: int(rep.n_points[i]) for i, q in enumerate(B.KEY_QUERIES)}
+        self.n_bad = {q: int(rep.n_bad[i]) for i, q in enumerate(B.KEY_QUERIES)}
+        self.n_infinity = {q: int(rep.n_infinity[i]) for i, q in enumerate(B.KEY_QUERIES)}
+        self.bad = [(B.KEY_QUERIES[b.query], int(b.index), int(b.reason)) for b in bad]
+
+    def __eq__(self, o):
+        return isinstance(o, KeyReport) and vars(o) == vars(self)
+
+    def describe(self) -> str:
+        if self.ok:
+            return "ok"
+        if self.bad:
+            q, i, why = self.bad[0]
+            words = ", ".join(w for bit, w in self.REASONS if why & bit)
+            name = f"{B.KEY_SINGLES[i]}" if q == "singles" else f"{q}[{i}]"
+            return f"{name}: {words} (reason {why}); {sum(self.n_bad.values())} bad point(s) in all"
+        if not self.relations_checked:
+            return f"{sum(self.n_bad.values())} bad point(s)"
+        return "; ".join(w for bit, w in self.RELATIONS if self.relations_failed & bit)
+
+    def __repr__(self):
+        return f"KeyReport({self.describe()})"
+
+
+def check_key(pk: "ProvingKey", vk=None, rho=None, device=0, max_listed=64,
+              lib: Optional[B.Library] = None) -> KeyReport:
+    """Validation of a proving key on the GPU (g16_key_check): every point of every query canonical, on
+    its curve and (G2) in the prime-order subgroup; then e(beta_g1, g2) = e(g1, beta_g2), the same for
+    delta, and e(sum rho_i B1_i, g2) = e(g1, sum rho_i B2_i).  Call it once after read_zkey on a key you
+    did not mint.  A passing report means the key is well formed and internally consistent, NOT that it
+    belongs to your circuit (that needs the ceremony's powers of tau).
+    vk: None = pk.vk, False = skip the verifying-key part (IC, gamma_g2, the byte comparison).
+    rho: None (drawn by the library from the OS CSPRNG) or n_vars ints in [1, 2^128)."""
+    lib = lib or B.load()
+    kd = pk.to_c()
+    if vk is None:
+        vk = pk.vk
+    d = None
+    if vk is not False:
+        ic = np.ascontiguousarray(vk.gamma_abc_g1, dtype=np.uint8).reshape(-1, 64)
+        d = B.VkDesc()
+        C.memmove(d.alpha_g1, bytes(vk.alpha_g1), 64)
+        C.memmove(d.beta_g2, bytes(vk.beta_g2), 128)
+        C.memmove(d.gamma_g2, bytes(vk.gamma_g2), 128)
+        C.memmove(d.delta_g2, bytes(vk.delta_g2), 128)
+        d.ic, d.ic_count = ic.ctypes.data, ic.shape[0]
+    rho_arr = None
+    if rho is not None:
+        rho = [int(x) for x in rho]
+        if len(rho) != pk.n_vars:
+            raise G16Error(B.G16_ERR_INVALID, "one coefficient per wire")
+        if any(not 0 <= x < 1 << 128 for x in rho):
+            raise G16Error(B.G16_ERR_INVALID, "coefficients are integers in [1, 2^128)")
+        rho_arr = np.array([[x & 0xFFFFFFFFFFFFFFFF, x >> 64] for x in rho], dtype=np.uint64).reshape(-1, 2)
+    max_listed = int(max_listed)
+    bad = (B.KeyBadPoint * max(max_listed, 1))()
+    rep = B.KeyReportC()
+    st = lib.g16_key_check(device, C.byref(kd), C.byref(d) if d is not None else None,
+                           _np_ptr(rho_arr) if rho_arr is not None else None, bad, max_listed, C.byref(rep))
+    if st != B.G16_OK:
+        raise G16Error(st, "g16_key_check failed")
+    return KeyReport(rep, bad[:rep.n_listed])
 
 
 def verify_batch(vk: "VerifyingKey", proofs, public_inputs, device=0, lib: Optional[B.Library] = None):

@@ -67,6 +67,24 @@ class VkDesc(C.Structure):
                 ("delta_g2", C.c_uint8 * 128), ("ic", C.c_void_p), ("ic_count", C.c_uint32)]
 
 
+# g16_key_check: query ids, per-point reason bits, relation bits (include/g16_amd.h)
+KEY_QUERIES = ("a_query", "b_g1_query", "b_g2_query", "l_query", "h_query", "ic", "singles")
+KEY_Q_A, KEY_Q_B1, KEY_Q_B2, KEY_Q_L, KEY_Q_H, KEY_Q_IC, KEY_Q_SINGLES = range(7)
+KEY_SINGLES = ("alpha_g1", "beta_g1", "delta_g1", "beta_g2", "delta_g2", "gamma_g2")
+KEY_BAD_NONCANONICAL, KEY_BAD_OFF_CURVE, KEY_BAD_SUBGROUP = 1, 2, 4
+KEY_PAIR_BETA, KEY_PAIR_DELTA, KEY_PAIR_B, KEY_VK_MISMATCH = 1, 2, 4, 8
+
+
+class KeyBadPoint(C.Structure):
+    _fields_ = [("query", C.c_uint32), ("index", C.c_uint32), ("reason", C.c_uint32)]
+
+
+class KeyReportC(C.Structure):
+    _fields_ = [("ok", C.c_uint8), ("relations_checked", C.c_uint8), ("relations_failed", C.c_uint32),
+                ("n_points", C.c_uint64 * 7), ("n_bad", C.c_uint64 * 7), ("n_infinity", C.c_uint64 * 7),
+                ("n_listed", C.c_uint32)]
+
+
 class ZkeyHeader(C.Structure):
     _fields_ = [("n8q", C.c_uint32), ("n8r", C.c_uint32), ("q", C.c_uint8 * 32),
                 ("r", C.c_uint8 * 32), ("n_vars", C.c_uint32), ("n_public", C.c_uint32),
@@ -105,6 +123,7 @@ ABI_SYMBOLS = [
     "g16_r1cs_wire_mapping", "g16_wtns_read", "g16_wtns_read_mem", "g16_free",
     "g16_fr_from_canonical", "g16_fr_to_canonical",
     "g16_prove_batch", "g16_prove_batch_dev", "g16_witness_map_batch",
+    "g16_key_check",
 ]
 
 
@@ -161,6 +180,8 @@ class Library:
             "g16_witness_host_buffer": (vp, [vp]),
             "g16_verify_batch": (C.c_int, [C.c_int, C.POINTER(VkDesc), vp, vp, C.c_uint32, vp]),
             "g16_verify_aggregate": (C.c_int, [C.c_int, C.POINTER(VkDesc), vp, vp, C.c_uint32, vp, vp, vp]),
+            "g16_key_check": (C.c_int, [C.c_int, C.POINTER(KeyDesc), C.POINTER(VkDesc), vp, C.POINTER(KeyBadPoint),
+                                        C.c_uint32, C.POINTER(KeyReportC)]),
             "g16_witness_upload": (C.c_int, [vp, vp, C.c_size_t]),
             "g16_witness_map_dev": (C.c_int, [vp, vp, C.c_size_t, vp]),
             "g16_msm_g1_dev": (C.c_int, [vp, C.c_int, vp, C.c_size_t, vp]),

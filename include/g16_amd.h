@@ -356,6 +356,71 @@ g16_status g16_verify_aggregate(int device, const g16_vk_desc* vk, const uint8_t
                                 const uint64_t* public_inputs, uint32_t n_proofs,
                                 const uint64_t* rho, uint8_t* ok_out, uint8_t* structural_out);
 
+/* ---- proving-key validation (not on the proving path) ------------------------------------------- */
+/* The loaders (g16_zkey_open, like the reference's deserialize_g1 / deserialize_g2, src/zkey.rs:328-360:
+ * `new_unchecked`) copy the point sections of a key as they come, and g16_ctx_create builds tables from
+ * whatever it is given: a key with a flipped bit, a b_g2_query point outside G2 or a b_g1_query that does
+ * not match b_g2_query proves at full speed and every proof is garbage.  g16_key_check is what
+ * ark-serialize's Validate::Yes / `snarkjs zkey verify` (its point checks) do for such a key, on the GPU:
+ * call it once after loading a key that was not minted locally.  Standalone: no ctx is needed, a ctx
+ * alive on the device is left untouched.
+ *
+ * Structural checks, on EVERY point of every query and on the single points -- the three tests
+ * g16_verify_batch applies to the points of a proof:
+ *   G16_KEY_BAD_NONCANONICAL  one of the 8 (G1) / 16 (G2) stored 32-byte words is >= q
+ *   G16_KEY_BAD_OFF_CURVE     not on y^2 = x^3 + 3 / on the twist y^2 = x^3 + 3 / (9 + i)
+ *   G16_KEY_BAD_SUBGROUP      G2 only: [r] P != infinity (the twist has the cofactor 2q - r; G1 has 1)
+ * A point's reason is the FIRST test it fails, in that order (field arithmetic on a value >= q and the
+ * group law on a point off the curve mean nothing, so the later tests are not evaluated).  The all-zero
+ * encoding is the point at infinity: valid, counted in n_infinity.
+ * Queries: A, B1, B2, L, H of the key; IC = vk->ic (n_points 0 without vk); SINGLES, index 0 alpha_g1,
+ * 1 beta_g1, 2 delta_g1, 3 beta_g2, 4 delta_g2, 5 vk->gamma_g2 (5 points without vk).
+ * bad_out receives the first min(bad_cap, 65536) bad points in ascending (query, index) order -- the same
+ * list on every run (built by scans, no atomics); n_bad counts all of them.
+ *
+ * Relations, evaluated only when no structural check failed (relations_checked = 0 and relations_failed
+ * = 0 otherwise: a pairing of a malformed point means nothing):
+ *   G16_KEY_PAIR_BETA    e(beta_g1, g2)  != e(g1, beta_g2)
+ *   G16_KEY_PAIR_DELTA   e(delta_g1, g2) != e(g1, delta_g2)
+ *   G16_KEY_PAIR_B       e(sum_i rho_i b_g1_query[i], g2) != e(g1, sum_i rho_i b_g2_query[i]) over all n_vars
+ *                        entries: the two B queries hold the same scalars.  With unpredictable rho a key
+ *                        whose queries differ in any entry passes with probability at most 2^-127 (the
+ *                        small-exponent test of g16_verify_aggregate; whoever knows rho can make two
+ *                        entries cancel: B1_j + rho_k D, B1_k - rho_j D).
+ *   G16_KEY_VK_MISMATCH  vk given: vk->alpha_g1 / beta_g2 / delta_g2 differ from the key's bytes, or
+ *                        vk->ic_count != n_public + 1
+ * (g1, g2: the standard generators, against which snarkjs and arkworks keys are made.)
+ * rho: n_vars x 2 u64 (little-endian 128-bit integers, NOT Montgomery), every one non-zero (a zero entry:
+ *      G16_ERR_INVALID), or NULL: drawn from the operating system's CSPRNG as g16_verify_aggregate does (a
+ *      failure to get randomness is G16_ERR_INTERNAL, never a fixed fallback).
+ *
+ * NOT checked: that the key belongs to a circuit.  The A / L / H queries and IC cannot be tied to the R1CS
+ * without the ceremony's powers of tau, and the matrices are not looked at.  report->ok = 1 means the key
+ * is well formed and internally consistent -- proofs made with it are then at least proofs under the key's
+ * own verifying key -- not that it is the key of your circuit.
+ *
+ * Memory: the queries are streamed through two page-locked host slots and two device slots of
+ * min(2^18, longest query) points (208 bytes per point), the copy of one chunk under the kernels of the
+ * one before; device use does not grow with the key.  G16_KEYCHECK_CHUNK=<points> overrides the chunk
+ * (tests).  Returns G16_OK when the check RAN (the verdict is in *report), G16_ERR_INVALID for bad
+ * arguments, G16_ERR_NO_DEVICE without a device: there is no CPU fallback.                           */
+enum { G16_KEY_Q_A = 0, G16_KEY_Q_B1, G16_KEY_Q_B2, G16_KEY_Q_L, G16_KEY_Q_H, G16_KEY_Q_IC,
+       G16_KEY_Q_SINGLES /* index: 0 alpha_g1 1 beta_g1 2 delta_g1 3 beta_g2 4 delta_g2 5 vk.gamma_g2 */,
+       G16_KEY_N_QUERIES };
+enum { G16_KEY_BAD_NONCANONICAL = 1, G16_KEY_BAD_OFF_CURVE = 2, G16_KEY_BAD_SUBGROUP = 4 };   /* per-point reason bits */
+enum { G16_KEY_PAIR_BETA = 1, G16_KEY_PAIR_DELTA = 2, G16_KEY_PAIR_B = 4, G16_KEY_VK_MISMATCH = 8 }; /* report.relations_failed */
+typedef struct { uint32_t query, index, reason; } g16_key_bad_point;
+typedef struct {
+  uint8_t  ok;                 /* 1 iff no bad point and no failed relation */
+  uint8_t  relations_checked;  /* 0 when a structural failure made the pairing relations meaningless */
+  uint32_t relations_failed;   /* G16_KEY_PAIR_* | G16_KEY_VK_MISMATCH */
+  uint64_t n_points[G16_KEY_N_QUERIES], n_bad[G16_KEY_N_QUERIES], n_infinity[G16_KEY_N_QUERIES];
+  uint32_t n_listed;           /* entries written to bad_out */
+} g16_key_report;
+g16_status g16_key_check(int device, const g16_key_desc* key, const g16_vk_desc* vk /* NULL ok */,
+                         const uint64_t* rho /* n_vars x 2 u64, NULL = CSPRNG */,
+                         g16_key_bad_point* bad_out, uint32_t bad_cap, g16_key_report* report);
+
 /* ---- RCCL inside the library (north_star: "a final RCCL all-reduce of partial bucket sums over xGMI") ---- */
 /* A host that is not PyTorch (the Rust shim) creates one per-rank ctx per process (g16_options.rank / world,
  * dist_wm = 1) and ONE ncclComm_t over the same ranks with its own RCCL (ncclGetUniqueId / ncclCommInitRank),

@@ -25,6 +25,22 @@ pub const G16_QUERY_A: c_int = 0;
 pub const G16_QUERY_B1: c_int = 1;
 pub const G16_QUERY_L: c_int = 2;
 pub const G16_QUERY_H: c_int = 3;
+// g16_key_check: query ids, per-point reason bits, report.relations_failed bits
+pub const G16_KEY_Q_A: u32 = 0;
+pub const G16_KEY_Q_B1: u32 = 1;
+pub const G16_KEY_Q_B2: u32 = 2;
+pub const G16_KEY_Q_L: u32 = 3;
+pub const G16_KEY_Q_H: u32 = 4;
+pub const G16_KEY_Q_IC: u32 = 5;
+pub const G16_KEY_Q_SINGLES: u32 = 6;
+pub const G16_KEY_N_QUERIES: usize = 7;
+pub const G16_KEY_BAD_NONCANONICAL: u32 = 1;
+pub const G16_KEY_BAD_OFF_CURVE: u32 = 2;
+pub const G16_KEY_BAD_SUBGROUP: u32 = 4;
+pub const G16_KEY_PAIR_BETA: u32 = 1;
+pub const G16_KEY_PAIR_DELTA: u32 = 2;
+pub const G16_KEY_PAIR_B: u32 = 4;
+pub const G16_KEY_VK_MISMATCH: u32 = 8;
 
 #[repr(C)]
 pub struct g16_ctx {
@@ -145,6 +161,26 @@ pub struct g16_r1cs_header {
     pub num_variables: u32,
 }
 
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct g16_key_bad_point {
+    pub query: u32,
+    pub index: u32,
+    pub reason: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct g16_key_report {
+    pub ok: u8,
+    pub relations_checked: u8,
+    pub relations_failed: u32,
+    pub n_points: [u64; G16_KEY_N_QUERIES],
+    pub n_bad: [u64; G16_KEY_N_QUERIES],
+    pub n_infinity: [u64; G16_KEY_N_QUERIES],
+    pub n_listed: u32,
+}
+
 extern "C" {
     // ---- include/g16_amd.h ---------------------------------------------------------------------
     pub fn g16_ctx_create(key: *const g16_key_desc, a: *const g16_csr, b: *const g16_csr, num_constraints: u32, opt: *const g16_options, out: *mut *mut g16_ctx) -> g16_status;
@@ -193,6 +229,7 @@ extern "C" {
     pub fn g16_check_satisfied(device: c_int, a: *const g16_csr, b: *const g16_csr, c: *const g16_csr, num_constraints: u32, w: *const u64, n_vars: usize, first_unsatisfied: *mut i64) -> g16_status;
     pub fn g16_verify_batch(device: c_int, vk: *const g16_vk_desc, proofs: *const u8, public_inputs: *const u64, n_proofs: u32, ok_out: *mut u8) -> g16_status;
     pub fn g16_verify_aggregate(device: c_int, vk: *const g16_vk_desc, proofs: *const u8, public_inputs: *const u64, n_proofs: u32, rho: *const u64, ok_out: *mut u8, structural_out: *mut u8) -> g16_status;
+    pub fn g16_key_check(device: c_int, key: *const g16_key_desc, vk: *const g16_vk_desc, rho: *const u64, bad_out: *mut g16_key_bad_point, bad_cap: u32, report: *mut g16_key_report) -> g16_status;
     pub fn g16_dist_attach_rccl(ctx: *mut g16_ctx, nccl_comm: *mut c_void) -> g16_status;
     pub fn g16_dist_rccl_ranks(ctx: *const g16_ctx) -> c_int;
     pub fn g16_prove_dist(ctx: *mut g16_ctx, r: *const u64, s: *const u64, w_dev: *const c_void, n_vars: usize, proof_out: *mut u8) -> g16_status;

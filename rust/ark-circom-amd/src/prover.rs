@@ -167,6 +167,90 @@ impl GpuProver {
         Ok(pack::unpack_proof(&raw))
     }
 
+    /// Validation of a proving key on the GPU (`g16_key_check`, include/g16_amd.h) -- no prover is needed.
+    /// `read_zkey` builds its points with `new_unchecked` (src/zkey.rs:328-360), so a corrupted or hostile
+    /// `.zkey` yields a `ProvingKey` that proves at full speed and whose proofs never verify: call this once
+    /// on a key you did not mint.  Every point of every query (and of `pk.vk`) is tested for canonical
+    /// coordinates, its curve equation and (G2) the prime-order subgroup; then `e(beta_g1, g2) = e(g1, beta_g2)`,
+    /// the same for delta, and `e(sum rho_i B1_i, g2) = e(g1, sum rho_i B2_i)`.  `rho`: `None` (drawn by the
+    /// library from the operating system's CSPRNG) or one non-zero 128-bit coefficient per wire.
+    /// Returns the report and the first `max_listed` bad points in `(query, index)` order.  A passing
+    /// report means the key is well formed and internally consistent, NOT that it belongs to your circuit.
+    pub fn check_key(
+        pk: &ProvingKey<Bn254>,
+        rho: Option<&[u128]>,
+        device: i32,
+        max_listed: usize,
+    ) -> Result<(ffi::g16_key_report, Vec<ffi::g16_key_bad_point>), GpuError> {
+        let n_vars = pk.a_query.len();
+        if pk.b_g1_query.len() != n_vars || pk.b_g2_query.len() != n_vars || pk.vk.gamma_abc_g1.is_empty() {
+            return Err(GpuError::Library(ffi::G16_ERR_INVALID, "query lengths differ".into()));
+        }
+        let n_public = pk.vk.gamma_abc_g1.len() - 1;
+        if pk.l_query.len() + n_public + 1 != n_vars {
+            return Err(GpuError::Library(ffi::G16_ERR_INVALID, "l_query length is not n_vars - n_public - 1".into()));
+        }
+        if let Some(r) = rho {
+            if r.len() != n_vars {
+                return Err(GpuError::Library(ffi::G16_ERR_INVALID, "one coefficient per wire".into()));
+            }
+        }
+        let a = pack::pack_g1_vec(&pk.a_query);
+        let b1 = pack::pack_g1_vec(&pk.b_g1_query);
+        let b2 = pack::pack_g2_vec(&pk.b_g2_query);
+        let l = pack::pack_g1_vec(&pk.l_query);
+        let h = pack::pack_g1_vec(&pk.h_query);
+        let ic = pack::pack_g1_vec(&pk.vk.gamma_abc_g1);
+        let mut key = ffi::g16_key_desc {
+            n_vars: n_vars as u32,
+            n_public: n_public as u32,
+            domain_size: pk.h_query.len() as u32, // the points that are there: no padding to check
+            a_query: a.as_ptr(),
+            b_g1_query: b1.as_ptr(),
+            b_g2_query: b2.as_ptr(),
+            l_query: l.as_ptr(),
+            h_query: h.as_ptr(),
+            alpha_g1: [0; 64],
+            beta_g1: [0; 64],
+            delta_g1: [0; 64],
+            beta_g2: [0; 128],
+            delta_g2: [0; 128],
+        };
+        pack::pack_g1(&pk.vk.alpha_g1, &mut key.alpha_g1);
+        pack::pack_g1(&pk.beta_g1, &mut key.beta_g1);
+        pack::pack_g1(&pk.delta_g1, &mut key.delta_g1);
+        pack::pack_g2(&pk.vk.beta_g2, &mut key.beta_g2);
+        pack::pack_g2(&pk.vk.delta_g2, &mut key.delta_g2);
+        let mut vk = ffi::g16_vk_desc {
+            alpha_g1: key.alpha_g1,
+            beta_g2: key.beta_g2,
+            gamma_g2: [0; 128],
+            delta_g2: key.delta_g2,
+            ic: ic.as_ptr(),
+            ic_count: pk.vk.gamma_abc_g1.len() as u32,
+        };
+        pack::pack_g2(&pk.vk.gamma_g2, &mut vk.gamma_g2);
+        let words: Option<Vec<u64>> = rho.map(|r| r.iter().flat_map(|x| [*x as u64, (*x >> 64) as u64]).collect());
+        let mut bad = vec![ffi::g16_key_bad_point::default(); max_listed];
+        let mut report = ffi::g16_key_report::default();
+        let st = unsafe {
+            ffi::g16_key_check(
+                device as c_int,
+                &key,
+                &vk,
+                words.as_ref().map_or(std::ptr::null(), |w| w.as_ptr()),
+                if max_listed == 0 { std::ptr::null_mut() } else { bad.as_mut_ptr() },
+                max_listed as u32,
+                &mut report,
+            )
+        };
+        if st != ffi::G16_OK {
+            return Err(GpuError::Library(st, "g16_key_check failed".into()));
+        }
+        bad.truncate(report.n_listed as usize);
+        Ok((report, bad))
+    }
+
     /// packs the key and the matrices once and hands them to `make` (g16_ctx_create / _multi)
     fn create_with(
         pk: &ProvingKey<Bn254>,
