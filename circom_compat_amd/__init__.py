@@ -37,7 +37,8 @@ __all__ = ["read_zkey", "R1CSFile", "R1CS", "CircomCircuit", "CircomBuilder", "C
            "Prover", "ProvingKey", "VerifyingKey", "ConstraintMatrices", "Proof", "G16Error",
            "SynthesisError", "SerializationError", "fr_from_ints", "fr_to_ints", "read_wtns",
            "trapdoor_setup", "Csr", "write_zkey", "device_tensor", "verify_batch", "verify_aggregate",
-           "verify_batch_fast", "check_key", "KeyReport"]
+           "verify_batch_fast", "check_key", "KeyReport", "contribute_key", "check_contribution",
+           "ContributionReport"]
 
 FR_MODULUS = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 
@@ -878,6 +879,105 @@ def check_key(pk: "ProvingKey", vk=None, rho=None, device=0, max_listed=64,
     if st != B.G16_OK:
         raise G16Error(st, "g16_key_check failed")
     return KeyReport(rep, bad[:rep.n_listed])
+
+
+def contribute_key(pk: "ProvingKey", d=None, device=0, lib: Optional[B.Library] = None) -> "ProvingKey":
+    """One phase-2 contribution on the GPU (g16_key_contribute): delta_g1 and delta_g2 times d, every point of
+    l_query and h_query times d^-1 -- the key of (tau, alpha, beta, gamma, delta) becomes the key of
+    (tau, alpha, beta, gamma, delta * d).  Returns a NEW ProvingKey with new l_query, h_query, delta_g1 and
+    vk.delta_g2; a_query, b_g1_query, b_g2_query and vk.gamma_abc_g1 are shared with pk.  write_zkey takes it
+    as it is.  d: an int in [1, r), or None: drawn by the library from the OS CSPRNG and never returned.
+    The snarkjs contribution transcript (challenge hash, proof of knowledge of d) is NOT produced."""
+    lib = lib or B.load()
+    kd = pk.to_c()
+    d_arr = None
+    if d is not None:
+        d = int(d)
+        if not 0 < d < FR_MODULUS:
+            raise G16Error(B.G16_ERR_INVALID, "d is an integer in [1, r)")
+        d_arr = fr_from_ints([d], lib)
+    l_out = np.empty((pk.n_vars - pk.n_public - 1, 64), dtype=np.uint8)
+    h_out = np.empty((pk.domain_size, 64), dtype=np.uint8)
+    d1, d2 = (C.c_uint8 * 64)(), (C.c_uint8 * 128)()
+    st = lib.g16_key_contribute(device, C.byref(kd), _np_ptr(d_arr) if d_arr is not None else None,
+                                _np_ptr(l_out), _np_ptr(h_out), d1, d2)
+    if st != B.G16_OK:
+        raise G16Error(st, "g16_key_contribute failed")
+    vk = VerifyingKey(pk.vk.alpha_g1, pk.vk.beta_g2, pk.vk.gamma_g2, bytes(d2), pk.vk.gamma_abc_g1)
+    return ProvingKey(pk.n_vars, pk.n_public, pk.domain_size, vk, pk.beta_g1, bytes(d1), pk.a_query,
+                      pk.b_g1_query, pk.b_g2_query, l_out, h_out, keepalive=pk)
+
+
+class ContributionReport:
+    """g16_contribution_report + the bad-point list of g16_key_contribution_check.  ok: nothing but delta
+    changed, no bad point, no failed relation; relations_checked: False when a structural failure (or keys of
+    different sizes) made the pairing relations meaningless; relations_failed: CONTRIB_* bits (_binding);
+    n_bad: {"l_query", "h_query"} counts; bad: [(query_name, index, reason_bits)] in ascending (query, index)
+    order, at most max_listed ("singles" index 2 = delta_g1, 4 = delta_g2)."""
+    RELATIONS = ((B.CONTRIB_UNCHANGED_MISMATCH, "something other than delta, l_query and h_query differs"),
+                 (B.CONTRIB_DELTA_INFINITE, "delta is the point at infinity"),
+                 (B.CONTRIB_PAIR_DELTA, "e(delta_g1', g2) != e(g1, delta_g2')"),
+                 (B.CONTRIB_PAIR_L, "l_query was not scaled by the inverse of delta's factor"),
+                 (B.CONTRIB_PAIR_H, "h_query was not scaled by the inverse of delta's factor"))
+
+    def __init__(self, rep: B.ContributionReportC, bad):
+        self.ok = bool(rep.ok)
+        self.relations_checked = bool(rep.relations_checked)
+        self.relations_failed = int(rep.relations_failed)
+        self.n_bad = {"l_query": int(rep.n_bad_l), "h_query": int(rep.n_bad_h)}
+        self.bad = [(B.KEY_QUERIES[b.query], int(b.index), int(b.reason)) for b in bad]
+
+    def __eq__(self, o):
+        return isinstance(o, ContributionReport) and vars(o) == vars(self)
+
+    def describe(self) -> str:
+        if self.ok:
+            return "ok"
+        if self.bad:
+            q, i, why = self.bad[0]
+            words = ", ".join(w for bit, w in KeyReport.REASONS if why & bit)
+            name = f"{B.KEY_SINGLES[i]}" if q == "singles" else f"{q}[{i}]"
+            return f"{name}: {words} (reason {why}); {len(self.bad)} bad point(s) listed"
+        if self.relations_failed:
+            return "; ".join(w for bit, w in self.RELATIONS if self.relations_failed & bit)
+        return f"{sum(self.n_bad.values())} bad point(s)"
+
+    def __repr__(self):
+        return f"ContributionReport({self.describe()})"
+
+
+def check_contribution(before: "ProvingKey", after: "ProvingKey", rho=None, device=0, max_listed=64,
+                       lib: Optional[B.Library] = None) -> ContributionReport:
+    """Is `after` the key `before` with only delta re-randomised (g16_key_contribution_check)?  Bytes of
+    everything a contribution leaves alone, structure of after's delta, l_query and h_query, then
+    e(delta_g1', g2) = e(g1, delta_g2') and e(sum rho_i L_i, delta_g2) = e(sum rho_i L'_i, delta_g2') for L and
+    for H.  `before` should have passed check_key.  vk.gamma_g2 and vk.gamma_abc_g1 are compared here (they are
+    not part of the C key descriptor).  rho: None (drawn by the library from the OS CSPRNG) or
+    len(l_query) + len(h_query) ints in [1, 2^128), L's first.  The contribution transcript is NOT checked."""
+    lib = lib or B.load()
+    kb, ka = before.to_c(), after.to_c()
+    rho_arr = None
+    if rho is not None:
+        rho = [int(x) for x in rho]
+        if len(rho) != before.n_vars - before.n_public - 1 + before.domain_size:
+            raise G16Error(B.G16_ERR_INVALID, "one coefficient per point of l_query and h_query")
+        if any(not 0 <= x < 1 << 128 for x in rho):
+            raise G16Error(B.G16_ERR_INVALID, "coefficients are integers in [1, 2^128)")
+        rho_arr = np.array([[x & 0xFFFFFFFFFFFFFFFF, x >> 64] for x in rho], dtype=np.uint64).reshape(-1, 2)
+    max_listed = int(max_listed)
+    bad = (B.KeyBadPoint * max(max_listed, 1))()
+    rep = B.ContributionReportC()
+    st = lib.g16_key_contribution_check(device, C.byref(kb), C.byref(ka),
+                                        _np_ptr(rho_arr) if rho_arr is not None else None, bad, max_listed,
+                                        C.byref(rep))
+    if st != B.G16_OK:
+        raise G16Error(st, "g16_key_contribution_check failed")
+    out = ContributionReport(rep, bad[:rep.n_listed])
+    if bytes(before.vk.gamma_g2) != bytes(after.vk.gamma_g2) or not np.array_equal(
+            np.asarray(before.vk.gamma_abc_g1), np.asarray(after.vk.gamma_abc_g1)):
+        out.relations_failed |= B.CONTRIB_UNCHANGED_MISMATCH
+        out.ok = False
+    return out
 
 
 def verify_batch(vk: "VerifyingKey", proofs, public_inputs, device=0, lib: Optional[B.Library] = None):

@@ -85,6 +85,15 @@ class KeyReportC(C.Structure):
                 ("n_listed", C.c_uint32)]
 
 
+# g16_key_contribution_check: report.relations_failed bits
+CONTRIB_UNCHANGED_MISMATCH, CONTRIB_PAIR_DELTA, CONTRIB_PAIR_L, CONTRIB_PAIR_H, CONTRIB_DELTA_INFINITE = 1, 2, 4, 8, 16
+
+
+class ContributionReportC(C.Structure):
+    _fields_ = [("ok", C.c_uint8), ("relations_checked", C.c_uint8), ("relations_failed", C.c_uint32),
+                ("n_bad_l", C.c_uint64), ("n_bad_h", C.c_uint64), ("n_listed", C.c_uint32)]
+
+
 class ZkeyHeader(C.Structure):
     _fields_ = [("n8q", C.c_uint32), ("n8r", C.c_uint32), ("q", C.c_uint8 * 32),
                 ("r", C.c_uint8 * 32), ("n_vars", C.c_uint32), ("n_public", C.c_uint32),
@@ -123,7 +132,7 @@ ABI_SYMBOLS = [
     "g16_r1cs_wire_mapping", "g16_wtns_read", "g16_wtns_read_mem", "g16_free",
     "g16_fr_from_canonical", "g16_fr_to_canonical",
     "g16_prove_batch", "g16_prove_batch_dev", "g16_witness_map_batch",
-    "g16_key_check",
+    "g16_key_check", "g16_key_contribute", "g16_key_contribution_check",
 ]
 
 
@@ -182,6 +191,10 @@ class Library:
             "g16_verify_aggregate": (C.c_int, [C.c_int, C.POINTER(VkDesc), vp, vp, C.c_uint32, vp, vp, vp]),
             "g16_key_check": (C.c_int, [C.c_int, C.POINTER(KeyDesc), C.POINTER(VkDesc), vp, C.POINTER(KeyBadPoint),
                                         C.c_uint32, C.POINTER(KeyReportC)]),
+            "g16_key_contribute": (C.c_int, [C.c_int, C.POINTER(KeyDesc), vp, vp, vp, vp, vp]),
+            "g16_key_contribution_check": (C.c_int, [C.c_int, C.POINTER(KeyDesc), C.POINTER(KeyDesc), vp,
+                                                     C.POINTER(KeyBadPoint), C.c_uint32,
+                                                     C.POINTER(ContributionReportC)]),
             "g16_witness_upload": (C.c_int, [vp, vp, C.c_size_t]),
             "g16_witness_map_dev": (C.c_int, [vp, vp, C.c_size_t, vp]),
             "g16_msm_g1_dev": (C.c_int, [vp, C.c_int, vp, C.c_size_t, vp]),

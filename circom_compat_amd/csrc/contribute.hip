@@ -1,0 +1,618 @@
+// contribute.hip -- phase-2 delta contributions: apply one (g16_key_contribute) and verify one
+// (g16_key_contribution_check).  What `snarkjs zkey contribute` does to the points of a key and what the
+// sameRatio part of `snarkjs zkey verify` checks of them; the section-10 transcript is NOT handled
+// (include/g16_amd.h).
+//
+// g16_key_contribute: delta1' = d delta1, delta2' = d delta2 (two points: on the host, the same field classes),
+// and every point of the L and H queries times d^-1 -- the streamed part.  Per chunk of `chunk` points:
+//   k_ct_mul     one lane per point: e P for the full-width e = d^-1, the same for every lane.  e is recoded
+//                ONCE on the host into its non-adjacent form (digits 0 / +1 / -1, two bit masks read by
+//                wave-uniform scalar loads): 254 doublings and ~85 MIXED additions of +-P (8M + 2S each, P
+//                stays affine in registers).  No per-lane table: a window of w bits would trade these for
+//                2^(w-2) full XYZZ additions (12M + 2S) plus 1 KiB of table per lane, which is scratch.
+//                No divergence: the digit schedule is uniform, only lanes at infinity idle.
+//   k_ct_affine  back to canonical affine with ONE Fermat inversion per CT_RUN points (Montgomery's trick down
+//                each lane's run of 8): 3 multiplications per point for the shared inverse instead of ~380.
+// Two page-locked host slots and two device slots; chunk k + 1 is staged and copied while the kernels of chunk k
+// run, and the results of chunk k come back on a third stream under the kernels of chunk k + 1.
+//
+// g16_key_contribution_check: keycheck.hip's structure on the points a contribution changes.  Per chunk of a
+// query (L or H), the AFTER points, the BEFORE points and rho side by side in one slot:
+//   k_cc_g1      reason byte per AFTER point       k_cc_rho / k_cc_fold   sum rho_i P_i over both sides
+//   k_cc_collect counts / lists the bad points by a scan (no atomics)
+//   k_cc_final   six Miller loops, three final exponentiations, the report and the list.
+#include <stdlib.h>
+
+#include <memory>
+
+#include "keycheck.h"
+
+namespace g16 {
+namespace {
+
+constexpr uint32_t CT_DEFAULT_CHUNK = 1u << 18;
+constexpr uint32_t CT_RUN = 8;  // points per lane of k_ct_affine: one inversion per CT_RUN points
+constexpr uint32_t CC_SLOT_BYTES_PER_POINT = 64 + 64 + 16;  // AFTER | BEFORE | rho
+
+// e = sum (pos_i - neg_i) 2^i, non-adjacent; top = index of the leading digit (always +1)
+struct CtSched {
+  uint32_t pos[8], neg[8];
+  int32_t top;
+};
+
+// non-adjacent form of a canonical e, 0 < e < r < 2^254: at most 255 digits
+CtSched naf_of(const U256& e) {
+  CtSched s;
+  memset(&s, 0, sizeof s);
+  uint32_t k[9];
+  for (int i = 0; i < 8; ++i) k[i] = e.v[i];
+  k[8] = 0;
+  s.top = -1;
+  for (int bit = 0; bit < 256; ++bit) {
+    if (k[0] & 1) {
+      if ((k[0] & 3) == 3) {  // digit -1: k += 1
+        s.neg[bit >> 5] |= 1u << (bit & 31);
+        for (int i = 0; i < 9 && ++k[i] == 0; ++i) {
+        }
+      } else {  // digit +1: k -= 1
+        s.pos[bit >> 5] |= 1u << (bit & 31);
+        k[0] &= ~1u;
+        s.top = bit;
+      }
+    }
+    for (int i = 0; i < 8; ++i) k[i] = (k[i] >> 1) | (k[i + 1] << 31);
+    k[8] >>= 1;
+  }
+  return s;
+}
+
+void wipe(void* p, size_t n) {
+  volatile uint8_t* v = (volatile uint8_t*)p;
+  while (n--) *v++ = 0;
+}
+
+bool fr_words_canonical(const Fr& a) {
+  for (int i = 7; i >= 0; --i) {
+    if (a.v[i] < FrParams::MOD[i]) return true;
+    if (a.v[i] > FrParams::MOD[i]) return false;
+  }
+  return false;
+}
+
+// ---- g16_key_contribute ------------------------------------------------------------------------------
+__global__ void __launch_bounds__(KC_BLOCK) k_ct_mul(const G1Affine* pts, uint32_t n, const CtSched* sched,
+                                                     G1XYZZ* work) {
+  const uint32_t i = blockIdx.x * KC_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const G1Affine p = pts[i];
+  const G1Affine np = p.neg();
+  G1XYZZ acc = G1XYZZ::from_affine(p);  // the leading digit
+#pragma unroll 1
+  for (int b = sched->top - 1; b >= 0; --b) {
+    acc.dbl_in_place();
+    const uint32_t m = 1u << (b & 31);
+    if (sched->pos[b >> 5] & m) {
+      acc.madd(p);
+    } else if (sched->neg[b >> 5] & m) {
+      acc.madd(np);
+    }
+  }
+  work[i] = acc;
+}
+
+// lane t of block g owns the points g * 64 * CT_RUN + j * 64 + t, j < CT_RUN (neighbouring lanes, neighbouring
+// points).  Prefix products of the ZZZ down the run (an infinite point counts as 1), one inversion, then back
+// up: 1/ZZZ_j = inv(prefix_j ZZZ_j) prefix_j.  1/ZZ = (ZZ / ZZZ)^2 as in XYZZ::to_affine.  The prefixes wait in
+// the x half of the output entry they belong to (written here, read back by the same lane): a register array
+// of CT_RUN field elements would be indexed by the loop counter and end up in scratch.
+__global__ void __launch_bounds__(KC_BLOCK) k_ct_affine(const G1XYZZ* work, uint32_t n, G1Affine* out) {
+  const uint32_t first = blockIdx.x * (KC_BLOCK * CT_RUN) + threadIdx.x;
+  Fq run = Fq::one();
+  uint32_t cnt = 0;
+#pragma unroll 1
+  for (uint32_t i = first; cnt < CT_RUN && i < n; ++cnt, i += KC_BLOCK) {
+    out[i].x = run;
+    const Fq z = work[i].zzz;
+    if (!z.is_zero()) run = run * z;
+  }
+  Fq inv = run.inv();
+#pragma unroll 1
+  for (; cnt > 0; --cnt) {
+    const uint32_t i = first + (cnt - 1) * KC_BLOCK;
+    const G1XYZZ P = work[i];
+    if (P.zzz.is_zero()) {
+      out[i] = G1Affine::infinity();
+      continue;
+    }
+    const Fq iz3 = inv * out[i].x;
+    inv = inv * P.zzz;
+    const Fq iz2 = (iz3 * P.zz).sqr();
+    out[i] = G1Affine{P.x * iz2, P.y * iz3};
+  }
+}
+
+// ---- g16_key_contribution_check ----------------------------------------------------------------------
+enum { CC_L = 0, CC_H = 1, CC_SINGLES = 2, CC_N = 3 };
+constexpr uint32_t CC_QUERY_ID[CC_N] = {G16_KEY_Q_L, G16_KEY_Q_H, G16_KEY_Q_SINGLES};
+
+struct CcKey {
+  G1Affine delta_g1_after, g1_neg;
+  G2Affine delta_g2_before, delta_g2_after, g2;
+};
+
+struct CcState {  // device-resident for the whole call
+  uint64_t n_bad[CC_N];
+  uint32_t n_list[CC_N];
+  G1XYZZ sum[2][2];  // [L, H][before, after]: sum rho_i P_i so far
+  g16_contribution_report report;
+};
+
+__global__ void __launch_bounds__(KC_BLOCK) k_cc_g1(const G1Affine* pts, uint32_t n, uint8_t* flags) {
+  const uint32_t i = blockIdx.x * KC_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  flags[i] = g1_flag(pts[i]);
+}
+
+__global__ void __launch_bounds__(KC_BLOCK) k_cc_g2(const VkDev* vk, const G2Affine* pts, uint32_t n, uint8_t* flags) {
+  const uint32_t i = blockIdx.x * KC_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  flags[i] = g2_flag(pts[i], vk);
+}
+
+// blockIdx.y = 0: part[block] = sum over the block of rho_i BEFORE_i; 1: part[nb + block] = the same over AFTER.
+// Entry i is left out on both sides when AFTER_i is malformed: the relations are not reported then anyway.
+__global__ void __launch_bounds__(KC_BLOCK) k_cc_rho(const G1Affine* before, const G1Affine* after, const uint64_t* rho,
+                                                     const uint8_t* flags, uint32_t n, G1XYZZ* part) {
+  __shared__ G1XYZZ sh[KC_BLOCK];
+  const uint32_t t = threadIdx.x, i = blockIdx.x * KC_BLOCK + t;
+  G1XYZZ acc = G1XYZZ::infinity();
+  if (i < n && !(flags[i] & ~KC_INF))
+    acc = mul_rho((blockIdx.y ? after : before)[i], rho[2 * (size_t)i], rho[2 * (size_t)i + 1]);
+  kc_block_sum(sh, acc);
+  if (t == 0) part[blockIdx.y * gridDim.x + blockIdx.x] = sh[0];
+}
+
+// one block: the chunk's 2 x nb block sums into the two running sums of query q
+__global__ void __launch_bounds__(KC_BLOCK) k_cc_fold(const G1XYZZ* part, uint32_t nb, uint32_t q, CcState* st) {
+  __shared__ G1XYZZ sh[KC_BLOCK];
+  const uint32_t t = threadIdx.x;
+#pragma unroll 1
+  for (uint32_t side = 0; side < 2; ++side) {
+    G1XYZZ a = G1XYZZ::infinity();
+#pragma unroll 1
+    for (uint32_t k = t; k < nb; k += KC_BLOCK) a.add(part[side * nb + k]);
+    kc_block_sum(sh, a);
+    if (t == 0) {
+      G1XYZZ s = st->sum[q][side];
+      s.add(sh[0]);
+      st->sum[q][side] = s;
+    }
+    __syncthreads();
+  }
+}
+
+// k_kc_collect of keycheck.hip on this call's state: lane t owns a contiguous run of the chunk's flags; counts,
+// an exclusive scan, then every lane appends its bad points behind those of the lanes before it
+__global__ void __launch_bounds__(KC_SCAN) k_cc_collect(const uint8_t* flags, uint32_t n, uint32_t q, uint32_t base,
+                                                        CcState* st, g16_key_bad_point* lists, uint32_t cap) {
+  __shared__ uint32_t sh_bad[KC_SCAN];
+  __shared__ uint32_t sh_start;
+  const uint32_t t = threadIdx.x;
+  const uint32_t seg = (n + KC_SCAN - 1) / KC_SCAN;
+  const uint32_t lo = t * seg < n ? t * seg : n, hi = lo + seg < n ? lo + seg : n;
+  uint32_t bad = 0;
+#pragma unroll 1
+  for (uint32_t i = lo; i < hi; ++i) bad += (flags[i] & ~KC_INF) ? 1 : 0;
+  sh_bad[t] = bad;
+  __syncthreads();
+  if (t == 0) {
+    uint32_t run = 0;
+#pragma unroll 1
+    for (uint32_t k = 0; k < KC_SCAN; ++k) {
+      const uint32_t c = sh_bad[k];
+      sh_bad[k] = run;
+      run += c;
+    }
+    const uint32_t start = st->n_list[q];
+    sh_start = start;
+    st->n_bad[q] += run;
+    st->n_list[q] = (uint64_t)start + run < cap ? start + run : cap;
+  }
+  __syncthreads();
+  uint64_t at = (uint64_t)sh_start + sh_bad[t];
+  g16_key_bad_point* list = lists + (size_t)q * cap;
+#pragma unroll 1
+  for (uint32_t i = lo; i < hi && bad && at < cap; ++i) {
+    const uint8_t f = flags[i] & ~KC_INF;
+    if (!f) continue;
+    list[at].query = CC_QUERY_ID[q];
+    list[at].index = base + i;
+    list[at].reason = f;
+    ++at;
+  }
+}
+
+// lanes 0..5: ML(g2, delta1') ML(delta2', -g1) | ML(delta2, S_L) ML(delta2', -S_L') | the same for H;
+// lanes 0..2: product and final exponentiation of one pair each; then the report and the list.
+// Nothing is paired when a structural check failed.
+__global__ void __launch_bounds__(KC_BLOCK) k_cc_final(const VkDev* vk, const CcKey* key, CcState* st,
+                                                       const g16_key_bad_point* lists, uint32_t cap, uint32_t mismatch,
+                                                       g16_key_bad_point* out_list) {
+  __shared__ F12 sh[6];
+  __shared__ uint32_t sh_fail[3];
+  __shared__ uint32_t sh_any, sh_off[CC_N + 1];
+  const uint32_t t = threadIdx.x;
+  if (t == 0) {
+    uint64_t bad = 0;
+    uint32_t off = 0;
+    for (int q = 0; q < CC_N; ++q) {
+      bad += st->n_bad[q];
+      sh_off[q] = off;
+      const uint32_t room = cap - off;
+      off += st->n_list[q] < room ? st->n_list[q] : room;
+    }
+    sh_off[CC_N] = off;
+    sh_any = bad ? 1 : 0;
+  }
+  __syncthreads();
+  const bool pair = !sh_any;
+  G2Affine Q = G2Affine::infinity();
+  G1Affine P = G1Affine::infinity();
+  if (pair && t < 6) {
+    if (t == 0) {
+      Q = key->g2;
+      P = key->delta_g1_after;
+    } else if (t == 1) {
+      Q = key->delta_g2_after;
+      P = key->g1_neg;
+    } else {
+      const uint32_t q = (t - 2) >> 1, side = t & 1;
+      Q = side ? key->delta_g2_after : key->delta_g2_before;
+      P = st->sum[q][side].to_affine();
+      if (side) P = P.neg();
+    }
+  }
+  F12 f = f12_one();
+  miller_mul(&f, &Q, &P, vk);  // one call site: infinity on either side (every idle lane) returns at once
+  if (t < 6) sh[t] = f;
+  __syncthreads();
+  if (t < 3) {
+    bool one = true;
+    if (pair) {
+      F12 g;
+      f12_mul(&g, &sh[2 * t], &sh[2 * t + 1]);
+      one = final_exp_is_one(&g, vk);
+    }
+    sh_fail[t] = one ? 0 : (2u << t);  // G16_CONTRIB_PAIR_DELTA, _L, _H
+  }
+  __syncthreads();
+  if (t == 0) {
+    g16_contribution_report r;
+    memset(&r, 0, sizeof r);
+    r.relations_checked = pair ? 1 : 0;
+    r.relations_failed = mismatch ? G16_CONTRIB_UNCHANGED_MISMATCH : 0;
+    if (pair) {
+      r.relations_failed |= sh_fail[0] | sh_fail[1] | sh_fail[2];
+      if (key->delta_g1_after.is_inf() || key->delta_g2_after.is_inf()) r.relations_failed |= G16_CONTRIB_DELTA_INFINITE;
+    }
+    r.ok = (pair && !r.relations_failed) ? 1 : 0;
+    r.n_bad_l = st->n_bad[CC_L];
+    r.n_bad_h = st->n_bad[CC_H];
+    r.n_listed = sh_off[CC_N];
+    st->report = r;
+  }
+#pragma unroll 1
+  for (int q = 0; q < CC_N; ++q) {
+    const uint32_t cnt = sh_off[q + 1] - sh_off[q];
+#pragma unroll 1
+    for (uint32_t k = t; k < cnt; k += KC_BLOCK) out_list[sh_off[q] + k] = lists[(size_t)q * cap + k];
+  }
+}
+
+// ---- host side -------------------------------------------------------------------------------------
+uint32_t chunk_from_env(uint64_t longest) {
+  uint32_t chunk = CT_DEFAULT_CHUNK;
+  if (const char* e = getenv("G16_CONTRIB_CHUNK")) {  // tests: points per staged chunk
+    const unsigned long long v = strtoull(e, nullptr, 0);
+    if (v >= 1 && v <= (1ull << 24)) chunk = (uint32_t)v;
+  }
+  if (longest < 1) longest = 1;
+  return chunk > longest ? (uint32_t)longest : chunk;
+}
+
+bool key_shape_ok(const g16_key_desc* k) {
+  if (!k || k->n_vars < 1 || (uint64_t)k->n_public + 1 > k->n_vars) return false;
+  const uint64_t n_l = (uint64_t)k->n_vars - k->n_public - 1;
+  return !(n_l && !k->l_query) && !(k->domain_size && !k->h_query);
+}
+
+struct CtItem {
+  const uint8_t* src;
+  uint8_t* dst;
+  uint32_t count;
+};
+
+enum { CCK_PAIR = 0, CCK_G1 = 1, CCK_G2 = 2 };
+struct CcItem {
+  int kind;
+  uint32_t q, base, count;
+  const uint8_t* after;
+  const uint8_t* before;
+  const uint64_t* rho;  // NULL: drawn into the slot
+};
+
+}  // namespace
+}  // namespace g16
+
+using namespace g16;
+
+extern "C" g16_status g16_key_contribute(int device, const g16_key_desc* key, const uint64_t d[4], uint8_t* l_out,
+                                         uint8_t* h_out, uint8_t delta_g1_out[64], uint8_t delta_g2_out[128]) {
+  if (!key_shape_ok(key) || !delta_g1_out || !delta_g2_out) return G16_ERR_INVALID;
+  const uint64_t n_l = (uint64_t)key->n_vars - key->n_public - 1, dom = key->domain_size;
+  if ((n_l && !l_out) || (dom && !h_out)) return G16_ERR_INVALID;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return G16_ERR_NO_DEVICE;
+  if (device < 0 || device >= ndev) return G16_ERR_INVALID;
+
+  // every copy of d and of what is derived from it lives in this struct and is wiped on every way out
+  struct Secret {
+    Fr d, d_inv;
+    U256 dc, ec;
+    CtSched sched;
+    ~Secret() { wipe(this, sizeof *this); }
+  } sec;
+  if (d) {
+    memcpy(&sec.d, d, 32);
+    if (!fr_words_canonical(sec.d) || sec.d.is_zero()) return G16_ERR_INVALID;
+  } else {  // uniform in [1, r): 254 random bits, rejected outside the range (r > 2^253: < 2 draws on average)
+    for (;;) {
+      if (!os_random(&sec.dc, 32)) return G16_ERR_INTERNAL;
+      sec.dc.v[7] &= 0x3fffffffu;
+      Fr c;
+      memcpy(&c, &sec.dc, 32);
+      const bool in_range = fr_words_canonical(c) && !c.is_zero();
+      wipe(&c, sizeof c);
+      if (in_range) break;
+    }
+    sec.d = Fr::from_canonical(sec.dc);
+  }
+  sec.d_inv = sec.d.inv();
+  sec.dc = sec.d.to_canonical();
+  sec.ec = sec.d_inv.to_canonical();
+  sec.sched = naf_of(sec.ec);
+
+  try {
+    G1Affine d1;
+    G2Affine d2;
+    memcpy(&d1, key->delta_g1, 64);
+    memcpy(&d2, key->delta_g2, 128);
+    const G1Affine nd1 = G1XYZZ::from_affine(d1).mul(sec.dc).to_affine();
+    const G2Affine nd2 = G2XYZZ::from_affine(d2).mul(sec.dc).to_affine();
+
+    const uint32_t chunk = chunk_from_env(n_l > dom ? n_l : dom);
+    std::vector<CtItem> items;
+    for (uint64_t at = 0; at < n_l; at += chunk)
+      items.push_back(CtItem{key->l_query + at * 64, l_out + at * 64, (uint32_t)(n_l - at < chunk ? n_l - at : chunk)});
+    for (uint64_t at = 0; at < dom; at += chunk)
+      items.push_back(CtItem{key->h_query + at * 64, h_out + at * 64, (uint32_t)(dom - at < chunk ? dom - at : chunk)});
+
+    G16_HIP(hipSetDevice(device));
+    // every allocation of the call: nothing is allocated inside the chunk loop
+    const size_t slot_bytes = (size_t)chunk * 64;
+    PinnedBuf pin[2];
+    DevBuf<uint8_t> dslot[2];
+    DevBuf<G1XYZZ> dwork;
+    DevBuf<CtSched> dsched;
+    StreamBox copy, comp, down;
+    EventBox copied[2], computed[2], done[2];
+    for (int s = 0; s < 2; ++s) {
+      pin[s].alloc(slot_bytes);
+      dslot[s].alloc(slot_bytes);
+      copied[s].create();
+      computed[s].create();
+      done[s].create();
+    }
+    dwork.alloc(chunk);
+    dsched.alloc(1);
+    copy.create();
+    comp.create();
+    down.create();
+    G16_HIP(hipMemcpy(dsched.p, &sec.sched, sizeof(CtSched), hipMemcpyHostToDevice));
+
+    for (size_t k = 0; k < items.size() + 2; ++k) {
+      const int s = (int)(k & 1);
+      if (k >= 2) {  // the results of the chunk that used this slot two chunks ago
+        G16_HIP(hipEventSynchronize(done[s].e));
+        memcpy(items[k - 2].dst, pin[s].p, (size_t)items[k - 2].count * 64);
+      }
+      if (k >= items.size()) continue;
+      const CtItem& it = items[k];
+      const uint32_t n = it.count;
+      const size_t bytes = (size_t)n * 64;
+      uint8_t* dv = dslot[s].p;
+      memcpy(pin[s].p, it.src, bytes);
+      G16_HIP(hipMemcpyAsync(dv, pin[s].p, bytes, hipMemcpyHostToDevice, copy.s));
+      G16_HIP(hipEventRecord(copied[s].e, copy.s));
+      G16_HIP(hipStreamWaitEvent(comp.s, copied[s].e, 0));
+      G16_LAUNCH(k_ct_mul, ceil_div(n, KC_BLOCK), KC_BLOCK, 0, comp.s, (const G1Affine*)dv, n,
+                 (const CtSched*)dsched.p, dwork.p);
+      G16_LAUNCH(k_ct_affine, ceil_div(n, KC_BLOCK * CT_RUN), KC_BLOCK, 0, comp.s, (const G1XYZZ*)dwork.p, n,
+                 (G1Affine*)dv);
+      G16_HIP(hipEventRecord(computed[s].e, comp.s));
+      G16_HIP(hipStreamWaitEvent(down.s, computed[s].e, 0));
+      G16_HIP(hipMemcpyAsync(pin[s].p, dv, bytes, hipMemcpyDeviceToHost, down.s));
+      G16_HIP(hipEventRecord(done[s].e, down.s));
+    }
+    G16_HIP(hipMemsetAsync(dsched.p, 0, sizeof(CtSched), comp.s));  // the recoded d^-1 does not outlive the call
+    G16_HIP(hipGetLastError());
+    G16_HIP(hipStreamSynchronize(comp.s));
+    G16_HIP(hipStreamSynchronize(down.s));
+    memcpy(delta_g1_out, &nd1, 64);
+    memcpy(delta_g2_out, &nd2, 128);
+    return G16_OK;
+  } catch (const HipError&) {
+    return G16_ERR_HIP;
+  } catch (const std::exception&) {
+    return G16_ERR_INTERNAL;
+  }
+}
+
+extern "C" g16_status g16_key_contribution_check(int device, const g16_key_desc* before, const g16_key_desc* after,
+                                                 const uint64_t* rho, g16_key_bad_point* bad_out, uint32_t bad_cap,
+                                                 g16_contribution_report* report) {
+  if (!report || (bad_cap && !bad_out) || !key_shape_ok(before) || !key_shape_ok(after)) return G16_ERR_INVALID;
+  if (!before->a_query || !before->b_g1_query || !before->b_g2_query || !after->a_query || !after->b_g1_query ||
+      !after->b_g2_query)
+    return G16_ERR_INVALID;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return G16_ERR_NO_DEVICE;
+  if (device < 0 || device >= ndev) return G16_ERR_INVALID;
+  memset(report, 0, sizeof *report);
+  // 1. what a contribution must leave alone: compared as bytes on the host
+  if (before->n_vars != after->n_vars || before->n_public != after->n_public ||
+      before->domain_size != after->domain_size) {
+    report->relations_failed = G16_CONTRIB_UNCHANGED_MISMATCH;  // not the same key: nothing to pair entry by entry
+    return G16_OK;
+  }
+  const uint64_t N = before->n_vars, n_l = N - before->n_public - 1, dom = before->domain_size;
+  if (rho)
+    for (uint64_t i = 0; i < n_l + dom; ++i)
+      if (!(rho[2 * i] | rho[2 * i + 1])) return G16_ERR_INVALID;
+  const uint32_t mismatch =
+      (memcmp(before->alpha_g1, after->alpha_g1, 64) || memcmp(before->beta_g1, after->beta_g1, 64) ||
+       memcmp(before->beta_g2, after->beta_g2, 128) || memcmp(before->a_query, after->a_query, N * 64) ||
+       memcmp(before->b_g1_query, after->b_g1_query, N * 64) || memcmp(before->b_g2_query, after->b_g2_query, N * 128))
+          ? 1
+          : 0;
+  try {
+    const uint32_t chunk = chunk_from_env(n_l > dom ? n_l : dom);
+    const uint32_t nb_max = ceil_div(chunk, KC_BLOCK);
+    const uint32_t cap = bad_cap < KC_MAX_LISTED ? bad_cap : KC_MAX_LISTED;
+
+    std::vector<CcItem> items;
+    auto add_pairs = [&](uint32_t q, const uint8_t* a, const uint8_t* b, uint64_t count, const uint64_t* r) {
+      for (uint64_t at = 0; at < count; at += chunk)
+        items.push_back(CcItem{CCK_PAIR, q, (uint32_t)at, (uint32_t)(count - at < chunk ? count - at : chunk),
+                               a + at * 64, b + at * 64, r ? r + 2 * at : nullptr});
+    };
+    add_pairs(CC_L, after->l_query, before->l_query, n_l, rho);
+    add_pairs(CC_H, after->h_query, before->h_query, dom, rho ? rho + 2 * n_l : nullptr);
+    // the single points under the indices g16_key_check gives them
+    items.push_back(CcItem{CCK_G1, CC_SINGLES, 2, 1, after->delta_g1, nullptr, nullptr});
+    items.push_back(CcItem{CCK_G2, CC_SINGLES, 4, 1, after->delta_g2, nullptr, nullptr});
+
+    G16_HIP(hipSetDevice(device));
+    std::unique_ptr<VkDev> hv(new VkDev());
+    {
+      const HostConsts& H = host_consts();
+      memset(hv.get(), 0, sizeof(VkDev));
+      hv->frob_x = H.frob_x;
+      hv->frob_y = H.frob_y;
+      hv->b_twist = H.b_twist;
+      memcpy(hv->frob, H.frob, sizeof H.frob);
+    }
+    CcKey hk;
+    memcpy(&hk.delta_g1_after, after->delta_g1, 64);
+    memcpy(&hk.delta_g2_before, before->delta_g2, 128);
+    memcpy(&hk.delta_g2_after, after->delta_g2, 128);
+    hk.g1_neg = G1Affine{Fq::one(), Fq::from_u32(2)}.neg();
+    memcpy(&hk.g2, G2_GEN_WORDS, 128);
+    std::unique_ptr<CcState> hs(new CcState());
+    memset(hs.get(), 0, sizeof(CcState));
+
+    // every allocation of the call: nothing is allocated inside the chunk loop
+    size_t slot_bytes = (size_t)chunk * CC_SLOT_BYTES_PER_POINT;
+    if (slot_bytes < 128) slot_bytes = 128;  // delta_g2 alone
+    PinnedBuf pin[2];
+    DevBuf<uint8_t> dslot[2], dflags;
+    DevBuf<VkDev> dvk;
+    DevBuf<CcKey> dkey;
+    DevBuf<CcState> dst;
+    DevBuf<G1XYZZ> dpart;
+    DevBuf<g16_key_bad_point> dlists, dout;
+    StreamBox copy, comp;
+    EventBox copied[2], done[2];
+    for (int s = 0; s < 2; ++s) {
+      pin[s].alloc(slot_bytes);
+      dslot[s].alloc(slot_bytes);
+      copied[s].create();
+      done[s].create();
+    }
+    dflags.alloc(chunk);
+    dvk.alloc(1);
+    dkey.alloc(1);
+    dst.alloc(1);
+    dpart.alloc(2 * (size_t)nb_max);
+    dlists.alloc((size_t)CC_N * (cap ? cap : 1));
+    dout.alloc(cap ? cap : 1);
+    copy.create();
+    comp.create();
+    G16_HIP(hipMemcpy(dvk.p, hv.get(), sizeof(VkDev), hipMemcpyHostToDevice));
+    G16_HIP(hipMemcpy(dkey.p, &hk, sizeof hk, hipMemcpyHostToDevice));
+    G16_HIP(hipMemcpy(dst.p, hs.get(), sizeof(CcState), hipMemcpyHostToDevice));
+
+    const size_t off_before = (size_t)chunk * 64, off_rho = (size_t)chunk * 128;
+    for (size_t k = 0; k < items.size(); ++k) {
+      const CcItem& it = items[k];
+      const int s = (int)(k & 1);
+      if (k >= 2) G16_HIP(hipEventSynchronize(done[s].e));  // the kernels that read this slot two chunks ago
+      uint8_t* h = pin[s].p;
+      uint8_t* dv = dslot[s].p;
+      const uint32_t n = it.count;
+      const uint32_t nb = ceil_div(n, KC_BLOCK);
+      if (it.kind == CCK_PAIR) {
+        memcpy(h, it.after, (size_t)n * 64);
+        memcpy(h + off_before, it.before, (size_t)n * 64);
+        uint64_t* hr = (uint64_t*)(h + off_rho);
+        if (it.rho) {
+          memcpy(hr, it.rho, (size_t)n * 16);
+        } else {  // drawn chunk by chunk, straight into the staging slot
+          bool drawn = os_random(hr, (size_t)n * 16);
+          for (uint32_t i = 0; drawn && i < n; ++i)
+            while (drawn && !(hr[2 * (size_t)i] | hr[2 * (size_t)i + 1]))  // probability 2^-128 per entry
+              drawn = os_random(&hr[2 * (size_t)i], 16);
+          if (!drawn) {  // never a fixed fallback; the chunks in flight still read the slots
+            (void)hipStreamSynchronize(copy.s);
+            (void)hipStreamSynchronize(comp.s);
+            return G16_ERR_INTERNAL;
+          }
+        }
+        G16_HIP(hipMemcpyAsync(dv, h, (size_t)n * 64, hipMemcpyHostToDevice, copy.s));
+        G16_HIP(hipMemcpyAsync(dv + off_before, h + off_before, (size_t)n * 64, hipMemcpyHostToDevice, copy.s));
+        G16_HIP(hipMemcpyAsync(dv + off_rho, h + off_rho, (size_t)n * 16, hipMemcpyHostToDevice, copy.s));
+      } else {
+        const size_t bytes = (size_t)n * (it.kind == CCK_G2 ? 128 : 64);
+        memcpy(h, it.after, bytes);
+        G16_HIP(hipMemcpyAsync(dv, h, bytes, hipMemcpyHostToDevice, copy.s));
+      }
+      G16_HIP(hipEventRecord(copied[s].e, copy.s));
+      G16_HIP(hipStreamWaitEvent(comp.s, copied[s].e, 0));
+      if (it.kind == CCK_G2) {
+        G16_LAUNCH(k_cc_g2, nb, KC_BLOCK, 0, comp.s, (const VkDev*)dvk.p, (const G2Affine*)dv, n, dflags.p);
+      } else {
+        G16_LAUNCH(k_cc_g1, nb, KC_BLOCK, 0, comp.s, (const G1Affine*)dv, n, dflags.p);
+      }
+      if (it.kind == CCK_PAIR) {
+        G16_LAUNCH(k_cc_rho, dim3(nb, 2), KC_BLOCK, 0, comp.s, (const G1Affine*)(dv + off_before), (const G1Affine*)dv,
+                   (const uint64_t*)(dv + off_rho), (const uint8_t*)dflags.p, n, dpart.p);
+        G16_LAUNCH(k_cc_fold, 1, KC_BLOCK, 0, comp.s, (const G1XYZZ*)dpart.p, nb, it.q, dst.p);
+      }
+      G16_LAUNCH(k_cc_collect, 1, KC_SCAN, 0, comp.s, (const uint8_t*)dflags.p, n, it.q, it.base, dst.p, dlists.p, cap);
+      G16_HIP(hipEventRecord(done[s].e, comp.s));
+    }
+    G16_LAUNCH(k_cc_final, 1, KC_BLOCK, 0, comp.s, (const VkDev*)dvk.p, (const CcKey*)dkey.p, dst.p,
+               (const g16_key_bad_point*)dlists.p, cap, mismatch, dout.p);
+    G16_HIP(hipGetLastError());
+    G16_HIP(hipStreamSynchronize(comp.s));  // the one synchronisation before the download
+    G16_HIP(hipMemcpy(hs.get(), dst.p, sizeof(CcState), hipMemcpyDeviceToHost));
+    *report = hs->report;
+    if (report->n_listed)
+      G16_HIP(hipMemcpy(bad_out, dout.p, (size_t)report->n_listed * sizeof(g16_key_bad_point), hipMemcpyDeviceToHost));
+    return G16_OK;
+  } catch (const HipError&) {
+    return G16_ERR_HIP;
+  } catch (const std::exception&) {
+    return G16_ERR_INTERNAL;
+  }
+}

@@ -421,6 +421,76 @@ g16_status g16_key_check(int device, const g16_key_desc* key, const g16_vk_desc*
                          const uint64_t* rho /* n_vars x 2 u64, NULL = CSPRNG */,
                          g16_key_bad_point* bad_out, uint32_t bad_cap, g16_key_report* report);
 
+/* ---- phase-2 delta contributions (not on the proving path) --------------------------------------- */
+/* g16_setup_create mints a key from toxic waste its caller knows.  g16_key_contribute re-randomises delta,
+ * the point arithmetic of `snarkjs zkey contribute` / `zkey beacon`:
+ *   delta_g1' = d delta_g1, delta_g2' = d delta_g2, l_query'[i] = d^-1 l_query[i], h_query'[i] = d^-1 h_query[i]
+ * Everything else of the key is untouched and not read beyond the descriptor (A, B1, B2, alpha, beta, IC,
+ * gamma).  The key of (tau, alpha, beta, gamma, delta) becomes, byte for byte, the key g16_setup_create mints
+ * for (tau, alpha, beta, gamma, delta d).
+ * d: 4 u64 Montgomery Fr, 1 <= d < r (0 or a non-canonical value: G16_ERR_INVALID), or NULL: the library draws
+ *    d uniformly from [1, r) from the operating system's CSPRNG (rejection sampling; a failure to get
+ *    randomness is G16_ERR_INTERNAL, never a fixed fallback), never returns it and overwrites every copy of d
+ *    and of d^-1 (host and device) before it returns.
+ * l_out: (n_vars - n_public - 1) x 64 bytes, h_out: domain_size x 64 bytes: canonical affine Montgomery x|y as
+ *    in the key, infinity stays all-zero.  l_out / h_out may BE key->l_query / key->h_query (in place); any
+ *    other overlap is not supported.
+ * The key is expected to be well formed (g16_key_check): a point off the curve is multiplied like any other
+ * and means nothing afterwards.
+ * Standalone like g16_key_check: no ctx, a ctx alive on the device is left untouched.  The two queries are
+ * streamed through two page-locked host slots and two device slots of min(2^18, longest query) points (64
+ * bytes per point, plus one 128-byte work entry per point of ONE chunk): the copy of chunk k + 1 and the
+ * download of chunk k - 1 run under the kernels of chunk k; device use does not grow with the key.
+ * G16_CONTRIB_CHUNK=<points> overrides the chunk (tests).  No atomics: the bytes do not depend on scheduling.
+ *
+ * NOT built: the snarkjs section-10 transcript (Blake2b challenge, proof of knowledge of d, beacon mode) is
+ * neither written nor verified, so a contributed .zkey carries no contribution record `snarkjs zkey verify`
+ * would accept.                                                                                      */
+g16_status g16_key_contribute(int device, const g16_key_desc* key,
+                              const uint64_t d[4] /* Montgomery Fr, 1 <= d < r; NULL = CSPRNG */,
+                              uint8_t* l_out, uint8_t* h_out, uint8_t delta_g1_out[64], uint8_t delta_g2_out[128]);
+
+/* Is `after` the key `before` with only delta changed (the sameRatio checks of `snarkjs zkey verify`)?
+ * In this order:
+ *   1. bytes, on the host: n_vars, n_public, domain_size, alpha_g1, beta_g1, beta_g2, a_query, b_g1_query and
+ *      b_g2_query must be identical; a difference sets G16_CONTRIB_UNCHANGED_MISMATCH (reported whatever
+ *      else fails).  When the SIZES differ nothing can be compared entry by entry: the call returns G16_OK at
+ *      once with ok = 0, relations_checked = 0 and that bit alone.
+ *   2. structure of after's delta_g1, delta_g2, l_query, h_query: canonical, on the curve, delta_g2 in the
+ *      r-torsion -- the predicates, reason bits and first-failure rule of g16_key_check.  bad_out receives the
+ *      first min(bad_cap, 65536) bad points in ascending (query, index) order (G16_KEY_Q_L, G16_KEY_Q_H, then
+ *      G16_KEY_Q_SINGLES with index 2 = delta_g1, 4 = delta_g2), built by scans: the same list on every run.
+ *      The all-zero encoding is the point at infinity: valid.
+ *   3. relations, evaluated only when nothing structural failed (relations_checked = 0 otherwise):
+ *      G16_CONTRIB_DELTA_INFINITE  after's delta_g1 or delta_g2 is the point at infinity
+ *      G16_CONTRIB_PAIR_DELTA      e(delta_g1', g2) != e(g1, delta_g2')
+ *      G16_CONTRIB_PAIR_L          e(sum rho_i L_i, delta_g2) != e(sum rho_i L'_i, delta_g2')
+ *      G16_CONTRIB_PAIR_H          the same for the H query, with its own rho
+ *      With unpredictable rho a pair of keys whose L (H) queries differ by anything but the one factor that
+ *      takes delta_g2' to delta_g2 passes with probability at most 2^-127 (the small-exponent test of
+ *      g16_verify_aggregate and g16_key_check); whoever knows rho makes two entries cancel
+ *      (L'_j + rho_k D, L'_k - rho_j D for any D in G1), and the relation holds.
+ * `before` is expected to have passed g16_key_check: its points are not tested again.
+ * rho: (len L + len H) x 2 u64 -- L's coefficients, then H's (little-endian 128-bit integers, NOT Montgomery),
+ *      every one non-zero (a zero entry: G16_ERR_INVALID), or NULL: drawn from the operating system's CSPRNG (a
+ *      failure to get randomness is G16_ERR_INTERNAL, never a fixed fallback).
+ * NOT checked: the contribution transcript (see g16_key_contribute), and that either key belongs to a circuit.
+ * Standalone and streamed like g16_key_check (144 bytes per point and slot; G16_CONTRIB_CHUNK).  Returns
+ * G16_OK when the check RAN: the verdict is in *report.                                               */
+enum { G16_CONTRIB_UNCHANGED_MISMATCH = 1, G16_CONTRIB_PAIR_DELTA = 2, G16_CONTRIB_PAIR_L = 4,
+       G16_CONTRIB_PAIR_H = 8, G16_CONTRIB_DELTA_INFINITE = 16 };   /* report.relations_failed */
+typedef struct {
+  uint8_t  ok;                 /* 1 iff no bad point, no failed relation and nothing else changed */
+  uint8_t  relations_checked;  /* 0 when a structural failure made the pairing relations meaningless */
+  uint32_t relations_failed;   /* G16_CONTRIB_* */
+  uint64_t n_bad_l, n_bad_h;   /* bad points of after's l_query / h_query (all of them, listed or not) */
+  uint32_t n_listed;           /* entries written to bad_out */
+} g16_contribution_report;
+g16_status g16_key_contribution_check(int device, const g16_key_desc* before, const g16_key_desc* after,
+                                      const uint64_t* rho /* (len L + len H) x 2 u64, NULL = CSPRNG */,
+                                      g16_key_bad_point* bad_out, uint32_t bad_cap,
+                                      g16_contribution_report* report);
+
 /* ---- RCCL inside the library (north_star: "a final RCCL all-reduce of partial bucket sums over xGMI") ---- */
 /* A host that is not PyTorch (the Rust shim) creates one per-rank ctx per process (g16_options.rank / world,
  * dist_wm = 1) and ONE ncclComm_t over the same ranks with its own RCCL (ncclGetUniqueId / ncclCommInitRank),

@@ -41,6 +41,12 @@ pub const G16_KEY_PAIR_BETA: u32 = 1;
 pub const G16_KEY_PAIR_DELTA: u32 = 2;
 pub const G16_KEY_PAIR_B: u32 = 4;
 pub const G16_KEY_VK_MISMATCH: u32 = 8;
+// g16_key_contribution_check: report.relations_failed bits
+pub const G16_CONTRIB_UNCHANGED_MISMATCH: u32 = 1;
+pub const G16_CONTRIB_PAIR_DELTA: u32 = 2;
+pub const G16_CONTRIB_PAIR_L: u32 = 4;
+pub const G16_CONTRIB_PAIR_H: u32 = 8;
+pub const G16_CONTRIB_DELTA_INFINITE: u32 = 16;
 
 #[repr(C)]
 pub struct g16_ctx {
@@ -181,6 +187,17 @@ pub struct g16_key_report {
     pub n_listed: u32,
 }
 
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct g16_contribution_report {
+    pub ok: u8,
+    pub relations_checked: u8,
+    pub relations_failed: u32,
+    pub n_bad_l: u64,
+    pub n_bad_h: u64,
+    pub n_listed: u32,
+}
+
 extern "C" {
     // ---- include/g16_amd.h ---------------------------------------------------------------------
     pub fn g16_ctx_create(key: *const g16_key_desc, a: *const g16_csr, b: *const g16_csr, num_constraints: u32, opt: *const g16_options, out: *mut *mut g16_ctx) -> g16_status;
@@ -230,6 +247,8 @@ extern "C" {
     pub fn g16_verify_batch(device: c_int, vk: *const g16_vk_desc, proofs: *const u8, public_inputs: *const u64, n_proofs: u32, ok_out: *mut u8) -> g16_status;
     pub fn g16_verify_aggregate(device: c_int, vk: *const g16_vk_desc, proofs: *const u8, public_inputs: *const u64, n_proofs: u32, rho: *const u64, ok_out: *mut u8, structural_out: *mut u8) -> g16_status;
     pub fn g16_key_check(device: c_int, key: *const g16_key_desc, vk: *const g16_vk_desc, rho: *const u64, bad_out: *mut g16_key_bad_point, bad_cap: u32, report: *mut g16_key_report) -> g16_status;
+    pub fn g16_key_contribute(device: c_int, key: *const g16_key_desc, d: *const u64, l_out: *mut u8, h_out: *mut u8, delta_g1_out: *mut u8, delta_g2_out: *mut u8) -> g16_status;
+    pub fn g16_key_contribution_check(device: c_int, before: *const g16_key_desc, after: *const g16_key_desc, rho: *const u64, bad_out: *mut g16_key_bad_point, bad_cap: u32, report: *mut g16_contribution_report) -> g16_status;
     pub fn g16_dist_attach_rccl(ctx: *mut g16_ctx, nccl_comm: *mut c_void) -> g16_status;
     pub fn g16_dist_rccl_ranks(ctx: *const g16_ctx) -> c_int;
     pub fn g16_prove_dist(ctx: *mut g16_ctx, r: *const u64, s: *const u64, w_dev: *const c_void, n_vars: usize, proof_out: *mut u8) -> g16_status;

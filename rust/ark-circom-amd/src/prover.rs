@@ -251,6 +251,132 @@ impl GpuProver {
         Ok((report, bad))
     }
 
+    /// the descriptor of `pk` over packed copies of its queries (which the caller keeps alive)
+    fn key_desc_of(
+        pk: &ProvingKey<Bn254>,
+        packed: &(Vec<u8>, Vec<u8>, Vec<u8>, Vec<u8>, Vec<u8>),
+    ) -> Result<ffi::g16_key_desc, GpuError> {
+        let n_vars = pk.a_query.len();
+        if pk.b_g1_query.len() != n_vars || pk.b_g2_query.len() != n_vars || pk.vk.gamma_abc_g1.is_empty() {
+            return Err(GpuError::Library(ffi::G16_ERR_INVALID, "query lengths differ".into()));
+        }
+        let n_public = pk.vk.gamma_abc_g1.len() - 1;
+        if pk.l_query.len() + n_public + 1 != n_vars {
+            return Err(GpuError::Library(ffi::G16_ERR_INVALID, "l_query length is not n_vars - n_public - 1".into()));
+        }
+        let mut key = ffi::g16_key_desc {
+            n_vars: n_vars as u32,
+            n_public: n_public as u32,
+            domain_size: pk.h_query.len() as u32, // the points that are there
+            a_query: packed.0.as_ptr(),
+            b_g1_query: packed.1.as_ptr(),
+            b_g2_query: packed.2.as_ptr(),
+            l_query: packed.3.as_ptr(),
+            h_query: packed.4.as_ptr(),
+            alpha_g1: [0; 64],
+            beta_g1: [0; 64],
+            delta_g1: [0; 64],
+            beta_g2: [0; 128],
+            delta_g2: [0; 128],
+        };
+        pack::pack_g1(&pk.vk.alpha_g1, &mut key.alpha_g1);
+        pack::pack_g1(&pk.beta_g1, &mut key.beta_g1);
+        pack::pack_g1(&pk.delta_g1, &mut key.delta_g1);
+        pack::pack_g2(&pk.vk.beta_g2, &mut key.beta_g2);
+        pack::pack_g2(&pk.vk.delta_g2, &mut key.delta_g2);
+        Ok(key)
+    }
+
+    fn packed_queries(pk: &ProvingKey<Bn254>) -> (Vec<u8>, Vec<u8>, Vec<u8>, Vec<u8>, Vec<u8>) {
+        (
+            pack::pack_g1_vec(&pk.a_query),
+            pack::pack_g1_vec(&pk.b_g1_query),
+            pack::pack_g2_vec(&pk.b_g2_query),
+            pack::pack_g1_vec(&pk.l_query),
+            pack::pack_g1_vec(&pk.h_query),
+        )
+    }
+
+    /// One phase-2 contribution on the GPU (`g16_key_contribute`, include/g16_amd.h) -- no prover is needed.
+    /// `delta_g1` and `vk.delta_g2` times `d`, every point of `l_query` and `h_query` times `d^-1`: the key of
+    /// `(tau, alpha, beta, gamma, delta)` becomes the key of `(tau, alpha, beta, gamma, delta * d)`.  `d`:
+    /// `Some(d)`, non-zero, or `None`: drawn by the library from the operating system's CSPRNG and never
+    /// returned.  The snarkjs contribution transcript (challenge hash, proof of knowledge of `d`) is NOT
+    /// produced.
+    pub fn contribute(pk: &ProvingKey<Bn254>, d: Option<Fr>, device: i32) -> Result<ProvingKey<Bn254>, GpuError> {
+        let packed = Self::packed_queries(pk);
+        let key = Self::key_desc_of(pk, &packed)?;
+        let words = d.map(|d| pack::fr_words(&d));
+        let mut l_out = vec![0u8; pk.l_query.len() * 64];
+        let mut h_out = vec![0u8; pk.h_query.len() * 64];
+        let (mut d1, mut d2) = ([0u8; 64], [0u8; 128]);
+        let st = unsafe {
+            ffi::g16_key_contribute(
+                device as c_int,
+                &key,
+                words.as_ref().map_or(std::ptr::null(), |w| w.as_ptr()),
+                l_out.as_mut_ptr(),
+                h_out.as_mut_ptr(),
+                d1.as_mut_ptr(),
+                d2.as_mut_ptr(),
+            )
+        };
+        if st != ffi::G16_OK {
+            return Err(GpuError::Library(st, "g16_key_contribute failed".into()));
+        }
+        let mut out = pk.clone();
+        out.delta_g1 = pack::unpack_g1(&d1);
+        out.vk.delta_g2 = pack::unpack_g2(&d2);
+        out.l_query = l_out.chunks_exact(64).map(pack::unpack_g1).collect();
+        out.h_query = h_out.chunks_exact(64).map(pack::unpack_g1).collect();
+        Ok(out)
+    }
+
+    /// Is `after` the key `before` with only delta re-randomised (`g16_key_contribution_check`)?  Bytes of
+    /// what a contribution leaves alone (here also `vk.gamma_g2` and `vk.gamma_abc_g1`, which the C key
+    /// descriptor does not carry), structure of `after`'s delta, `l_query` and `h_query`, then
+    /// `e(delta_g1', g2) = e(g1, delta_g2')` and `e(sum rho_i L_i, delta_g2) = e(sum rho_i L'_i, delta_g2')`
+    /// for L and for H.  `rho`: `None` (drawn by the library) or one non-zero 128-bit coefficient per point
+    /// of `l_query`, then of `h_query`.  The contribution transcript is NOT checked.
+    pub fn check_contribution(
+        before: &ProvingKey<Bn254>,
+        after: &ProvingKey<Bn254>,
+        rho: Option<&[u128]>,
+        device: i32,
+        max_listed: usize,
+    ) -> Result<(ffi::g16_contribution_report, Vec<ffi::g16_key_bad_point>), GpuError> {
+        let (pb, pa) = (Self::packed_queries(before), Self::packed_queries(after));
+        let (kb, ka) = (Self::key_desc_of(before, &pb)?, Self::key_desc_of(after, &pa)?);
+        if let Some(r) = rho {
+            if r.len() != before.l_query.len() + before.h_query.len() {
+                return Err(GpuError::Library(ffi::G16_ERR_INVALID, "one coefficient per point of l_query and h_query".into()));
+            }
+        }
+        let words: Option<Vec<u64>> = rho.map(|r| r.iter().flat_map(|x| [*x as u64, (*x >> 64) as u64]).collect());
+        let mut bad = vec![ffi::g16_key_bad_point::default(); max_listed];
+        let mut report = ffi::g16_contribution_report::default();
+        let st = unsafe {
+            ffi::g16_key_contribution_check(
+                device as c_int,
+                &kb,
+                &ka,
+                words.as_ref().map_or(std::ptr::null(), |w| w.as_ptr()),
+                if max_listed == 0 { std::ptr::null_mut() } else { bad.as_mut_ptr() },
+                max_listed as u32,
+                &mut report,
+            )
+        };
+        if st != ffi::G16_OK {
+            return Err(GpuError::Library(st, "g16_key_contribution_check failed".into()));
+        }
+        if before.vk.gamma_g2 != after.vk.gamma_g2 || before.vk.gamma_abc_g1 != after.vk.gamma_abc_g1 {
+            report.relations_failed |= ffi::G16_CONTRIB_UNCHANGED_MISMATCH;
+            report.ok = 0;
+        }
+        bad.truncate(report.n_listed as usize);
+        Ok((report, bad))
+    }
+
     /// packs the key and the matrices once and hands them to `make` (g16_ctx_create / _multi)
     fn create_with(
         pk: &ProvingKey<Bn254>,
