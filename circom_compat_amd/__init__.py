@@ -38,7 +38,8 @@ __all__ = ["read_zkey", "R1CSFile", "R1CS", "CircomCircuit", "CircomBuilder", "C
            "SynthesisError", "SerializationError", "fr_from_ints", "fr_to_ints", "read_wtns",
            "trapdoor_setup", "Csr", "write_zkey", "device_tensor", "verify_batch", "verify_aggregate",
            "verify_batch_fast", "check_key", "KeyReport", "contribute_key", "check_contribution",
-           "ContributionReport"]
+           "ContributionReport", "Srs", "trapdoor_srs", "setup_from_srs", "check_key_circuit",
+           "CircuitBindingReport"]
 
 FR_MODULUS = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 
@@ -734,27 +735,18 @@ REDUCTIONS = {"circom": 0, "libsnark": 1}
 SHARD_MODES = {"auto": B.SHARD_AUTO, "points": B.SHARD_POINTS, "buckets": B.SHARD_BUCKETS}
 
 
-def trapdoor_setup(a: Csr, b: Csr, c: Csr, n_vars: int, n_public: int, toxic: Sequence[int],
-                   device=0, lib: Optional[B.Library] = None, reduction: str = "circom") -> ProvingKey:
-    """Known-toxic-waste setup on the GPU (g16_setup_create_ex): the key
-    Groth16::generate_random_parameters_with_reduction::<QAP> would produce for
-    (tau, alpha, beta, gamma, delta) = toxic, QAP = CircomReduction ("circom", snarkjs-compatible)
-    or LibsnarkReduction ("libsnark", arkworks' default: reference tests/groth16.rs:25).
-    Used to mint the synthetic BASELINE keys."""
-    lib = lib or B.load()
+def _setup_matrices(a: Csr, b: Csr, c: Csr, n_vars: int, n_public: int, lib):
+    """the transposed matrices g16_setup_create_ex / g16_setup_from_srs take: rows = wires, `at` with the
+    n_public + 1 rows snarkjs appends"""
     m = a.num_rows
     ni = n_public + 1
     one = fr_from_ints([1], lib)
     at = _transpose_csr(a, n_vars, (np.arange(m, m + ni), np.arange(ni), np.tile(one, (ni, 1))))
-    bt = _transpose_csr(b, n_vars)
-    ct = _transpose_csr(c, n_vars)
-    tox = fr_from_ints(list(toxic), lib)
-    h = C.c_void_p()
-    cat, cbt, cct = at.to_c(), bt.to_c(), ct.to_c()
-    st = lib.g16_setup_create_ex(device, C.byref(cat), C.byref(cbt), C.byref(cct), n_vars, n_public, m,
-                                 _np_ptr(tox), REDUCTIONS[reduction], C.byref(h))
-    if st != B.G16_OK:
-        raise (SynthesisError if st == B.G16_ERR_DOMAIN_TOO_LARGE else G16Error)(st, "g16_setup_create failed")
+    return at, _transpose_csr(b, n_vars), _transpose_csr(c, n_vars)
+
+
+def _setup_key(lib, h, n_vars: int, n_public: int) -> ProvingKey:
+    """ProvingKey over the host arrays a g16_setup handle owns"""
     handle = _Handle(lib, h, lib.g16_setup_destroy)
     kd = B.KeyDesc()
     icp = C.c_void_p()
@@ -773,6 +765,142 @@ def trapdoor_setup(a: Csr, b: Csr, c: Csr, n_vars: int, n_public: int, toxic: Se
                       view(kd.a_query, n_vars, 64), view(kd.b_g1_query, n_vars, 64),
                       view(kd.b_g2_query, n_vars, 128), view(kd.l_query, n_vars - n_public - 1, 64),
                       view(kd.h_query, kd.domain_size, 64), keepalive=handle)
+
+
+def trapdoor_setup(a: Csr, b: Csr, c: Csr, n_vars: int, n_public: int, toxic: Sequence[int],
+                   device=0, lib: Optional[B.Library] = None, reduction: str = "circom") -> ProvingKey:
+    """Known-toxic-waste setup on the GPU (g16_setup_create_ex): the key
+    Groth16::generate_random_parameters_with_reduction::<QAP> would produce for
+    (tau, alpha, beta, gamma, delta) = toxic, QAP = CircomReduction ("circom", snarkjs-compatible)
+    or LibsnarkReduction ("libsnark", arkworks' default: reference tests/groth16.rs:25).
+    Used to mint the synthetic BASELINE keys."""
+    lib = lib or B.load()
+    at, bt, ct = _setup_matrices(a, b, c, n_vars, n_public, lib)
+    tox = fr_from_ints(list(toxic), lib)
+    h = C.c_void_p()
+    cat, cbt, cct = at.to_c(), bt.to_c(), ct.to_c()
+    st = lib.g16_setup_create_ex(device, C.byref(cat), C.byref(cbt), C.byref(cct), n_vars, n_public, a.num_rows,
+                                 _np_ptr(tox), REDUCTIONS[reduction], C.byref(h))
+    if st != B.G16_OK:
+        raise (SynthesisError if st == B.G16_ERR_DOMAIN_TOO_LARGE else G16Error)(st, "g16_setup_create failed")
+    return _setup_key(lib, h, n_vars, n_public)
+
+
+class Srs:
+    """A powers-of-tau string as g16_setup_from_srs reads it (sections 2-6 of a snarkjs .ptau): packed affine
+    points in the zkey encoding, one per row.  tau_g1: (>= 2 domain - 1, 64) uint8, tau^i G1; tau_g2:
+    (>= domain, 128), tau^i G2; alpha_tau_g1 / beta_tau_g1: (>= domain, 64), alpha tau^i G1 / beta tau^i G1;
+    beta_g2: 128 bytes.  Arrays a caller supplies are taken as they are: nothing here checks that they are a
+    consistent powers-of-tau string."""
+
+    def __init__(self, tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, beta_g2, keepalive=None):
+        self.tau_g1 = np.ascontiguousarray(tau_g1, dtype=np.uint8).reshape(-1, 64)
+        self.tau_g2 = np.ascontiguousarray(tau_g2, dtype=np.uint8).reshape(-1, 128)
+        self.alpha_tau_g1 = np.ascontiguousarray(alpha_tau_g1, dtype=np.uint8).reshape(-1, 64)
+        self.beta_tau_g1 = np.ascontiguousarray(beta_tau_g1, dtype=np.uint8).reshape(-1, 64)
+        self.beta_g2 = bytes(beta_g2)
+        if len(self.beta_g2) != 128:
+            raise G16Error(B.G16_ERR_INVALID, "beta_g2 is one packed G2 point: 128 bytes")
+        self._keepalive = keepalive
+
+    def to_c(self) -> B.SrsDesc:
+        d = B.SrsDesc()
+        d.n_tau_g1 = self.tau_g1.shape[0]
+        d.n_tau = min(self.tau_g2.shape[0], self.alpha_tau_g1.shape[0], self.beta_tau_g1.shape[0])
+        d.tau_g1, d.tau_g2 = self.tau_g1.ctypes.data, self.tau_g2.ctypes.data
+        d.alpha_tau_g1, d.beta_tau_g1 = self.alpha_tau_g1.ctypes.data, self.beta_tau_g1.ctypes.data
+        C.memmove(d.beta_g2, self.beta_g2, 128)
+        return d
+
+
+def trapdoor_srs(log2_domain: int, toxic: Sequence[int], device=0, lib: Optional[B.Library] = None) -> Srs:
+    """An SRS for domains up to 2^log2_domain from a trapdoor the caller knows, toxic = (tau, alpha, beta), on
+    the GPU (g16_srs_create) -- for tests and synthetic keys; a real ceremony's string comes from its .ptau."""
+    lib = lib or B.load()
+    if len(toxic) != 3:
+        raise G16Error(B.G16_ERR_INVALID, "toxic = (tau, alpha, beta)")
+    tox = fr_from_ints(list(toxic), lib)
+    h = C.c_void_p()
+    st = lib.g16_srs_create(device, int(log2_domain), _np_ptr(tox), C.byref(h))
+    if st != B.G16_OK:
+        raise (SynthesisError if st == B.G16_ERR_DOMAIN_TOO_LARGE else G16Error)(st, "g16_srs_create failed")
+    handle = _Handle(lib, h, lib.g16_srs_destroy)
+    d = B.SrsDesc()
+    lib.check(lib.g16_srs_desc_of(h, C.byref(d)))
+
+    def view(ptr, count, width):
+        return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(count * width,)).reshape(count, width)
+
+    return Srs(view(d.tau_g1, d.n_tau_g1, 64), view(d.tau_g2, d.n_tau, 128), view(d.alpha_tau_g1, d.n_tau, 64),
+               view(d.beta_tau_g1, d.n_tau, 64), bytes(d.beta_g2), keepalive=handle)
+
+
+def setup_from_srs(a: Csr, b: Csr, c: Csr, n_vars: int, n_public: int, srs: Srs, device=0,
+                   lib: Optional[B.Library] = None, reduction: str = "circom") -> ProvingKey:
+    """The initial key (gamma = delta = 1) of a circuit from a powers-of-tau string, on the GPU
+    (g16_setup_from_srs): what `snarkjs zkey new` computes of the points, nobody knowing tau, alpha or beta.
+    Matrix arguments and reduction as trapdoor_setup takes them; byte for byte the key trapdoor_setup mints
+    for (tau, alpha, beta, 1, 1).  contribute_key then re-randomises delta.  The SRS is NOT verified."""
+    lib = lib or B.load()
+    at, bt, ct = _setup_matrices(a, b, c, n_vars, n_public, lib)
+    h = C.c_void_p()
+    cat, cbt, cct = at.to_c(), bt.to_c(), ct.to_c()
+    d = srs.to_c()
+    st = lib.g16_setup_from_srs(device, C.byref(cat), C.byref(cbt), C.byref(cct), n_vars, n_public, a.num_rows,
+                                C.byref(d), REDUCTIONS[reduction], C.byref(h))
+    if st != B.G16_OK:
+        raise (SynthesisError if st == B.G16_ERR_DOMAIN_TOO_LARGE else G16Error)(st, "g16_setup_from_srs failed")
+    return _setup_key(lib, h, n_vars, n_public)
+
+
+SETUP_SRS_PHASES = ("upload", "ntt_g1", "ntt_g2", "ntt_h", "affine", "combine", "download")
+
+
+def setup_from_srs_times(lib: Optional[B.Library] = None) -> dict:
+    """milliseconds per phase of this thread's last setup_from_srs (g16_setup_from_srs_times)"""
+    lib = lib or B.load()
+    ms = (C.c_float * len(SETUP_SRS_PHASES))()
+    lib.check(lib.g16_setup_from_srs_times(ms, len(SETUP_SRS_PHASES)))
+    return dict(zip(SETUP_SRS_PHASES, (float(x) for x in ms)))
+
+
+class CircuitBindingReport:
+    """check_key_circuit's verdict.  failed: None, or the first part that did not hold -- "shape" (sizes),
+    "gamma_abc_g1" (IC), "gamma_g2", "contribution" (see .contribution, the ContributionReport of the fresh
+    key against the key under test; None when an earlier part failed)."""
+
+    def __init__(self, failed, contribution=None):
+        self.failed, self.contribution = failed, contribution
+        self.ok = failed is None
+
+    def describe(self) -> str:
+        if self.ok:
+            return "ok"
+        if self.failed == "contribution":
+            return "not a delta contribution to the circuit's initial key: " + self.contribution.describe()
+        return f"{self.failed} differs from the circuit's initial key"
+
+    def __repr__(self):
+        return f"CircuitBindingReport({self.describe()})"
+
+
+def check_key_circuit(pk: "ProvingKey", a: Csr, b: Csr, c: Csr, srs: Srs, rho=None, device=0, max_listed=64,
+                      lib: Optional[B.Library] = None, reduction: str = "circom") -> CircuitBindingReport:
+    """Is pk a key of THIS circuit under THIS ceremony -- the binding check_key cannot give.  Recomputes the
+    initial key from the SRS and the matrices (setup_from_srs), then requires, in this order, vk.gamma_abc_g1
+    and vk.gamma_g2 equal to the fresh key's, and check_contribution(fresh, pk).ok: a_query, b_g1_query,
+    b_g2_query, alpha and beta byte for byte, l_query, h_query and delta by pairings.  pk should have passed
+    check_key; rho, max_listed as check_contribution takes them."""
+    lib = lib or B.load()
+    fresh = setup_from_srs(a, b, c, pk.n_vars, pk.n_public, srs, device=device, lib=lib, reduction=reduction)
+    if fresh.domain_size != pk.domain_size:
+        return CircuitBindingReport("shape")
+    if not np.array_equal(np.asarray(fresh.vk.gamma_abc_g1), np.asarray(pk.vk.gamma_abc_g1)):
+        return CircuitBindingReport("gamma_abc_g1")
+    if bytes(fresh.vk.gamma_g2) != bytes(pk.vk.gamma_g2):
+        return CircuitBindingReport("gamma_g2")
+    rep = check_contribution(fresh, pk, rho=rho, device=device, max_listed=max_listed, lib=lib)
+    return CircuitBindingReport(None if rep.ok else "contribution", rep)
 
 
 def _verify_args(vk, proofs, public_inputs, lib):
@@ -847,7 +975,7 @@ def check_key(pk: "ProvingKey", vk=None, rho=None, device=0, max_listed=64,
     its curve and (G2) in the prime-order subgroup; then e(beta_g1, g2) = e(g1, beta_g2), the same for
     delta, and e(sum rho_i B1_i, g2) = e(g1, sum rho_i B2_i).  Call it once after read_zkey on a key you
     did not mint.  A passing report means the key is well formed and internally consistent, NOT that it
-    belongs to your circuit (that needs the ceremony's powers of tau).
+    belongs to your circuit: check_key_circuit ties it to the matrices through the ceremony's powers of tau.
     vk: None = pk.vk, False = skip the verifying-key part (IC, gamma_g2, the byte comparison).
     rho: None (drawn by the library from the OS CSPRNG) or n_vars ints in [1, 2^128)."""
     lib = lib or B.load()

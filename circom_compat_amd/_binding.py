@@ -94,6 +94,11 @@ class ContributionReportC(C.Structure):
                 ("n_bad_l", C.c_uint64), ("n_bad_h", C.c_uint64), ("n_listed", C.c_uint32)]
 
 
+class SrsDesc(C.Structure):
+    _fields_ = [("n_tau_g1", C.c_uint32), ("n_tau", C.c_uint32), ("tau_g1", C.c_void_p), ("tau_g2", C.c_void_p),
+                ("alpha_tau_g1", C.c_void_p), ("beta_tau_g1", C.c_void_p), ("beta_g2", C.c_uint8 * 128)]
+
+
 class ZkeyHeader(C.Structure):
     _fields_ = [("n8q", C.c_uint32), ("n8r", C.c_uint32), ("q", C.c_uint8 * 32),
                 ("r", C.c_uint8 * 32), ("n_vars", C.c_uint32), ("n_public", C.c_uint32),
@@ -133,6 +138,7 @@ ABI_SYMBOLS = [
     "g16_fr_from_canonical", "g16_fr_to_canonical",
     "g16_prove_batch", "g16_prove_batch_dev", "g16_witness_map_batch",
     "g16_key_check", "g16_key_contribute", "g16_key_contribution_check",
+    "g16_srs_create", "g16_srs_desc_of", "g16_srs_destroy", "g16_setup_from_srs", "g16_setup_from_srs_times",
 ]
 
 
@@ -238,6 +244,13 @@ class Library:
                                            C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_int, C.POINTER(vp)]),
             "g16_setup_destroy": (None, [vp]),
             "g16_setup_key": (C.c_int, [vp, C.POINTER(KeyDesc), C.POINTER(vp), _u32p, vp]),
+            "g16_srs_create": (C.c_int, [C.c_int, C.c_uint32, vp, C.POINTER(vp)]),
+            "g16_srs_desc_of": (C.c_int, [vp, C.POINTER(SrsDesc)]),
+            "g16_srs_destroy": (None, [vp]),
+            "g16_setup_from_srs": (C.c_int, [C.c_int, C.POINTER(Csr), C.POINTER(Csr), C.POINTER(Csr),
+                                             C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SrsDesc), C.c_int,
+                                             C.POINTER(vp)]),
+            "g16_setup_from_srs_times": (C.c_int, [C.POINTER(C.c_float), C.c_uint32]),
         }
         # measurement builds only (make EXTRA=-DG16_DEBUG_ABI; include/g16_amd.h): not an ABI symbol, never "missing"
         optional = {"g16_debug_alu_bench": (C.c_int, [C.c_int, C.c_int, C.c_uint32, C.c_uint32,

@@ -16,6 +16,7 @@
 #include "msm.h"
 #include "ntt.h"
 #include "witness_map.h"
+#include "keygen.h"
 
 using namespace g16;
 
@@ -125,12 +126,49 @@ void download(std::vector<uint8_t>& dst, const T* dev, size_t count) {
 
 }  // namespace
 
-struct g16_setup {
-  uint32_t n_vars = 0, n_public = 0, domain = 0;
-  std::vector<uint8_t> a, b1, b2, l, h, ic;
-  uint8_t alpha1[64], beta1[64], delta1[64], beta2[128], gamma2[128], delta2[128];
-  std::string err;
-};
+// ---- the pieces setup_srs.hip shares (keygen.h) --------------------------------------------------
+namespace g16 {
+
+G1Affine g1_generator() { return G1Affine{Fq::one(), Fq::one() + Fq::one()}; }
+
+G2Affine g2_generator() {  // reference src/zkey.rs:443-463
+  static const uint32_t X0[8] = {0xd992f6edu, 0x46debd5cu, 0xf75edaddu, 0x674322d4u, 0x5e5c4479u, 0x426a0066u, 0x121f1e76u, 0x1800deefu};
+  static const uint32_t X1[8] = {0xaef312c2u, 0x97e485b7u, 0x35a9e712u, 0xf1aa4933u, 0x31fb5d25u, 0x7260bfb7u, 0x920d483au, 0x198e9393u};
+  static const uint32_t Y0[8] = {0x66fa7daau, 0x4ce6cc01u, 0x0c43d37bu, 0xe3d1e769u, 0x8dcb408fu, 0x4aab7180u, 0xdb8c6debu, 0x12c85ea5u};
+  static const uint32_t Y1[8] = {0xd122975bu, 0x55acdadcu, 0x70b38ef3u, 0xbc4b3133u, 0x690c3395u, 0xec9e99adu, 0x585ff075u, 0x090689d0u};
+  auto fqc = [](const uint32_t* l) {
+    U256 u;
+    memcpy(u.v, l, 32);
+    return Fq::from_canonical(u);
+  };
+  return G2Affine{Fq2{fqc(X0), fqc(X1)}, Fq2{fqc(Y0), fqc(Y1)}};
+}
+
+void fr_powers(const Fr& base, const Fr& scale, Fr* out, uint32_t count, uint32_t total, hipStream_t s) {
+  if (!total) return;
+  PowTable T;
+  Fr x = base;
+  for (int j = 0; j < 28; ++j) {
+    T.p[j] = x;
+    x = x.sqr();
+  }
+  G16_LAUNCH(k_powers, ceil_div(total, 256), 256, 0, s, T, scale, out, count, total);
+}
+
+void FixedBase::build(hipStream_t s) {
+  tab1.alloc(FB_NWIN * FB_ROW);
+  tab2.alloc(FB_NWIN * FB_ROW);
+  G16_LAUNCH((k_fb_table<Fq>), 1, 64, 0, s, g1_generator(), tab1.p);
+  G16_LAUNCH((k_fb_table<Fq2>), 1, 64, 0, s, g2_generator(), tab2.p);
+}
+void FixedBase::mul_g1(const Fr* scalars, uint32_t n, G1Affine* out, hipStream_t s) const {
+  if (n) G16_LAUNCH((k_fb_mul<Fq>), ceil_div(n, 128), 128, 0, s, (const G1Affine*)tab1.p, scalars, n, out);
+}
+void FixedBase::mul_g2(const Fr* scalars, uint32_t n, G2Affine* out, hipStream_t s) const {
+  if (n) G16_LAUNCH((k_fb_mul<Fq2>), ceil_div(n, 128), 128, 0, s, (const G2Affine*)tab2.p, scalars, n, out);
+}
+
+}  // namespace g16
 
 namespace {
 thread_local std::string t_setup_err;
@@ -240,23 +278,10 @@ g16_status g16_setup_create_ex(int device, const g16_csr* at, const g16_csr* bt,
     }
 
     // ---- fixed-base tables
-    G1Affine g1{Fq::one(), Fq::one() + Fq::one()};
-    static const uint32_t X0[8] = {0xd992f6edu, 0x46debd5cu, 0xf75edaddu, 0x674322d4u, 0x5e5c4479u, 0x426a0066u, 0x121f1e76u, 0x1800deefu};
-    static const uint32_t X1[8] = {0xaef312c2u, 0x97e485b7u, 0x35a9e712u, 0xf1aa4933u, 0x31fb5d25u, 0x7260bfb7u, 0x920d483au, 0x198e9393u};
-    static const uint32_t Y0[8] = {0x66fa7daau, 0x4ce6cc01u, 0x0c43d37bu, 0xe3d1e769u, 0x8dcb408fu, 0x4aab7180u, 0xdb8c6debu, 0x12c85ea5u};
-    static const uint32_t Y1[8] = {0xd122975bu, 0x55acdadcu, 0x70b38ef3u, 0xbc4b3133u, 0x690c3395u, 0xec9e99adu, 0x585ff075u, 0x090689d0u};
-    auto fqc = [](const uint32_t* l) {
-      U256 u;
-      memcpy(u.v, l, 32);
-      return Fq::from_canonical(u);
-    };
-    G2Affine g2{Fq2{fqc(X0), fqc(X1)}, Fq2{fqc(Y0), fqc(Y1)}};  // reference src/zkey.rs:443-463
-    DevBuf<G1Affine> tab1;
-    DevBuf<G2Affine> tab2;
-    tab1.alloc(FB_NWIN * FB_ROW);
-    tab2.alloc(FB_NWIN * FB_ROW);
-    G16_LAUNCH((k_fb_table<Fq>), 1, 64, 0, s, g1, tab1.p);
-    G16_LAUNCH((k_fb_table<Fq2>), 1, 64, 0, s, g2, tab2.p);
+    FixedBase fb;
+    fb.build(s);
+    DevBuf<G1Affine>& tab1 = fb.tab1;
+    DevBuf<G2Affine>& tab2 = fb.tab2;
 
     // ---- batched fixed-base multiplications
     const size_t maxn = N > n ? N : n;

@@ -394,10 +394,12 @@ g16_status g16_verify_aggregate(int device, const g16_vk_desc* vk, const uint8_t
  *      G16_ERR_INVALID), or NULL: drawn from the operating system's CSPRNG as g16_verify_aggregate does (a
  *      failure to get randomness is G16_ERR_INTERNAL, never a fixed fallback).
  *
- * NOT checked: that the key belongs to a circuit.  The A / L / H queries and IC cannot be tied to the R1CS
- * without the ceremony's powers of tau, and the matrices are not looked at.  report->ok = 1 means the key
- * is well formed and internally consistent -- proofs made with it are then at least proofs under the key's
- * own verifying key -- not that it is the key of your circuit.
+ * NOT checked: that the key belongs to a circuit.  The A / L / H queries and IC are tied to the R1CS only
+ * through the ceremony's powers of tau, and the matrices are not looked at here: g16_setup_from_srs
+ * recomputes the initial key from them and g16_key_contribution_check compares (the Python binding's
+ * check_key_circuit does both).  report->ok = 1 means the key is well formed and internally consistent --
+ * proofs made with it are then at least proofs under the key's own verifying key -- not that it is the key
+ * of your circuit.
  *
  * Memory: the queries are streamed through two page-locked host slots and two device slots of
  * min(2^18, longest query) points (208 bytes per point), the copy of one chunk under the kernels of the
@@ -549,6 +551,53 @@ g16_status g16_setup_create_ex(int device, const g16_csr* at, const g16_csr* bt,
 g16_status g16_setup_key(g16_setup* s, g16_key_desc* key, const uint8_t** ic, uint32_t* ic_count,
                          uint8_t gamma_g2[128]);
 void g16_setup_destroy(g16_setup* s);
+
+/* ---- setup from a powers-of-tau string: keys without toxic waste (not on the proving path) ------- */
+/* The first step of `snarkjs zkey new <r1cs> <ptau>` -> `zkey contribute` -> `zkey verify`: the initial key
+ * (gamma = delta = 1) of a circuit from a ceremony's structured reference string, with nobody knowing tau,
+ * alpha or beta.  The SRS holds packed affine points in the zkey encoding (Montgomery limbs, all-zero =
+ * infinity), sections 2-6 of a snarkjs .ptau:
+ *   tau_g1[i] = tau^i G1 (>= 2 domain - 1 entries), tau_g2[i] = tau^i G2, alpha_tau_g1[i] = alpha tau^i G1,
+ *   beta_tau_g1[i] = beta tau^i G1 (>= domain entries each), beta_g2 = beta G2
+ * with domain the smallest power of two >= num_constraints + n_public + 1 (g16_setup_create's rule and its
+ * G16_ERR_DOMAIN_TOO_LARGE limit, which is tested before anything is dereferenced).  Entries beyond those
+ * counts are ignored.  at / bt / ct, n_vars, n_public, num_constraints and reduction are g16_setup_create_ex's.
+ * The Lagrange bases L_j(tau) G1, alpha L_j(tau) G1, beta L_j(tau) G1 and L_j(tau) G2 are inverse size-domain
+ * transforms over the group; every query entry is a sparse combination of them with the circuit's
+ * coefficients; the H query is the odd half of a size-2 domain transform of tau_g1 (circom) or
+ * tau_g1[i + domain] - tau_g1[i] (libsnark).  alpha_g1 = alpha_tau_g1[0], beta_g1 = beta_tau_g1[0],
+ * delta_g1 = G1, delta_g2 = gamma_g2 = G2.  Canonical affine encodings are unique: the key is, byte for
+ * byte, what g16_setup_create_ex mints for toxic = (tau, alpha, beta, 1, 1).  No atomics: the same bytes on
+ * every run.  The result is the g16_setup handle of g16_setup_create: g16_setup_key / g16_setup_destroy.
+ * Memory: the whole transform is resident on the device, 144 bytes per G1 and 288 per G2 point of
+ * max(domain, n_vars), plus 64 bytes of twiddle schedule per domain point.
+ * An SRS too short for the domain, a NULL pointer or an unknown reduction: G16_ERR_INVALID.
+ *
+ * NOT checked: that the SRS is a consistent powers-of-tau string (there is no `powersoftau verify` here:
+ * the points are not tested for the curve, the subgroup or the ratios between neighbours).  A malformed SRS
+ * yields a key that means nothing; g16_key_check then still tells whether it is well formed.
+ * NOT built: a .ptau file reader, and the snarkjs section-10 transcript (see g16_key_contribute).
+ *
+ * g16_srs_create mints an SRS of 2^log2_domain (tests, synthetic keys) from a trapdoor its caller knows --
+ * toxic: tau, alpha, beta as 3 x 4 u64 Montgomery Fr -- with the kernels of g16_setup_create.  The arrays
+ * g16_srs_desc_of points at are owned by the handle.
+ * g16_setup_from_srs_times: milliseconds the calling thread's last g16_setup_from_srs spent in
+ * 0 upload + twiddle schedules, 1 G1 transforms (three of size domain), 2 the G2 transform, 3 the H
+ * transform, 4 affine passes, 5 combinations, 6 downloads; entries from 7 on are 0.               */
+typedef struct {
+  uint32_t n_tau_g1;            /* entries of tau_g1; need >= 2*domain - 1 */
+  uint32_t n_tau;               /* entries of tau_g2, alpha_tau_g1, beta_tau_g1; need >= domain */
+  const uint8_t *tau_g1, *tau_g2, *alpha_tau_g1, *beta_tau_g1;
+  uint8_t beta_g2[128];
+} g16_srs_desc;
+typedef struct g16_srs g16_srs;
+g16_status g16_srs_create(int device, uint32_t log2_domain, const uint64_t* toxic, g16_srs** out);
+g16_status g16_srs_desc_of(g16_srs* s, g16_srs_desc* out);
+void g16_srs_destroy(g16_srs* s);
+g16_status g16_setup_from_srs(int device, const g16_csr* at, const g16_csr* bt, const g16_csr* ct,
+                              uint32_t n_vars, uint32_t n_public, uint32_t num_constraints,
+                              const g16_srs_desc* srs, int reduction, g16_setup** out);
+g16_status g16_setup_from_srs_times(float* ms, uint32_t cap);
 
 /* ---- loaders (host side, C++): see g16_loaders.h ---------------------------------------------- */
 

@@ -57,6 +57,10 @@ pub struct g16_setup {
     _private: [u8; 0],
 }
 #[repr(C)]
+pub struct g16_srs {
+    _private: [u8; 0],
+}
+#[repr(C)]
 pub struct g16_zkey {
     _private: [u8; 0],
 }
@@ -117,6 +121,18 @@ pub struct g16_vk_desc {
     pub delta_g2: [u8; 128],
     pub ic: *const u8,
     pub ic_count: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct g16_srs_desc {
+    pub n_tau_g1: u32,
+    pub n_tau: u32,
+    pub tau_g1: *const u8,
+    pub tau_g2: *const u8,
+    pub alpha_tau_g1: *const u8,
+    pub beta_tau_g1: *const u8,
+    pub beta_g2: [u8; 128],
 }
 
 #[repr(C)]
@@ -257,6 +273,11 @@ extern "C" {
     pub fn g16_setup_create_ex(device: c_int, at: *const g16_csr, bt: *const g16_csr, ct: *const g16_csr, n_vars: u32, n_public: u32, num_constraints: u32, toxic: *const u64, reduction: c_int, out: *mut *mut g16_setup) -> g16_status;
     pub fn g16_setup_key(s: *mut g16_setup, key: *mut g16_key_desc, ic: *mut *const u8, ic_count: *mut u32, gamma_g2: *mut u8) -> g16_status;
     pub fn g16_setup_destroy(s: *mut g16_setup);
+    pub fn g16_srs_create(device: c_int, log2_domain: u32, toxic: *const u64, out: *mut *mut g16_srs) -> g16_status;
+    pub fn g16_srs_desc_of(s: *mut g16_srs, out: *mut g16_srs_desc) -> g16_status;
+    pub fn g16_srs_destroy(s: *mut g16_srs);
+    pub fn g16_setup_from_srs(device: c_int, at: *const g16_csr, bt: *const g16_csr, ct: *const g16_csr, n_vars: u32, n_public: u32, num_constraints: u32, srs: *const g16_srs_desc, reduction: c_int, out: *mut *mut g16_setup) -> g16_status;
+    pub fn g16_setup_from_srs_times(ms: *mut c_float, cap: u32) -> g16_status;
 
     // ---- include/g16_loaders.h -----------------------------------------------------------------
     pub fn g16_loader_last_error() -> *const c_char;
