@@ -39,7 +39,7 @@ __all__ = ["read_zkey", "R1CSFile", "R1CS", "CircomCircuit", "CircomBuilder", "C
            "trapdoor_setup", "Csr", "write_zkey", "device_tensor", "verify_batch", "verify_aggregate",
            "verify_batch_fast", "check_key", "KeyReport", "contribute_key", "check_contribution",
            "ContributionReport", "Srs", "trapdoor_srs", "setup_from_srs", "check_key_circuit",
-           "CircuitBindingReport"]
+           "CircuitBindingReport", "read_ptau", "write_ptau", "check_srs", "SrsReport"]
 
 FR_MODULUS = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 
@@ -790,8 +790,9 @@ class Srs:
     """A powers-of-tau string as g16_setup_from_srs reads it (sections 2-6 of a snarkjs .ptau): packed affine
     points in the zkey encoding, one per row.  tau_g1: (>= 2 domain - 1, 64) uint8, tau^i G1; tau_g2:
     (>= domain, 128), tau^i G2; alpha_tau_g1 / beta_tau_g1: (>= domain, 64), alpha tau^i G1 / beta tau^i G1;
-    beta_g2: 128 bytes.  Arrays a caller supplies are taken as they are: nothing here checks that they are a
-    consistent powers-of-tau string."""
+    beta_g2: 128 bytes.  Arrays a caller supplies are taken as they are: check_srs tells whether they are a
+    consistent powers-of-tau string.  power / ceremony_power: the header of the .ptau it was read from, else None."""
+    power = ceremony_power = None
 
     def __init__(self, tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, beta_g2, keepalive=None):
         self.tau_g1 = np.ascontiguousarray(tau_g1, dtype=np.uint8).reshape(-1, 64)
@@ -840,7 +841,8 @@ def setup_from_srs(a: Csr, b: Csr, c: Csr, n_vars: int, n_public: int, srs: Srs,
     """The initial key (gamma = delta = 1) of a circuit from a powers-of-tau string, on the GPU
     (g16_setup_from_srs): what `snarkjs zkey new` computes of the points, nobody knowing tau, alpha or beta.
     Matrix arguments and reduction as trapdoor_setup takes them; byte for byte the key trapdoor_setup mints
-    for (tau, alpha, beta, 1, 1).  contribute_key then re-randomises delta.  The SRS is NOT verified."""
+    for (tau, alpha, beta, 1, 1).  contribute_key then re-randomises delta.  The SRS is NOT verified here:
+    check_srs / read_ptau(validate=True) do that."""
     lib = lib or B.load()
     at, bt, ct = _setup_matrices(a, b, c, n_vars, n_public, lib)
     h = C.c_void_p()
@@ -851,6 +853,122 @@ def setup_from_srs(a: Csr, b: Csr, c: Csr, n_vars: int, n_public: int, srs: Srs,
     if st != B.G16_OK:
         raise (SynthesisError if st == B.G16_ERR_DOMAIN_TOO_LARGE else G16Error)(st, "g16_setup_from_srs failed")
     return _setup_key(lib, h, n_vars, n_public)
+
+
+def read_ptau(src, validate=False, lib: Optional[B.Library] = None) -> Srs:
+    """snarkjs .ptau (a path, or bytes) -> Srs, with .power and .ceremony_power (g16_ptau_open; the arrays are
+    views of the mapped file).  validate=True runs check_srs (on the GPU) and raises G16Error naming the first
+    bad point or the failed relation; the default looks at no point.  The contribution transcript of the file
+    is not verified either way."""
+    lib = lib or B.load()
+    h = C.c_void_p()
+    if isinstance(src, (bytes, bytearray, memoryview)):
+        buf = np.frombuffer(bytes(src), dtype=np.uint8)
+        lib.check(lib.g16_ptau_open_mem(_np_ptr(buf), buf.shape[0], C.byref(h)), loader=True)
+    else:
+        lib.check(lib.g16_ptau_open(os.fsencode(src), C.byref(h)), loader=True)
+    handle = _Handle(lib, h, lib.g16_ptau_close)
+    hdr = B.PtauHeader()
+    lib.check(lib.g16_ptau_header_get(h, C.byref(hdr)), loader=True)
+    d = B.SrsDesc()
+    lib.check(lib.g16_ptau_srs(h, C.byref(d)), loader=True)
+
+    def view(ptr, count, width):
+        return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(count * width,)).reshape(count, width)
+
+    srs = Srs(view(d.tau_g1, d.n_tau_g1, 64), view(d.tau_g2, d.n_tau, 128), view(d.alpha_tau_g1, d.n_tau, 64),
+              view(d.beta_tau_g1, d.n_tau, 64), bytes(d.beta_g2), keepalive=handle)
+    srs.power, srs.ceremony_power = int(hdr.power), int(hdr.ceremony_power)
+    if validate:
+        rep = check_srs(srs, lib=lib)
+        if not rep.ok:
+            raise G16Error(B.G16_ERR_INVALID, "ptau failed validation: " + rep.describe())
+    return srs
+
+
+def write_ptau(path, srs: Srs, lib: Optional[B.Library] = None):
+    """Srs -> snarkjs .ptau (g16_ptau_write) of the largest power the arrays cover: sections 1-6 and an empty
+    contribution list, entries beyond 2^power dropped."""
+    lib = lib or B.load()
+    d = srs.to_c()
+    power = 0
+    while power < 28 and d.n_tau >= 2 << power and d.n_tau_g1 >= (4 << power) - 1:
+        power += 1
+    lib.check(lib.g16_ptau_write(os.fsencode(path), C.byref(d), power), loader=True)
+
+
+class SrsReport:
+    """g16_srs_report + the bad-point list of g16_srs_check.  ok: no bad point and no failed relation;
+    relations_checked: False when a structural failure made the pairing relations meaningless;
+    relations_failed: SRS_* bits (_binding); n_points / n_bad / n_infinity: dicts by array name
+    (_binding.SRS_QUERIES); bad_points: [(array_name, index, reason_bits)] in ascending (array, index) order, at
+    most max_listed."""
+    RELATIONS = ((B.SRS_BASE, "tau_g1[0] / tau_g2[0] are not the generators"),
+                 (B.SRS_DEGENERATE, "tau, alpha or beta is zero"),
+                 (B.SRS_PAIR_TAU, "e(tau_g1[1], g2) != e(g1, tau_g2[1])"),
+                 (B.SRS_PAIR_TAU_G1, "tau_g1 is not a sequence of powers of tau"),
+                 (B.SRS_PAIR_TAU_G2, "tau_g2 is not a sequence of powers of tau"),
+                 (B.SRS_PAIR_ALPHA, "alpha_tau_g1 is not a sequence of powers of tau"),
+                 (B.SRS_PAIR_BETA, "beta_tau_g1 is not a sequence of powers of tau"),
+                 (B.SRS_PAIR_BETA_G2, "e(beta_tau_g1[0], g2) != e(g1, beta_g2)"))
+    REASONS = ((B.KEY_BAD_NONCANONICAL, "non-canonical coordinate"), (B.KEY_BAD_OFF_CURVE, "off the curve"),
+               (B.KEY_BAD_SUBGROUP, "outside the prime-order subgroup"))
+
+    def __init__(self, rep: B.SrsReportC, bad):
+        self.ok = bool(rep.ok)
+        self.relations_checked = bool(rep.relations_checked)
+        self.relations_failed = int(rep.relations_failed)
+        self.n_points = {q: int(rep.n_points[i]) for i, q in enumerate(B.SRS_QUERIES)}
+        self.n_bad = {q: int(rep.n_bad[i]) for i, q in enumerate(B.SRS_QUERIES)}
+        self.n_infinity = {q: int(rep.n_infinity[i]) for i, q in enumerate(B.SRS_QUERIES)}
+        self.bad_points = [(B.SRS_QUERIES[b.query], int(b.index), int(b.reason)) for b in bad]
+
+    def __eq__(self, o):
+        return isinstance(o, SrsReport) and vars(o) == vars(self)
+
+    def describe(self) -> str:
+        if self.ok:
+            return "ok"
+        if self.bad_points:
+            q, i, why = self.bad_points[0]
+            words = ", ".join(w for bit, w in self.REASONS if why & bit)
+            name = f"{B.SRS_SINGLES[i]}" if q == "singles" else f"{q}[{i}]"
+            return f"{name}: {words} (reason {why}); {sum(self.n_bad.values())} bad point(s) in all"
+        if not self.relations_checked:
+            return f"{sum(self.n_bad.values())} bad point(s)"
+        return "; ".join(w for bit, w in self.RELATIONS if self.relations_failed & bit)
+
+    def __repr__(self):
+        return f"SrsReport({self.describe()})"
+
+
+def check_srs(srs: Srs, rho=None, device=0, max_listed=64, lib: Optional[B.Library] = None) -> SrsReport:
+    """Validation of a powers-of-tau string on the GPU (g16_srs_check), the point arithmetic of `snarkjs
+    powersoftau verify`: every point canonical, on its curve and (G2) in the prime-order subgroup; then the
+    bases are the generators, tau_g1 and tau_g2 hold the same tau, every array is a sequence in that one ratio
+    and beta_g2 matches beta_tau_g1[0].  Call it once on an SRS you did not mint, before setup_from_srs or
+    check_key_circuit build on it.  The ceremony's contribution transcript is NOT verified: a passing report
+    says nothing about who knows tau.
+    rho: None (drawn by the library from the OS CSPRNG) or (len(tau_g1) - 1) + 3 (n_tau - 1) ints in
+    [1, 2^128), the coefficients of tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1 in this order."""
+    lib = lib or B.load()
+    d = srs.to_c()
+    rho_arr = None
+    if rho is not None:
+        rho = [int(x) for x in rho]
+        if len(rho) != (d.n_tau_g1 - 1) + 3 * (d.n_tau - 1):
+            raise G16Error(B.G16_ERR_INVALID, "one coefficient per pair of neighbours")
+        if any(not 0 <= x < 1 << 128 for x in rho):
+            raise G16Error(B.G16_ERR_INVALID, "coefficients are integers in [1, 2^128)")
+        rho_arr = np.array([[x & 0xFFFFFFFFFFFFFFFF, x >> 64] for x in rho], dtype=np.uint64).reshape(-1, 2)
+    max_listed = int(max_listed)
+    bad = (B.KeyBadPoint * max(max_listed, 1))()
+    rep = B.SrsReportC()
+    st = lib.g16_srs_check(device, C.byref(d), _np_ptr(rho_arr) if rho_arr is not None else None, bad, max_listed,
+                           C.byref(rep))
+    if st != B.G16_OK:
+        raise G16Error(st, "g16_srs_check failed")
+    return SrsReport(rep, bad[:rep.n_listed])
 
 
 SETUP_SRS_PHASES = ("upload", "ntt_g1", "ntt_g2", "ntt_h", "affine", "combine", "download")

@@ -99,6 +99,24 @@ class SrsDesc(C.Structure):
                 ("alpha_tau_g1", C.c_void_p), ("beta_tau_g1", C.c_void_p), ("beta_g2", C.c_uint8 * 128)]
 
 
+# g16_srs_check: query ids and relation bits (include/g16_amd.h); the reason bits are KEY_BAD_*
+SRS_QUERIES = ("tau_g1", "tau_g2", "alpha_tau_g1", "beta_tau_g1", "singles")
+SRS_Q_TAU_G1, SRS_Q_TAU_G2, SRS_Q_ALPHA_TAU_G1, SRS_Q_BETA_TAU_G1, SRS_Q_SINGLES = range(5)
+SRS_SINGLES = ("beta_g2",)
+SRS_BASE, SRS_DEGENERATE, SRS_PAIR_TAU, SRS_PAIR_TAU_G1, SRS_PAIR_TAU_G2, SRS_PAIR_ALPHA, SRS_PAIR_BETA, \
+    SRS_PAIR_BETA_G2 = 1, 2, 4, 8, 16, 32, 64, 128
+
+
+class SrsReportC(C.Structure):
+    _fields_ = [("ok", C.c_uint8), ("relations_checked", C.c_uint8), ("relations_failed", C.c_uint32),
+                ("n_points", C.c_uint64 * 5), ("n_bad", C.c_uint64 * 5), ("n_infinity", C.c_uint64 * 5),
+                ("n_listed", C.c_uint32)]
+
+
+class PtauHeader(C.Structure):
+    _fields_ = [("n8q", C.c_uint32), ("q", C.c_uint8 * 32), ("power", C.c_uint32), ("ceremony_power", C.c_uint32)]
+
+
 class ZkeyHeader(C.Structure):
     _fields_ = [("n8q", C.c_uint32), ("n8r", C.c_uint32), ("q", C.c_uint8 * 32),
                 ("r", C.c_uint8 * 32), ("n_vars", C.c_uint32), ("n_public", C.c_uint32),
@@ -139,6 +157,8 @@ ABI_SYMBOLS = [
     "g16_prove_batch", "g16_prove_batch_dev", "g16_witness_map_batch",
     "g16_key_check", "g16_key_contribute", "g16_key_contribution_check",
     "g16_srs_create", "g16_srs_desc_of", "g16_srs_destroy", "g16_setup_from_srs", "g16_setup_from_srs_times",
+    "g16_srs_check", "g16_ptau_open", "g16_ptau_open_mem", "g16_ptau_close", "g16_ptau_header_get", "g16_ptau_srs",
+    "g16_ptau_write",
 ]
 
 
@@ -251,6 +271,14 @@ class Library:
                                              C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SrsDesc), C.c_int,
                                              C.POINTER(vp)]),
             "g16_setup_from_srs_times": (C.c_int, [C.POINTER(C.c_float), C.c_uint32]),
+            "g16_srs_check": (C.c_int, [C.c_int, C.POINTER(SrsDesc), vp, C.POINTER(KeyBadPoint), C.c_uint32,
+                                        C.POINTER(SrsReportC)]),
+            "g16_ptau_open": (C.c_int, [C.c_char_p, C.POINTER(vp)]),
+            "g16_ptau_open_mem": (C.c_int, [vp, C.c_size_t, C.POINTER(vp)]),
+            "g16_ptau_close": (None, [vp]),
+            "g16_ptau_header_get": (C.c_int, [vp, C.POINTER(PtauHeader)]),
+            "g16_ptau_srs": (C.c_int, [vp, C.POINTER(SrsDesc)]),
+            "g16_ptau_write": (C.c_int, [C.c_char_p, C.POINTER(SrsDesc), C.c_uint32]),
         }
         # measurement builds only (make EXTRA=-DG16_DEBUG_ABI; include/g16_amd.h): not an ABI symbol, never "missing"
         optional = {"g16_debug_alu_bench": (C.c_int, [C.c_int, C.c_int, C.c_uint32, C.c_uint32,

@@ -4,6 +4,7 @@
 //          HeaderGroth::read :288-317, deserialize_field_fr :322-325, deserialize_g1/g2 :340-360)
 //   r1cs : reference src/circom/r1cs_reader.rs (R1CSFile::new :54-146, Header::new :161-200,
 //          read_constraint_vec :203-213, read_constraints :215-229, read_map :231-249, R1CS::from :26-39)
+//   ptau : snarkjs powers-of-tau files, the same container (not parsed by the reference; g16_loaders.h)
 // The point sections are handed out as zero-copy views: the on-disk encoding (x|y Montgomery LE,
 // all-zero = infinity) is already the device encoding.
 #include <fcntl.h>
@@ -214,6 +215,12 @@ struct g16_zkey {
   CsrOwned A, B;
 };
 
+struct g16_ptau {
+  FileView data;
+  std::map<uint32_t, Section> sec;  // first occurrence wins, as for a zkey
+  g16_ptau_header hdr;
+};
+
 struct g16_r1cs {
   g16_r1cs_header hdr;
   CsrOwned A, B, C;
@@ -285,6 +292,64 @@ g16_status zkey_parse(g16_zkey* z) {
   for (auto& nd : needs)
     if (z->sec[nd.id].size < nd.bytes)
       return fail(G16_ERR_IO, "zkey: section " + std::to_string(nd.id) + " is too short");
+  return G16_OK;
+}
+
+// snarkjs .ptau (include/g16_loaders.h).  Written from knowledge of snarkjs: there
+// was no .ptau file to pin the reader to.
+constexpr uint32_t kPtauMaxPower = 28;
+
+uint64_t ptau_section_bytes(uint32_t id, uint32_t power) {
+  const uint64_t n = (uint64_t)1 << power;
+  switch (id) {
+    case 2: return (2 * n - 1) * 64;
+    case 3: return n * 128;
+    case 4: case 5: return n * 64;
+    default: return 128;  // 6
+  }
+}
+
+g16_status ptau_parse(g16_ptau* z) {
+  const uint8_t* d = z->data.data();
+  const size_t n = z->data.size();
+  Cursor c(d, n);
+  const uint8_t* magic = c.bytes(4);
+  if (!magic) return fail(G16_ERR_IO, "ptau: truncated file header");
+  if (memcmp(magic, "ptau", 4) != 0) return fail(G16_ERR_IO, "ptau: bad magic");
+  const uint32_t version = c.u32();
+  const uint32_t nsec = c.u32();
+  if (!c.ok) return fail(G16_ERR_IO, "ptau: truncated file header");
+  if (version != 1) return fail(G16_ERR_IO, "ptau: unsupported version " + std::to_string(version));
+  for (uint32_t i = 0; i < nsec; ++i) {
+    const uint32_t id = c.u32();
+    const uint64_t len = c.u64();
+    if (!c.ok) return fail(G16_ERR_IO, "ptau: truncated section table");
+    if (!z->sec.count(id)) z->sec[id] = Section{c.o, len};
+    c.skip(len);
+    if (!c.ok) return fail(G16_ERR_IO, "ptau: section " + std::to_string(id) + " runs past the end of the file");
+  }
+  for (uint32_t id : {1u, 2u, 3u, 4u, 5u, 6u})
+    if (!z->sec.count(id)) return fail(G16_ERR_IO, "ptau: missing section " + std::to_string(id));
+  const Section s1 = z->sec[1];
+  Cursor h(d, s1.pos + (size_t)s1.size, s1.pos);  // the section lies inside the file: checked above
+  g16_ptau_header& H = z->hdr;
+  memset(&H, 0, sizeof H);
+  H.n8q = h.u32();
+  if (!h.ok) return fail(G16_ERR_IO, "ptau: truncated header section");
+  if (H.n8q != 32) return fail(G16_ERR_IO, "ptau: n8 != 32");
+  const uint8_t* q = h.bytes(32);
+  H.power = h.u32();
+  H.ceremony_power = h.u32();
+  if (!h.ok) return fail(G16_ERR_IO, "ptau: truncated header section");
+  if (memcmp(q, g16::FqParams::MOD, 32) != 0) return fail(G16_ERR_IO, "ptau: the prime is not the BN254 base field's");
+  memcpy(H.q, q, 32);
+  if (H.power > kPtauMaxPower)
+    return fail(G16_ERR_IO, "ptau: power " + std::to_string(H.power) + " > " + std::to_string(kPtauMaxPower));
+  for (uint32_t id : {2u, 3u, 4u, 5u, 6u})
+    if (z->sec[id].size != ptau_section_bytes(id, H.power))
+      return fail(G16_ERR_IO, "ptau: section " + std::to_string(id) + " has " + std::to_string(z->sec[id].size) +
+                                  " bytes, power " + std::to_string(H.power) + " needs " +
+                                  std::to_string(ptau_section_bytes(id, H.power)));
   return G16_OK;
 }
 
@@ -554,6 +619,100 @@ g16_status g16_zkey_matrices(g16_zkey* z, g16_matrices* out) {
   }
   *out = z->mat;
   return G16_OK;
+}
+
+g16_status g16_ptau_open_mem(const uint8_t* data, size_t len, g16_ptau** out) {
+  if (!data || !out) return fail(G16_ERR_INVALID, "null argument");
+  *out = nullptr;
+  g16_ptau* z = new g16_ptau();
+  z->data.copy_of(data, len);
+  g16_status st = ptau_parse(z);
+  if (st != G16_OK) {
+    delete z;
+    return st;
+  }
+  *out = z;
+  return G16_OK;
+}
+
+g16_status g16_ptau_open(const char* path, g16_ptau** out) {
+  if (!path || !out) return fail(G16_ERR_INVALID, "null argument");
+  *out = nullptr;
+  g16_ptau* z = new g16_ptau();
+  std::string err;
+  if (!z->data.map_file(path, err)) {
+    delete z;
+    return fail(G16_ERR_IO, err);
+  }
+  g16_status st = ptau_parse(z);
+  if (st != G16_OK) {
+    delete z;
+    return st;
+  }
+  *out = z;
+  return G16_OK;
+}
+
+void g16_ptau_close(g16_ptau* p) { delete p; }
+
+g16_status g16_ptau_header_get(const g16_ptau* p, g16_ptau_header* out) {
+  if (!p || !out) return fail(G16_ERR_INVALID, "null argument");
+  *out = p->hdr;
+  return G16_OK;
+}
+
+g16_status g16_ptau_srs(const g16_ptau* p, g16_srs_desc* out) {
+  if (!p || !out) return fail(G16_ERR_INVALID, "null argument");
+  const uint8_t* d = p->data.data();
+  const uint32_t n = 1u << p->hdr.power;
+  memset(out, 0, sizeof *out);
+  out->n_tau_g1 = 2 * n - 1;
+  out->n_tau = n;
+  out->tau_g1 = d + p->sec.at(2).pos;
+  out->tau_g2 = d + p->sec.at(3).pos;
+  out->alpha_tau_g1 = d + p->sec.at(4).pos;
+  out->beta_tau_g1 = d + p->sec.at(5).pos;
+  memcpy(out->beta_g2, d + p->sec.at(6).pos, 128);
+  return G16_OK;
+}
+
+g16_status g16_ptau_write(const char* path, const g16_srs_desc* srs, uint32_t power) {
+  if (!path || !srs || !srs->tau_g1 || !srs->tau_g2 || !srs->alpha_tau_g1 || !srs->beta_tau_g1)
+    return fail(G16_ERR_INVALID, "null argument");
+  if (power > kPtauMaxPower) return fail(G16_ERR_INVALID, "ptau: power > 28");
+  const uint64_t n = (uint64_t)1 << power;
+  if (srs->n_tau_g1 < 2 * n - 1 || srs->n_tau < n) return fail(G16_ERR_INVALID, "ptau: the SRS is shorter than 2^power");
+  FILE* f = fopen(path, "wb");
+  if (!f) return fail(G16_ERR_IO, std::string("cannot create ") + path);
+  bool ok = true;
+  auto put = [&](const void* p, size_t k) { ok = ok && (k == 0 || fwrite(p, 1, k, f) == k); };
+  auto u32 = [&](uint32_t v) { put(&v, 4); };
+  auto sec = [&](uint32_t id, const void* p) {
+    const uint64_t len = ptau_section_bytes(id, power);
+    u32(id);
+    put(&len, 8);
+    put(p, (size_t)len);
+  };
+  put("ptau", 4);
+  u32(1);
+  u32(7);
+  const uint64_t len1 = 4 + 32 + 4 + 4, len7 = 4;
+  u32(1);
+  put(&len1, 8);
+  u32(32);
+  put(g16::FqParams::MOD, 32);
+  u32(power);
+  u32(power);
+  sec(2, srs->tau_g1);
+  sec(3, srs->tau_g2);
+  sec(4, srs->alpha_tau_g1);
+  sec(5, srs->beta_tau_g1);
+  sec(6, srs->beta_g2);
+  u32(7);
+  put(&len7, 8);
+  u32(0);  // no contributions recorded
+  ok = (fclose(f) == 0) && ok;
+  return ok ? G16_OK : fail(G16_ERR_IO, "short write");
 }
 
 g16_status g16_r1cs_open_mem(const uint8_t* data, size_t len, g16_r1cs** out) {

@@ -573,10 +573,13 @@ void g16_setup_destroy(g16_setup* s);
  * max(domain, n_vars), plus 64 bytes of twiddle schedule per domain point.
  * An SRS too short for the domain, a NULL pointer or an unknown reduction: G16_ERR_INVALID.
  *
- * NOT checked: that the SRS is a consistent powers-of-tau string (there is no `powersoftau verify` here:
- * the points are not tested for the curve, the subgroup or the ratios between neighbours).  A malformed SRS
- * yields a key that means nothing; g16_key_check then still tells whether it is well formed.
- * NOT built: a .ptau file reader, and the snarkjs section-10 transcript (see g16_key_contribute).
+ * NOT checked HERE: that the SRS is a consistent powers-of-tau string.  g16_setup_from_srs takes the points as
+ * they come; a malformed SRS yields a key that means nothing (g16_key_check then still tells whether it is
+ * well formed).  Run g16_srs_check (below) once on an SRS that was not minted locally -- it tests every point
+ * for the curve and the subgroup and the ratios between neighbours; g16_ptau_open (g16_loaders.h) reads the
+ * arrays from a snarkjs .ptau file.
+ * NOT built: the transcripts -- section 7 of a .ptau (the ceremony's contributions) and section 10 of a .zkey
+ * (see g16_key_contribute) are neither written nor verified.
  *
  * g16_srs_create mints an SRS of 2^log2_domain (tests, synthetic keys) from a trapdoor its caller knows --
  * toxic: tau, alpha, beta as 3 x 4 u64 Montgomery Fr -- with the kernels of g16_setup_create.  The arrays
@@ -598,6 +601,67 @@ g16_status g16_setup_from_srs(int device, const g16_csr* at, const g16_csr* bt, 
                               uint32_t n_vars, uint32_t n_public, uint32_t num_constraints,
                               const g16_srs_desc* srs, int reduction, g16_setup** out);
 g16_status g16_setup_from_srs_times(float* ms, uint32_t cap);
+
+/* ---- powers-of-tau validation (not on the proving path) ------------------------------------------ */
+/* g16_setup_from_srs and the binding's check_key_circuit build on the SRS they are given: a crafted SRS makes
+ * the circuit-binding check vouch for a forged key, one flipped bit makes it reject every honest one.
+ * g16_srs_check is the point arithmetic of `snarkjs powersoftau verify` on the GPU: call it once on an SRS
+ * that was not minted locally (g16_ptau_open).  Standalone like g16_key_check: no ctx is needed, a ctx alive on
+ * the device is left untouched.
+ *
+ * Structural checks, on EVERY entry handed over (all n_tau_g1 and n_tau of them, not only those some domain
+ * needs) and on beta_g2: the predicates, reason bits (G16_KEY_BAD_*) and first-failure rule of g16_key_check;
+ * the all-zero encoding is the point at infinity, valid and counted in n_infinity.  Queries: G16_SRS_Q_TAU_G1,
+ * _TAU_G2, _ALPHA_TAU_G1, _BETA_TAU_G1 and _SINGLES (index 0 = beta_g2).  bad_out receives the first
+ * min(bad_cap, 65536) bad points in ascending (query, index) order -- the same list on every run (scans, no
+ * atomics); n_bad counts all of them.
+ *
+ * Relations, evaluated only when no structural check failed (relations_checked = 0, relations_failed = 0
+ * otherwise).  For an array P of m points and its own segment of coefficients rho_0 .. rho_{m-2},
+ *   Lo(P) = sum_{i<m-1} rho_i P[i]        Hi(P) = sum_{i<m-1} rho_i P[i+1]
+ *   G16_SRS_BASE          tau_g1[0] != the G1 generator or tau_g2[0] != the G2 generator (bytes)
+ *   G16_SRS_DEGENERATE    tau_g1[1], tau_g2[1], alpha_tau_g1[0], beta_tau_g1[0] or beta_g2 is infinity
+ *                         (tau, alpha or beta = 0)
+ *   G16_SRS_PAIR_TAU      e(tau_g1[1], g2) != e(g1, tau_g2[1])            the two arrays hold the same tau
+ *   G16_SRS_PAIR_TAU_G1   e(Hi(tau_g1), g2) != e(Lo(tau_g1), tau_g2[1])   every neighbour ratio of tau_g1 is tau
+ *   G16_SRS_PAIR_TAU_G2   e(tau_g1[1], Lo(tau_g2)) != e(g1, Hi(tau_g2))   the same for tau_g2
+ *   G16_SRS_PAIR_ALPHA    e(Hi(alpha_tau_g1), g2) != e(Lo(alpha_tau_g1), tau_g2[1])
+ *   G16_SRS_PAIR_BETA     the same for beta_tau_g1
+ *   G16_SRS_PAIR_BETA_G2  e(beta_tau_g1[0], g2) != e(g1, beta_g2)
+ * (g1, g2: the standard generators.)  Soundness: every point that reaches a relation is in its prime-order
+ * group (G1 has cofactor 1, G2 points are subgroup-tested), so P[i+1] - tau P[i] = d_i G for scalars d_i and
+ * a relation holds iff sum rho_i d_i = 0 mod r: with unpredictable rho a string whose neighbours are not all
+ * in the one ratio tau passes with probability at most 2^-127 (the small-exponent test of
+ * g16_verify_aggregate and g16_key_check).  Whoever knows rho makes two entries cancel (d_j = rho_k,
+ * d_k = -rho_j), and the relation holds.
+ * rho: ((n_tau_g1 - 1) + 3 (n_tau - 1)) x 2 u64 in the order tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1
+ *      (little-endian 128-bit integers, NOT Montgomery), every one non-zero (a zero entry: G16_ERR_INVALID), or
+ *      NULL: drawn from the operating system's CSPRNG (a failure to get randomness is G16_ERR_INTERNAL, never
+ *      a fixed fallback).
+ * n_tau_g1 < 2, n_tau < 2 or a NULL pointer: G16_ERR_INVALID.
+ *
+ * NOT checked: the section-7 contribution transcript of the ceremony (challenge hashes, proofs of knowledge,
+ * the beacon), so nothing is said about WHO knows tau, alpha or beta -- report->ok = 1 means the string is a
+ * well formed powers-of-tau string over the standard generators for SOME (tau, alpha, beta) != 0.
+ *
+ * Memory: the arrays are streamed through two page-locked host slots and two device slots of
+ * min(2^18, longest array) points (128 bytes per point plus 16 per coefficient), the copy of one chunk under
+ * the kernels of the one before; device use does not grow with the SRS.  G16_SRSCHECK_CHUNK=<points>
+ * overrides the chunk (tests).  No atomics: the same report and list on every run.  Returns G16_OK when the
+ * check RAN (the verdict is in *report), G16_ERR_NO_DEVICE without a device: there is no CPU fallback.    */
+enum { G16_SRS_Q_TAU_G1 = 0, G16_SRS_Q_TAU_G2, G16_SRS_Q_ALPHA_TAU_G1, G16_SRS_Q_BETA_TAU_G1,
+       G16_SRS_Q_SINGLES /* index 0: beta_g2 */, G16_SRS_N_QUERIES };
+enum { G16_SRS_BASE = 1, G16_SRS_DEGENERATE = 2, G16_SRS_PAIR_TAU = 4, G16_SRS_PAIR_TAU_G1 = 8,
+       G16_SRS_PAIR_TAU_G2 = 16, G16_SRS_PAIR_ALPHA = 32, G16_SRS_PAIR_BETA = 64, G16_SRS_PAIR_BETA_G2 = 128 };
+typedef struct {
+  uint8_t  ok;                 /* 1 iff no bad point and no failed relation */
+  uint8_t  relations_checked;  /* 0 when a structural failure made the pairing relations meaningless */
+  uint32_t relations_failed;   /* G16_SRS_* */
+  uint64_t n_points[G16_SRS_N_QUERIES], n_bad[G16_SRS_N_QUERIES], n_infinity[G16_SRS_N_QUERIES];
+  uint32_t n_listed;           /* entries written to bad_out */
+} g16_srs_report;
+g16_status g16_srs_check(int device, const g16_srs_desc* srs, const uint64_t* rho /* NULL = CSPRNG */,
+                         g16_key_bad_point* bad_out, uint32_t bad_cap, g16_srs_report* report);
 
 /* ---- loaders (host side, C++): see g16_loaders.h ---------------------------------------------- */
 

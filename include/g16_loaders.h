@@ -3,6 +3,7 @@
  *   g16_zkey_*  <- read_zkey / BinFile (reference src/zkey.rs:53-60,73-133,151-196,288-368)
  *   g16_r1cs_*  <- R1CSFile::new + R1CS::from (reference src/circom/r1cs_reader.rs:26-39,54-249)
  *   g16_wtns_*  <- snarkjs .wtns (not parsed by the reference)
+ *   g16_ptau_*  <- snarkjs .ptau (not parsed by the reference)
  * but hand back GPU-ready packed arrays (the on-disk point encoding IS the device encoding) from
  * one bulk read instead of one Read call per 32-byte field (src/zkey.rs:328-368).
  * All returned pointers are owned by the handle and stay valid until *_close.                    */
@@ -57,6 +58,36 @@ g16_status g16_zkey_matrices(g16_zkey* z, g16_matrices* out);
 g16_status g16_zkey_write(const char* path, const g16_key_desc* key, const uint8_t* ic,
                           const uint8_t gamma_g2[128], const g16_csr* a, const g16_csr* b,
                           uint32_t num_constraints);
+
+/* ---------------------------------------------------------------- .ptau ---------------------- */
+/* snarkjs powers-of-tau files: the SRS g16_setup_from_srs / g16_srs_check take.  The binfile container of
+ * .zkey: magic "ptau", version u32 = 1, nSections u32, then (id u32, size u64,
+ * payload) in any order (the first occurrence of an id wins).
+ *   1  n8 u32 (= 32), q[n8] little-endian (must be BN254 q), power u32, ceremony_power u32
+ *   2  tauG1, 2 * 2^power - 1 G1 points      3  tauG2, 2^power G2 points
+ *   4  alphaTauG1, 2^power G1 points          5  betaTauG1, 2^power G1 points        6  betaG2, one G2 point
+ *   7  contributions: ignored on read, written as a zero count
+ *   12..15  the Lagrange-form copies of a "prepared" file: ignored, g16_setup_from_srs computes its own
+ * Points in the encoding of the rest of the ABI: 32-byte little-endian Montgomery coordinates, all-zero =
+ * infinity.  THIS DESCRIPTION IS WRITTEN FROM KNOWLEDGE OF snarkjs: no .ptau file and no snarkjs were at hand to
+ * pin it to, the reader is tested against this writer and against an independent encoding of the same
+ * description only.
+ * G16_ERR_IO with a message in g16_loader_last_error: wrong magic, version or prime; a section among 1..6
+ * missing; a section size that does not match power; a truncated file; power > 28.
+ * The points are handed out as they come: run g16_srs_check on them.  The section-7 transcript is NOT
+ * verified.  g16_ptau_open maps the file under the rules of g16_zkey_open (the file must stay unchanged
+ * until g16_ptau_close; G16_ZKEY_COPY=1 reads it into owned memory).                                      */
+typedef struct g16_ptau g16_ptau;
+typedef struct { uint32_t n8q; uint8_t q[32]; uint32_t power, ceremony_power; } g16_ptau_header;
+g16_status g16_ptau_open(const char* path, g16_ptau** out);
+g16_status g16_ptau_open_mem(const uint8_t* data, size_t len, g16_ptau** out); /* data is copied */
+void g16_ptau_close(g16_ptau* p);
+g16_status g16_ptau_header_get(const g16_ptau* p, g16_ptau_header* out);
+/* zero-copy views of sections 2..6, owned by the handle */
+g16_status g16_ptau_srs(const g16_ptau* p, g16_srs_desc* out);
+/* writes sections 1..7 from an SRS with n_tau_g1 >= 2 * 2^power - 1 and n_tau >= 2^power (entries beyond are
+ * dropped); ceremony_power = power                                                                       */
+g16_status g16_ptau_write(const char* path, const g16_srs_desc* srs, uint32_t power);
 
 /* ---------------------------------------------------------------- .r1cs ---------------------- */
 typedef struct g16_r1cs g16_r1cs;

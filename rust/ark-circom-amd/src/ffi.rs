@@ -68,6 +68,10 @@ pub struct g16_zkey {
 pub struct g16_r1cs {
     _private: [u8; 0],
 }
+#[repr(C)]
+pub struct g16_ptau {
+    _private: [u8; 0],
+}
 
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -214,6 +218,29 @@ pub struct g16_contribution_report {
     pub n_listed: u32,
 }
 
+pub const G16_SRS_N_QUERIES: usize = 5;
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct g16_srs_report {
+    pub ok: u8,
+    pub relations_checked: u8,
+    pub relations_failed: u32,
+    pub n_points: [u64; G16_SRS_N_QUERIES],
+    pub n_bad: [u64; G16_SRS_N_QUERIES],
+    pub n_infinity: [u64; G16_SRS_N_QUERIES],
+    pub n_listed: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct g16_ptau_header {
+    pub n8q: u32,
+    pub q: [u8; 32],
+    pub power: u32,
+    pub ceremony_power: u32,
+}
+
 extern "C" {
     // ---- include/g16_amd.h ---------------------------------------------------------------------
     pub fn g16_ctx_create(key: *const g16_key_desc, a: *const g16_csr, b: *const g16_csr, num_constraints: u32, opt: *const g16_options, out: *mut *mut g16_ctx) -> g16_status;
@@ -278,9 +305,16 @@ extern "C" {
     pub fn g16_srs_destroy(s: *mut g16_srs);
     pub fn g16_setup_from_srs(device: c_int, at: *const g16_csr, bt: *const g16_csr, ct: *const g16_csr, n_vars: u32, n_public: u32, num_constraints: u32, srs: *const g16_srs_desc, reduction: c_int, out: *mut *mut g16_setup) -> g16_status;
     pub fn g16_setup_from_srs_times(ms: *mut c_float, cap: u32) -> g16_status;
+    pub fn g16_srs_check(device: c_int, srs: *const g16_srs_desc, rho: *const u64, bad_out: *mut g16_key_bad_point, bad_cap: u32, report: *mut g16_srs_report) -> g16_status;
 
     // ---- include/g16_loaders.h -----------------------------------------------------------------
     pub fn g16_loader_last_error() -> *const c_char;
+    pub fn g16_ptau_open(path: *const c_char, out: *mut *mut g16_ptau) -> g16_status;
+    pub fn g16_ptau_open_mem(data: *const u8, len: usize, out: *mut *mut g16_ptau) -> g16_status;
+    pub fn g16_ptau_close(p: *mut g16_ptau);
+    pub fn g16_ptau_header_get(p: *const g16_ptau, out: *mut g16_ptau_header) -> g16_status;
+    pub fn g16_ptau_srs(p: *const g16_ptau, out: *mut g16_srs_desc) -> g16_status;
+    pub fn g16_ptau_write(path: *const c_char, srs: *const g16_srs_desc, power: u32) -> g16_status;
     pub fn g16_zkey_open(path: *const c_char, out: *mut *mut g16_zkey) -> g16_status;
     pub fn g16_zkey_open_mem(data: *const u8, len: usize, out: *mut *mut g16_zkey) -> g16_status;
     pub fn g16_zkey_close(z: *mut g16_zkey);
