@@ -139,6 +139,16 @@ inline bool sched_r5() {
   return v;
 }
 
+// Where the latency-bound tails (k_set_sum x 2 + k_horner) of a large single-device proof's reductions run
+// (enqueue_witness_msms, large bucket sets).  G16_TAIL_SPLIT (diagnostic, A/B): 0 all on the main stream (the
+// round-6 schedule), 1 those of A | B1 and L on `red`, 2 that of B2 as well (the default), 3 B2's on the
+// high-priority aux stream instead.  One stream (G16_NO_OVERLAP), sharded ranks and the round-5 schedule: 0.
+inline int tail_split(const g16_ctx* c, bool sharded) {
+  static const int v = [] { const char* e = getenv("G16_TAIL_SPLIT"); return e ? atoi(e) : 2; }();
+  if (!c->overlap || sharded || sched_r5()) return 0;
+  return v < 0 ? 0 : v > 3 ? 3 : v;
+}
+
 void collect_times(g16_ctx* c) {
   if (c->timer.enabled) c->timer.collect(c->st_ms, c->st_cnt);
 }
@@ -301,16 +311,61 @@ void enqueue_witness_msms(g16_ctx* c, const BucketChunk& ch, Hook after_ab, Hook
     msm_reduce<Fq>(*ch.sort_w, *ch.work1, 0, 3, &S->A, s, tm, false, ps);
     after_ab(s);
   } else {
-    // large bucket sets: the reduction is throughput bound, and reducing A and B1 at once lets
-    // the variable-base part of the finalisation start ~10 ms earlier (measured at 2^22: 41.3 vs
-    // 43.0 ms per proof)
+    // Large bucket sets (>= 2^18 buckets: 2^21-constraint proofs and up).  k_combine_large + k_bucket_reduce (the
+    // HEAD of a reduction) are throughput bound: off the main stream they only take issue slots from the
+    // accumulation they would run beside (round 4: the whole L reduction beside the H accumulation or the H
+    // reduction, 37.67 / 37.50 ms shipped vs 37.56 / 37.59 and 37.77 / 37.46, profiles/r04_defer_l_reduction_ab.txt),
+    // so they stay here.  The TAIL -- two k_set_sum levels and k_horner -- is a few workgroups in a dependent chain
+    // of EC additions (0.25 - 0.5 ms, profiles/r06_timeline_k22.txt) that issues next to nothing: the tails of
+    // A | B1, L and B2 go to the `red` stream (tail_split) and the next accumulation starts right behind the head.
+    // A and B1 are reduced at once so that the variable-base part of the finalisation starts ~10 ms earlier
+    // (measured at 2^22: 41.3 vs 43.0 ms per proof); it is ordered behind their TAIL (after_ab(red)).
+    // A | B1 and L share slot 0 of work1: the L accumulation overwrites `partial` behind the A | B1 head (stream
+    // order), the L head writes `contrib` and waits for the A | B1 tail to have read it (ev_acc[1]).  The tails are
+    // serialised on `red`; ev_b2 -- recorded last on `red` -- and with it ev_side cover all of them, and every
+    // caller joins ev_side on the main stream before the proof ends, so the next proof's heads find them drained.
+    const int ts = small ? 0 : tail_split(c, sharded);  // (small sets with a two-slot workspace, or one stream: as before)
+    hipStream_t q = ts >= 1 ? c->red : s;
     accumulate_ab(c, ch, s, tm);
-    msm_reduce<Fq>(*ch.sort_w, *ch.work1, 0, 2, &S->A, s, tm, false, ps);  // ProofSums keeps A, B1 adjacent
-    after_ab(s);
-    // (round 4, VERDICT r3 item 5: taking the L reduction off the main stream -- beside the H
-    // accumulation, or beside the H reduction -- was built and measured: 37.67 / 37.50 ms shipped vs
-    // 37.56 / 37.59 and 37.77 / 37.46, same box; profiles/r04_defer_l_reduction_ab.txt.  Not kept.)
-    msm_run<Fq>(*ch.sort_w, c->ptsL, c->l_idx_min, *ch.work1, &S->L, s, tm, ps);
+    if (q == s) {
+      msm_reduce<Fq>(*ch.sort_w, *ch.work1, 0, 2, &S->A, s, tm, false, ps);  // ProofSums keeps A, B1 adjacent
+      after_ab(s);
+      msm_run<Fq>(*ch.sort_w, c->ptsL, c->l_idx_min, *ch.work1, &S->L, s, tm, ps);
+    } else {
+      msm_reduce_head<Fq>(*ch.sort_w, *ch.work1, 0, 2, s, tm);
+      G16_HIP(hipEventRecord(c->ev_acc[0], s));
+      G16_HIP(hipStreamWaitEvent(q, c->ev_acc[0], 0));
+      msm_reduce_tail<Fq>(*ch.sort_w, *ch.work1, 0, 2, &S->A, q, tm, false, ps);
+      G16_HIP(hipEventRecord(c->ev_acc[1], q));
+      after_ab(q);
+      msm_accumulate<Fq>(*ch.sort_w, c->ptsL, c->l_idx_min, *ch.work1, 0, s, tm);
+      G16_HIP(hipStreamWaitEvent(s, c->ev_acc[1], 0));  // slot 0's contrib is free (long since: 4 ms of accumulation)
+      msm_reduce_head<Fq>(*ch.sort_w, *ch.work1, 0, 1, s, tm);
+      G16_HIP(hipEventRecord(c->ev_acc[2], s));
+      G16_HIP(hipStreamWaitEvent(q, c->ev_acc[2], 0));
+      msm_reduce_tail<Fq>(*ch.sort_w, *ch.work1, 0, 1, &S->L, q, tm, false, ps);
+    }
+    if (ts >= 2) {
+      // B2: the same cut.  after_b2 continues behind the tail; the main stream goes on to the H MSM.  ts == 3: the
+      // tail on the high-priority aux stream (idle by now unless the H-query sort is late -- it then queues
+      // behind it), for when the H accumulation's grid keeps a normal-priority tail waiting for wave slots
+      hipStream_t qb = ts == 3 ? c->aux : c->red;
+      wait_for_b_view(c, s);
+      msm_accumulate<Fq2>(ch.sort_for_b(c), c->ptsB2, 0, *ch.work2, 0, s, tm);
+      msm_reduce_head<Fq2>(ch.sort_for_b(c), *ch.work2, 0, 1, s, tm);
+      G16_HIP(hipEventRecord(c->ev_b2, s));
+      G16_HIP(hipStreamWaitEvent(qb, c->ev_b2, 0));
+      msm_reduce_tail<Fq2>(ch.sort_for_b(c), *ch.work2, 0, 1, &S->B2, qb, tm, false, ps);
+      if (qb != c->red) {
+        G16_HIP(hipEventRecord(c->ev_b2, qb));
+        G16_HIP(hipStreamWaitEvent(c->red, c->ev_b2, 0));
+      }
+      after_b2();
+      G16_HIP(hipEventRecord(c->ev_b2, c->red));
+      G16_HIP(hipStreamWaitEvent(c->side, c->ev_b2, 0));  // the side stream joins it: one event to wait on
+      G16_HIP(hipEventRecord(c->ev_side, c->side));
+      return;
+    }
   }
   // B2: accumulate here; with small bucket sets its reduction (a latency-bound chain of Fq2 point
   // additions) runs on its own stream underneath the H MSM -- with large ones it only takes VALU
@@ -326,7 +381,8 @@ void enqueue_witness_msms(g16_ctx* c, const BucketChunk& ch, Hook after_ab, Hook
   G16_HIP(hipStreamWaitEvent(rs, c->ev_b2, 0));
   msm_reduce<Fq2>(ch.sort_for_b(c), *ch.work2, 0, 1, &S->B2, rs, tm, false, ps);
   // what only needs the B2 sum continues on the `red` stream (never on the main stream: it is a
-  // single-lane chain)
+  // single-lane chain).  `red` also carries the tails of a large proof's A | B1 and L reductions: this record
+  // is behind them
   G16_HIP(hipEventRecord(c->ev_b2, rs));
   if (rs != c->red) G16_HIP(hipStreamWaitEvent(c->red, c->ev_b2, 0));
   after_b2();

@@ -9,6 +9,10 @@
 //   stored y                    :  limbs 0..7 in [-8, 2^29 + 8), |value| < 3 p
 //   stored zz, zzz              :  M class
 //
+// The Fq2 squarings (F29x2::sqr, (c0 + c1)(c0 - c1)) multiply the carried SUM of the two components by their
+// difference: with stored-class components that is limbs within [-4, 2^29 + 4) against +-(2^30 + 16), and
+// values |c0^2 - c1^2| <= max(|c0|, |c1|)^2 < 100 p^2 for the Pp and R below -- the classes are unchanged.
+//
 // Every formula below lists the classes it produces; F29_CHECK (emulator build) asserts the
 // column and value bounds on every product actually formed in the test-suite.
 // The point at infinity is the exact all-zero limb pattern of zz (a valid zz is != 0 mod p, so it

@@ -608,7 +608,14 @@ struct F29x2 {
   friend G16_HD F29x2 operator*(const F29x2& a, const F29x2& b) {
     return F29x2{B::mul_sub(a.c0, b.c0, a.c1, b.c1), B::mul2(a.c0, b.c1, a.c1, b.c0)};
   }
-  G16_HD F29x2 sqr() const { return F29x2{B::mul_sub(c0, c0, c1, c1), c0.dbl() * c1}; }
+  // Complex squaring: c0' = (c0 + c1)(c0 - c1), c1' = 2 c0 c1 -- two products of 81 limb multiply-adds each where
+  // c0^2 - c1^2 as a merged mul_sub took 162 for c0' alone.
+  // Values: |c0 + c1| |c0 - c1| = |c0^2 - c1^2| <= max(|c0|, |c1|)^2, so whatever met the old demand
+  // (|c0|^2 + |c1|^2 < 169 p^2) meets this one, and the result is in (-p, 2p) as before.
+  // Limbs: callers hold components within +-(2^29 + 8) (ec29.h: Pp, R), so sum and difference reach 2^30 + 16 --
+  // too wide for BOTH sides of a product (9 x 2^60 > 2^62.9).  The sum is carried (27 cheap 32-bit operations):
+  // limbs 0..7 back in [-4, 2^29 + 4), columns below 9 x 2^59.01.
+  G16_HD F29x2 sqr() const { return F29x2{(c0 + c1).carry() * (c0 - c1), c0.dbl() * c1}; }
   // a b - c d; components carried (two separate reductions per component would overflow the
   // 64-bit columns if merged: 36 products)
   static G16_HD F29x2 mul_sub(const F29x2& a, const F29x2& b, const F29x2& c, const F29x2& d) {

@@ -280,6 +280,18 @@ void msm_fixup_pair(const MsmSort& s, const MsmPoints<F>& a, const MsmPoints<F>&
 template <class F>
 void msm_reduce(const MsmSort& s, MsmWork<F>& work, int first_slot, int nbatch, MsmAcc<F>* out_dev,
                 hipStream_t stream, StageTimer* tm = nullptr, bool hidden = false, size_t out_stride = 0);
+// The two halves of msm_reduce, for a caller that keeps the throughput-bound part on the stream that accumulates
+// and lets the latency-bound part finish elsewhere.  head: k_combine_large + k_bucket_reduce, reads the slots'
+// partial sums and writes their `contrib`.  tail: the k_set_sum tree + k_horner, reads `contrib`, goes through
+// `bsum` / `wsum` of first_slot and writes out_dev.  Same (first_slot, nbatch, hidden) for both; the caller orders
+// the tail behind the head, and the next head that writes the same slot's `contrib` behind this tail.  Each
+// half is its own ST_MSM_REDUCE interval on its own stream.
+template <class F>
+void msm_reduce_head(const MsmSort& s, MsmWork<F>& work, int first_slot, int nbatch, hipStream_t stream,
+                     StageTimer* tm = nullptr, bool hidden = false);
+template <class F>
+void msm_reduce_tail(const MsmSort& s, MsmWork<F>& work, int first_slot, int nbatch, MsmAcc<F>* out_dev,
+                     hipStream_t stream, StageTimer* tm = nullptr, bool hidden = false, size_t out_stride = 0);
 // contributions (MsmWork::ncontrib) that msm_reduce needs for any chunk of <= nproof_cap proofs and <= 3 MSMs
 inline uint32_t msm_contrib_cap(const MsmConfig& cfg, uint32_t nproof_cap) {
   uint32_t m = 1;

@@ -694,49 +694,86 @@ void msm_fixup_pair(const MsmSort& s, const MsmPoints<F>& A, const MsmPoints<F>&
 // whatever the size), so MSMs sharing a sort pay it once.  out_dev: nbatch consecutive sums.
 // A chunk sort (s.nproof proofs) is reduced as nproof D bucket sets -- proof z's sets are z D .. z D + D - 1
 // (MsmSort: bucket z nb + set B + digit) -- and k_horner folds each proof's D sets into out_dev + z out_stride.
+//
+// Two halves (msm.h): the HEAD (k_combine_large + k_bucket_reduce) is the throughput-bound part, partial ->
+// contrib; the TAIL (two k_set_sum levels + k_horner) is a handful of workgroups in a dependent chain,
+// contrib -> bsum -> wsum -> out_dev.  Both derive the same geometry from (sort, workspace, nbatch, hidden).
+namespace {
+template <class F>
+struct ReducePlan {
+  uint32_t nb, sets, lanes, red_chunk, cps, nchunks, nblk;
+  const uint32_t* rng;  // bucket-range sharding: this rank's run of the bucket set
+  MsmAcc<F>*partial, *contrib, *bsum, *wsum;
+};
+template <class F>
+ReducePlan<F> reduce_plan(const MsmSort& s, MsmWork<F>& work, int first_slot, int nbatch, bool hidden) {
+  const MsmConfig& cfg = s.cfg;
+  if (first_slot < 0 || nbatch < 1 || first_slot + nbatch > work.batch)
+    throw std::runtime_error("msm_reduce: bad workspace slots");
+  ReducePlan<F> p;
+  p.nb = s.nbt();  // a chunk sort: the buckets of every proof
+  p.sets = (uint32_t)cfg.D * s.nproof;
+  p.lanes = s.lanes_of(sizeof(F) != sizeof(Fq));
+  p.rng = s.range_dev();
+  // buckets per thread: the running sums are a dependent chain of EC additions (~10 us each on
+  // one lane): see msm_red_chunk for the thread count this aims at
+  p.red_chunk = msm_red_chunk(cfg, (uint32_t)nbatch * s.nproof, (uint32_t)s.world, hidden);
+  p.cps = ceil_div(cfg.B, p.red_chunk);
+  p.nchunks = p.cps * p.sets;
+  if (p.nchunks > work.ncontrib) throw std::runtime_error("msm_reduce: contribution buffer too small");
+  if ((int)p.sets > work.sets) throw std::runtime_error("msm_reduce: more bucket sets than the workspace holds");
+  // two-level tree: cps contributions -> nblk block sums -> 1 per set
+  p.nblk = ceil_div(p.cps / (uint32_t)s.world, SUM_THREADS * 2);
+  if (p.nblk > 256) p.nblk = 256;
+  if (p.nblk < 1) p.nblk = 1;
+  p.partial = work.partial.p + (size_t)first_slot * work.slots;
+  // the scratch of slot k starts at k * (its per-slot size): reductions of DIFFERENT slots may run on different
+  // streams at the same time (round 6: the L reduction of a mid-sized proof runs on the side stream)
+  p.contrib = work.contrib.p + (size_t)first_slot * work.ncontrib;
+  p.bsum = work.bsum.p + (size_t)first_slot * 256 * work.sets;
+  p.wsum = work.wsum.p + (size_t)first_slot * work.sets;
+  return p;
+}
+}  // namespace
+
+template <class F>
+void msm_reduce_head(const MsmSort& s, MsmWork<F>& work, int first_slot, int nbatch, hipStream_t stream,
+                     StageTimer* tm, bool hidden) {
+  const ReducePlan<F> p = reduce_plan<F>(s, work, first_slot, nbatch, hidden);
+  const bool g2 = sizeof(F) != sizeof(Fq);
+  int id = tm ? tm->begin(ST_MSM_REDUCE, stream) : -1;
+  G16_LAUNCH((k_combine_large<F>), dim3(1024, nbatch), COMB_THREADS, COMB_THREADS * sizeof(MsmAcc<F>),
+             stream, s.large_list(g2), s.large_meta(g2),
+             (const uint32_t*)s.offset.p, p.nb, p.lanes, p.partial, (size_t)work.slots);
+  G16_LAUNCH((k_bucket_reduce<F>), dim3(ceil_div(p.nchunks, 64), nbatch), 64, 0, stream,
+             (const MsmAcc<F>*)p.partial, (const uint32_t*)s.offset.p, p.nb, p.lanes, s.cfg.B, p.red_chunk,
+             p.cps, p.nchunks, p.contrib, (size_t)work.slots, p.rng);
+  if (tm) tm->end(id, stream);
+}
+
+template <class F>
+void msm_reduce_tail(const MsmSort& s, MsmWork<F>& work, int first_slot, int nbatch, MsmAcc<F>* out_dev,
+                     hipStream_t stream, StageTimer* tm, bool hidden, size_t out_stride) {
+  const ReducePlan<F> p = reduce_plan<F>(s, work, first_slot, nbatch, hidden);
+  int id = tm ? tm->begin(ST_MSM_REDUCE, stream) : -1;
+  G16_LAUNCH((k_set_sum<F>), dim3(p.sets * p.nblk, nbatch), SUM_THREADS,
+             SUM_THREADS * sizeof(MsmAcc<F>), stream, (const MsmAcc<F>*)p.contrib, p.cps, p.nblk,
+             p.bsum, (size_t)p.nchunks, (size_t)256 * work.sets, p.rng, p.red_chunk);
+  G16_LAUNCH((k_set_sum<F>), dim3(p.sets, nbatch), SUM_THREADS,
+             SUM_THREADS * sizeof(MsmAcc<F>), stream, (const MsmAcc<F>*)p.bsum, p.nblk, 1u,
+             p.wsum, (size_t)256 * work.sets, (size_t)work.sets, (const uint32_t*)nullptr, 1u);
+  G16_LAUNCH((k_horner<F>), dim3(nbatch, s.nproof), 64, 0, stream, (const MsmAcc<F>*)p.wsum, work.sets, s.cfg.D,
+             s.cfg.c, out_dev, out_stride);
+  if (tm) tm->end(id, stream);
+}
+
+// head, then tail, on one stream: ONE ST_MSM_REDUCE interval over both
 template <class F>
 void msm_reduce(const MsmSort& s, MsmWork<F>& work, int first_slot, int nbatch, MsmAcc<F>* out_dev,
                 hipStream_t stream, StageTimer* tm, bool hidden, size_t out_stride) {
-  const MsmConfig& cfg = s.cfg;
-  const uint32_t nb = s.nbt();  // a chunk sort: the buckets of every proof
-  const uint32_t sets = (uint32_t)cfg.D * s.nproof;
-  if (first_slot < 0 || nbatch < 1 || first_slot + nbatch > work.batch)
-    throw std::runtime_error("msm_reduce: bad workspace slots");
-  MsmAcc<F>* partial = work.partial.p + (size_t)first_slot * work.slots;
   int id = tm ? tm->begin(ST_MSM_REDUCE, stream) : -1;
-  const bool g2 = sizeof(F) != sizeof(Fq);
-  const uint32_t lanes = s.lanes_of(g2);
-  G16_LAUNCH((k_combine_large<F>), dim3(1024, nbatch), COMB_THREADS, COMB_THREADS * sizeof(MsmAcc<F>),
-             stream, s.large_list(g2), s.large_meta(g2),
-             (const uint32_t*)s.offset.p, nb, lanes, partial, (size_t)work.slots);
-  // buckets per thread: the running sums are a dependent chain of EC additions (~10 us each on
-  // one lane): see msm_red_chunk for the thread count this aims at
-  const uint32_t* rng = s.range_dev();  // bucket-range sharding: this rank's run of the bucket set
-  const uint32_t red_chunk = msm_red_chunk(cfg, (uint32_t)nbatch * s.nproof, (uint32_t)s.world, hidden);
-  const uint32_t cps = ceil_div(cfg.B, red_chunk);
-  const uint32_t nchunks = cps * sets;
-  if (nchunks > work.ncontrib) throw std::runtime_error("msm_reduce: contribution buffer too small");
-  if ((int)sets > work.sets) throw std::runtime_error("msm_reduce: more bucket sets than the workspace holds");
-  // the scratch of slot k starts at k * (its per-slot size): reductions of DIFFERENT slots may run on different
-  // streams at the same time (round 6: the L reduction of a mid-sized proof runs on the side stream)
-  MsmAcc<F>* contrib = work.contrib.p + (size_t)first_slot * work.ncontrib;
-  MsmAcc<F>* bsum = work.bsum.p + (size_t)first_slot * 256 * work.sets;
-  MsmAcc<F>* wsum = work.wsum.p + (size_t)first_slot * work.sets;
-  G16_LAUNCH((k_bucket_reduce<F>), dim3(ceil_div(nchunks, 64), nbatch), 64, 0, stream,
-             (const MsmAcc<F>*)partial, (const uint32_t*)s.offset.p, nb, lanes, cfg.B, red_chunk,
-             cps, nchunks, contrib, (size_t)work.slots, rng);
-  // two-level tree: cps contributions -> nblk block sums -> 1 per set
-  uint32_t nblk = ceil_div(cps / (uint32_t)s.world, SUM_THREADS * 2);
-  if (nblk > 256) nblk = 256;
-  if (nblk < 1) nblk = 1;
-  G16_LAUNCH((k_set_sum<F>), dim3(sets * nblk, nbatch), SUM_THREADS,
-             SUM_THREADS * sizeof(MsmAcc<F>), stream, (const MsmAcc<F>*)contrib, cps, nblk,
-             bsum, (size_t)nchunks, (size_t)256 * work.sets, rng, red_chunk);
-  G16_LAUNCH((k_set_sum<F>), dim3(sets, nbatch), SUM_THREADS,
-             SUM_THREADS * sizeof(MsmAcc<F>), stream, (const MsmAcc<F>*)bsum, nblk, 1u,
-             wsum, (size_t)256 * work.sets, (size_t)work.sets, (const uint32_t*)nullptr, 1u);
-  G16_LAUNCH((k_horner<F>), dim3(nbatch, s.nproof), 64, 0, stream, (const MsmAcc<F>*)wsum, work.sets, cfg.D,
-             cfg.c, out_dev, out_stride);
+  msm_reduce_head<F>(s, work, first_slot, nbatch, stream, nullptr, hidden);
+  msm_reduce_tail<F>(s, work, first_slot, nbatch, out_dev, stream, nullptr, hidden, out_stride);
   if (tm) tm->end(id, stream);
 }
 

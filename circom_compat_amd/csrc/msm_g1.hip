@@ -14,4 +14,7 @@ template void msm_fixup_pair<Fq>(const MsmSort&, const MsmPoints<Fq>&, const Msm
                                  hipStream_t, StageTimer*);
 template void msm_reduce<Fq>(const MsmSort&, MsmWork<Fq>&, int, int, MsmAcc<Fq>*, hipStream_t,
                              StageTimer*, bool, size_t);
+template void msm_reduce_head<Fq>(const MsmSort&, MsmWork<Fq>&, int, int, hipStream_t, StageTimer*, bool);
+template void msm_reduce_tail<Fq>(const MsmSort&, MsmWork<Fq>&, int, int, MsmAcc<Fq>*, hipStream_t,
+                                  StageTimer*, bool, size_t);
 }  // namespace g16

@@ -10,4 +10,7 @@ template void msm_accumulate<Fq2>(const MsmSort&, const MsmPoints<Fq2>&, uint32_
 template void msm_fixup<Fq2>(const MsmSort&, const MsmPoints<Fq2>&, uint32_t, MsmWork<Fq2>&, int, hipStream_t, StageTimer*);
 template void msm_reduce<Fq2>(const MsmSort&, MsmWork<Fq2>&, int, int, MsmAcc<Fq2>*, hipStream_t,
                              StageTimer*, bool, size_t);
+template void msm_reduce_head<Fq2>(const MsmSort&, MsmWork<Fq2>&, int, int, hipStream_t, StageTimer*, bool);
+template void msm_reduce_tail<Fq2>(const MsmSort&, MsmWork<Fq2>&, int, int, MsmAcc<Fq2>*, hipStream_t,
+                                  StageTimer*, bool, size_t);
 }  // namespace g16
