@@ -18,8 +18,10 @@
 // src/zkey.rs:320-332) is converted at the edges by from_mont256 / to_mont256.
 //
 // Contract of mul / sqr (checked by the emulator build, see F29_CHECK):
-//   inputs : sum_i |a.l[i]| * |b.l[k-i]| < 2^62.9 for every column k   (e.g. all |limbs| <= 2^30 on
-//            one side and <= 2^29.5 on the other), |value(a) * value(b)| < 169 p^2;
+//   inputs : sum_i |a.l[i]| * |b.l[k-i]| < 2^63 - 9 * 2^58 - 2^36 = 2^62.5 for every column k: the
+//            reduction adds up to 9 terms m_i p_j < 2^58 and the carry to the same 64-bit column
+//            (e.g. all |limbs| <= 2^30 + 2^4 on one side and <= 2^29 + 2^4 on the other: 9 * 2^59),
+//            |value(a) * value(b)| < 169 p^2  (168.9 p^2 is what keeps the output below 2p);
 //   output : limbs 0..7 in [0, 2^29), |top limb| < 2^24, value in (-p, 2p).
 // carry() renormalises limbs (not values) after a few additions: limbs 0..7 end in [-8, 2^29 + 8).
 #pragma once

@@ -1,10 +1,14 @@
-"""field.h / ec.h (the device arithmetic source) compiled for the host vs the oracle.
+"""field.h / ec.h (the device arithmetic source) vs the oracle, one operation per kernel thread.
 
-Not a GPU parity claim: this pins the *source* of the device arithmetic, bit for bit, before any
-kernel runs.  The same vectors run on the real GPU in test_gpu_parity.py.
+The emulator legs (test_*) run the host loops of tests/emu/emu_exports.cpp and pin the *source* of the device
+arithmetic, bit for bit.  The same operation sets are kernels in tests/arith/arith_hooks.hip: test_*_hooks_emu runs
+the same vectors through them on the emulator, test_*_gpu through their gfx950 build,
+tests/arith/libg16_arith_gpu.so.
 """
 import ctypes as C
+import os
 import random
+import types
 
 import numpy as np
 import pytest
@@ -24,13 +28,35 @@ def _unmont(arr, p):
     return [int.from_bytes(b[i:i + 32], "little") * ri % p for i in range(0, len(b), 32)]
 
 
+@pytest.fixture(scope="module")
+def arith_gpu():
+    """the hipcc build of the hooks, made by the default make target: missing is a failure, nothing compiles here"""
+    so = os.path.join(os.path.dirname(os.path.abspath(__file__)), "arith", "libg16_arith_gpu.so")
+    if not os.path.exists(so):
+        pytest.fail(f"{so} is not built (make -C circom_compat_amd/csrc)")
+    return types.SimpleNamespace(L=C.CDLL(so))
+
+
+def _entry(lib, name, argtypes):
+    """emu_*: the host loops of tests/emu/emu_exports.cpp (no status); arith_*: the kernels, which return one"""
+    fn = getattr(lib.L, name)
+    fn.argtypes = argtypes
+    if name.startswith("emu_"):
+        fn.restype = None
+        return fn
+    fn.restype = C.c_int
+
+    def checked(*args):
+        assert fn(*args) == 0, name
+    return checked
+
+
 def _edge(p, rng, n):
     base = [0, 1, 2, p - 1, p - 2, (p - 1) // 2, (1 << 253) % p, (1 << 32) - 1, (1 << 64) - 1, R % p, (R * R) % p]
     return base + [rng.randrange(p) for _ in range(n)]
 
 
-@pytest.mark.parametrize("field", [0, 1])
-def test_fp_ops(emu, field):
+def _fp_ops(emu, field, prefix="emu_"):
     p = o.R_MOD if field == 0 else o.Q_MOD
     rng = random.Random(100 + field)
     xs = _edge(p, rng, 300)
@@ -38,8 +64,8 @@ def test_fp_ops(emu, field):
     n = len(xs)
     a, b = _mont(xs, p), _mont(ys, p)
     out = np.empty_like(a)
-    f = emu.L.emu_fp_op
-    f.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+    f = _entry(emu, prefix + "fp_op", [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t])
+
     ops = {0: lambda x, y: x * y % p, 1: lambda x, y: (x + y) % p, 2: lambda x, y: (x - y) % p,
            3: lambda x, y: (-x) % p, 5: lambda x, y: x * x % p, 8: lambda x, y: 2 * x % p,
            4: lambda x, y: pow(x, p - 2, p)}
@@ -56,7 +82,18 @@ def test_fp_ops(emu, field):
     assert _unmont(out, p) == xs
 
 
-def test_fq2_ops(emu):
+@pytest.mark.parametrize("field", [0, 1])
+def test_fp_ops(emu, field):
+    _fp_ops(emu, field)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("field", [0, 1])
+def test_fp_ops_gpu(arith_gpu, field):
+    _fp_ops(arith_gpu, field, "arith_")
+
+
+def _fq2_ops(emu, prefix="emu_"):
     rng = random.Random(7)
     p = o.Q_MOD
     n = 100
@@ -66,8 +103,8 @@ def test_fq2_ops(emu):
     flat = lambda zs: _mont([c for z in zs for c in z], p)
     a, b = flat(xs), flat(ys)
     out = np.empty_like(a)
-    f = emu.L.emu_fq2_op
-    f.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+    f = _entry(emu, prefix + "fq2_op", [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t])
+
     refs = {0: o.f2_mul, 1: o.f2_add, 2: o.f2_sub, 3: lambda x, y: o.f2_neg(x), 5: lambda x, y: o.f2_sqr(x)}
     for op, ref in refs.items():
         f(op, a.ctypes.data, b.ctypes.data, out.ctypes.data, n)
@@ -82,7 +119,16 @@ def test_fq2_ops(emu):
     assert [(got[2 * i], got[2 * i + 1]) for i in range(len(nz))] == [o.f2_inv(x) for x in nz]
 
 
-def _ec_case(emu, g2):
+def test_fq2_ops(emu):
+    _fq2_ops(emu)
+
+
+@pytest.mark.gpu
+def test_fq2_ops_gpu(arith_gpu):
+    _fq2_ops(arith_gpu, "arith_")
+
+
+def _ec_case(emu, g2, prefix="emu_"):
     rng = random.Random(11 + g2)
     Cv = o.G2 if g2 else o.G1
     gen = o.G2_GEN if g2 else o.G1_GEN
@@ -90,8 +136,7 @@ def _ec_case(emu, g2):
     from_b = o.g2_from_bytes if g2 else o.g1_from_bytes
     ps = 128 if g2 else 64
     fs = 64 if g2 else 32
-    f = emu.L.emu_g2_op if g2 else emu.L.emu_g1_op
-    f.argtypes = [C.c_int] + [C.c_void_p] * 6 + [C.c_size_t]
+    f = _entry(emu, prefix + ("g2_op" if g2 else "g1_op"), [C.c_int] + [C.c_void_p] * 6 + [C.c_size_t])
     n = 24
     P = [Cv.mul(gen, rng.randrange(1, o.R_MOD)) for _ in range(n)]
     Q = [Cv.mul(gen, rng.randrange(1, o.R_MOD)) for _ in range(n)]
@@ -135,3 +180,24 @@ def test_g1_ops(emu):
 
 def test_g2_ops(emu):
     _ec_case(emu, 1)
+
+
+@pytest.mark.gpu
+def test_g1_ops_gpu(arith_gpu):
+    _ec_case(arith_gpu, 0, "arith_")
+
+
+@pytest.mark.gpu
+def test_g2_ops_gpu(arith_gpu):
+    _ec_case(arith_gpu, 1, "arith_")
+
+
+def test_field_hooks_emu(emu):
+    for field in (0, 1):
+        _fp_ops(emu, field, "arith_")
+    _fq2_ops(emu, "arith_")
+
+
+@pytest.mark.parametrize("g2", [0, 1])
+def test_curve_hooks_emu(emu, g2):
+    _ec_case(emu, g2, "arith_")
