@@ -39,7 +39,7 @@ __all__ = ["read_zkey", "R1CSFile", "R1CS", "CircomCircuit", "CircomBuilder", "C
            "trapdoor_setup", "Csr", "write_zkey", "device_tensor", "verify_batch", "verify_aggregate",
            "verify_batch_fast", "check_key", "KeyReport", "contribute_key", "check_contribution",
            "ContributionReport", "Srs", "trapdoor_srs", "setup_from_srs", "check_key_circuit",
-           "CircuitBindingReport", "read_ptau", "write_ptau", "check_srs", "SrsReport"]
+           "CircuitBindingReport", "read_ptau", "write_ptau", "check_srs", "SrsReport", "contribute_srs", "new_srs"]
 
 FR_MODULUS = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 
@@ -969,6 +969,59 @@ def check_srs(srs: Srs, rho=None, device=0, max_listed=64, lib: Optional[B.Libra
     if st != B.G16_OK:
         raise G16Error(st, "g16_srs_check failed")
     return SrsReport(rep, bad[:rep.n_listed])
+
+
+def new_srs(log2_domain: int, device=0, lib: Optional[B.Library] = None) -> Srs:
+    """The string of `snarkjs powersoftau new`: every entry a generator (tau = alpha = beta = 1), byte for byte
+    trapdoor_srs(log2_domain, (1, 1, 1)).  It is the start of a ceremony, not a usable SRS: contribute_srs
+    re-randomises it."""
+    return trapdoor_srs(log2_domain, (1, 1, 1), device=device, lib=lib)
+
+
+def contribute_srs(srs: Srs, secrets=None, device=0, lib: Optional[B.Library] = None) -> Srs:
+    """One powers-of-tau contribution on the GPU (g16_srs_contribute), the point arithmetic of `snarkjs powersoftau
+    contribute`: tau_g1[i] and tau_g2[i] times t^i, alpha_tau_g1[i] times a t^i, beta_tau_g1[i] times b t^i and
+    beta_g2 times b -- the string of (tau, alpha, beta) becomes the string of (tau t, alpha a, beta b).  Returns a
+    NEW Srs with its own arrays (len(srs.tau_g1) and the n_tau of srs.to_c() entries); srs is not written;
+    power / ceremony_power are carried over.  secrets: (t, a, b) as ints in [1, r), or None: drawn by the library
+    from the OS CSPRNG, never returned and wiped before the call returns.
+    The .ptau contribution transcript (challenge hashes, proofs of knowledge of t, a, b, beacon mode) is NOT
+    produced, and nothing proves that the result was derived from srs: without the transcript any consistent
+    string is a rescaling of any other.  check_srs on the result is the whole of what the points alone can tell."""
+    lib = lib or B.load()
+    d = srs.to_c()
+    sec = None
+    if secrets is not None:
+        secrets = [int(x) for x in secrets]
+        if len(secrets) != 3:
+            raise G16Error(B.G16_ERR_INVALID, "secrets = (t, a, b)")
+        if any(not 0 < x < FR_MODULUS for x in secrets):
+            raise G16Error(B.G16_ERR_INVALID, "t, a and b are integers in [1, r)")
+        sec = fr_from_ints(secrets, lib)
+    tau_g1 = np.empty((d.n_tau_g1, 64), dtype=np.uint8)
+    tau_g2 = np.empty((d.n_tau, 128), dtype=np.uint8)
+    alpha = np.empty((d.n_tau, 64), dtype=np.uint8)
+    beta = np.empty((d.n_tau, 64), dtype=np.uint8)
+    beta_g2 = (C.c_uint8 * 128)()
+    st = lib.g16_srs_contribute(device, C.byref(d), _np_ptr(sec) if sec is not None else None, _np_ptr(tau_g1),
+                                _np_ptr(tau_g2), _np_ptr(alpha), _np_ptr(beta), beta_g2)
+    if st != B.G16_OK:
+        raise G16Error(st, "g16_srs_contribute failed")
+    out = Srs(tau_g1, tau_g2, alpha, beta, bytes(beta_g2))
+    out.power, out.ceremony_power = srs.power, srs.ceremony_power
+    return out
+
+
+SRS_CONTRIBUTE_PHASES = ("upload", "scalars", "mul_g1", "mul_g2", "affine", "download")
+
+
+def contribute_srs_times(lib: Optional[B.Library] = None) -> dict:
+    """milliseconds of device time per phase of this thread's last contribute_srs, summed over the chunks
+    (g16_srs_contribute_times); the copies run under the kernels, so the sum exceeds the wall time"""
+    lib = lib or B.load()
+    ms = (C.c_float * len(SRS_CONTRIBUTE_PHASES))()
+    lib.check(lib.g16_srs_contribute_times(ms, len(SRS_CONTRIBUTE_PHASES)))
+    return dict(zip(SRS_CONTRIBUTE_PHASES, (float(x) for x in ms)))
 
 
 SETUP_SRS_PHASES = ("upload", "ntt_g1", "ntt_g2", "ntt_h", "affine", "combine", "download")

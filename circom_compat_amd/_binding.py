@@ -158,7 +158,7 @@ ABI_SYMBOLS = [
     "g16_key_check", "g16_key_contribute", "g16_key_contribution_check",
     "g16_srs_create", "g16_srs_desc_of", "g16_srs_destroy", "g16_setup_from_srs", "g16_setup_from_srs_times",
     "g16_srs_check", "g16_ptau_open", "g16_ptau_open_mem", "g16_ptau_close", "g16_ptau_header_get", "g16_ptau_srs",
-    "g16_ptau_write",
+    "g16_ptau_write", "g16_srs_contribute", "g16_srs_contribute_times",
 ]
 
 
@@ -273,6 +273,8 @@ class Library:
             "g16_setup_from_srs_times": (C.c_int, [C.POINTER(C.c_float), C.c_uint32]),
             "g16_srs_check": (C.c_int, [C.c_int, C.POINTER(SrsDesc), vp, C.POINTER(KeyBadPoint), C.c_uint32,
                                         C.POINTER(SrsReportC)]),
+            "g16_srs_contribute": (C.c_int, [C.c_int, C.POINTER(SrsDesc), vp, vp, vp, vp, vp, vp]),
+            "g16_srs_contribute_times": (C.c_int, [C.POINTER(C.c_float), C.c_uint32]),
             "g16_ptau_open": (C.c_int, [C.c_char_p, C.POINTER(vp)]),
             "g16_ptau_open_mem": (C.c_int, [vp, C.c_size_t, C.POINTER(vp)]),
             "g16_ptau_close": (None, [vp]),

@@ -663,6 +663,50 @@ typedef struct {
 g16_status g16_srs_check(int device, const g16_srs_desc* srs, const uint64_t* rho /* NULL = CSPRNG */,
                          g16_key_bad_point* bad_out, uint32_t bad_cap, g16_srs_report* report);
 
+/* ---- powers-of-tau contributions (not on the proving path) ---------------------------------------- */
+/* g16_srs_contribute is the point arithmetic of `snarkjs powersoftau contribute` on the GPU: every entry of an
+ * existing string is multiplied through by fresh secrets t, a, b, so that the string of (tau, alpha, beta)
+ * becomes the string of (tau t, alpha a, beta b) and nobody knows the product:
+ *   tau_g1'[i] = t^i tau_g1[i]              tau_g2'[i] = t^i tau_g2[i]
+ *   alpha_tau_g1'[i] = a t^i alpha_tau_g1[i]   beta_tau_g1'[i] = b t^i beta_tau_g1[i]   beta_g2' = b beta_g2
+ * Applied to the string whose every entry is a generator (g16_srs_create with toxic = (1, 1, 1)) it is
+ * `powersoftau new` followed by the first contribution.  Canonical affine encodings are unique: the result
+ * is, byte for byte, what g16_srs_create mints for (tau t, alpha a, beta b).  ALL n_tau_g1 / n_tau entries handed
+ * over are multiplied.  Standalone like g16_key_contribute: no ctx is needed, a ctx alive on the device is
+ * left untouched.  No atomics: the same bytes on every run.
+ *
+ * secrets: t, a, b as 3 x 4 u64 Montgomery Fr, each in [1, r) (zero or a non-canonical value:
+ *          G16_ERR_INVALID), or NULL: the three are drawn from the operating system's CSPRNG, never returned, and
+ *          wiped on the host and on the device before the call returns (a failure to get randomness is
+ *          G16_ERR_INTERNAL, never a fixed fallback).
+ * Outputs: tau_g1_out n_tau_g1 x 64 bytes, tau_g2_out n_tau x 128, alpha_tau_g1_out / beta_tau_g1_out
+ *          n_tau x 64, beta_g2_out 128.  Each may be exactly the matching input array (in place); any other
+ *          overlap is unsupported.  A NULL pointer, n_tau_g1 == 0 or n_tau == 0: G16_ERR_INVALID, and nothing is
+ *          written.
+ * The all-zero encoding (infinity) stays all-zero.  A point off the curve is multiplied like any other and means
+ * nothing afterwards: run g16_srs_check first on a string that was not minted locally.
+ *
+ * Every point has its own full-width scalar c t^i.  The scalars of a chunk are generated on the device; one lane
+ * per point then walks the 256 bit positions with a doubling at each and a mixed addition of the affine point
+ * predicated on the lane's own bit, and one shared inversion per 8 points brings the chunk back to affine.
+ * Memory: the arrays are streamed through two page-locked host slots and two device slots of
+ * min(2^18, longest array) points, the copy of chunk k + 1 and the download of chunk k - 1 under the kernels of
+ * chunk k; device use does not grow with the SRS.  G16_SRSCONTRIB_CHUNK=<points> overrides the chunk (tests).
+ *
+ * NOT built: the section-7 transcript of a .ptau (the Blake2b challenge chain, the proofs of knowledge of
+ * t, a, b, beacon mode) is neither written nor verified.  Nothing here or in g16_srs_check proves that one
+ * string was derived from another: without the transcript any consistent string is a rescaling of any other.
+ * g16_srs_check on the result is the whole of what the points alone can tell.
+ *
+ * g16_srs_contribute_times: milliseconds of device time the calling thread's last g16_srs_contribute spent in
+ * 0 uploads, 1 scalar generation, 2 G1 multiplications, 3 G2 multiplications, 4 affine passes, 5 downloads,
+ * summed over the chunks (copies run under kernels, so the sum exceeds the wall time); entries from 6 on are 0. */
+g16_status g16_srs_contribute(int device, const g16_srs_desc* srs,
+                              const uint64_t* secrets /* 3 x 4 u64 Montgomery Fr: t, a, b; NULL = CSPRNG */,
+                              uint8_t* tau_g1_out, uint8_t* tau_g2_out, uint8_t* alpha_tau_g1_out,
+                              uint8_t* beta_tau_g1_out, uint8_t beta_g2_out[128]);
+g16_status g16_srs_contribute_times(float* ms, uint32_t cap);
+
 /* ---- loaders (host side, C++): see g16_loaders.h ---------------------------------------------- */
 
 #ifdef __cplusplus

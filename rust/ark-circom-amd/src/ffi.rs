@@ -306,6 +306,8 @@ extern "C" {
     pub fn g16_setup_from_srs(device: c_int, at: *const g16_csr, bt: *const g16_csr, ct: *const g16_csr, n_vars: u32, n_public: u32, num_constraints: u32, srs: *const g16_srs_desc, reduction: c_int, out: *mut *mut g16_setup) -> g16_status;
     pub fn g16_setup_from_srs_times(ms: *mut c_float, cap: u32) -> g16_status;
     pub fn g16_srs_check(device: c_int, srs: *const g16_srs_desc, rho: *const u64, bad_out: *mut g16_key_bad_point, bad_cap: u32, report: *mut g16_srs_report) -> g16_status;
+    pub fn g16_srs_contribute(device: c_int, srs: *const g16_srs_desc, secrets: *const u64, tau_g1_out: *mut u8, tau_g2_out: *mut u8, alpha_tau_g1_out: *mut u8, beta_tau_g1_out: *mut u8, beta_g2_out: *mut u8) -> g16_status;
+    pub fn g16_srs_contribute_times(ms: *mut c_float, cap: u32) -> g16_status;
 
     // ---- include/g16_loaders.h -----------------------------------------------------------------
     pub fn g16_loader_last_error() -> *const c_char;
