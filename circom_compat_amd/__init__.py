@@ -39,7 +39,9 @@ __all__ = ["read_zkey", "R1CSFile", "R1CS", "CircomCircuit", "CircomBuilder", "C
            "trapdoor_setup", "Csr", "write_zkey", "device_tensor", "verify_batch", "verify_aggregate",
            "verify_batch_fast", "check_key", "KeyReport", "contribute_key", "check_contribution",
            "ContributionReport", "Srs", "trapdoor_srs", "setup_from_srs", "check_key_circuit",
-           "CircuitBindingReport", "read_ptau", "write_ptau", "check_srs", "SrsReport", "contribute_srs", "new_srs"]
+           "CircuitBindingReport", "read_ptau", "write_ptau", "check_srs", "SrsReport", "contribute_srs", "new_srs",
+           "points_from_ark", "points_to_ark", "read_ark_key", "write_ark_key", "read_ark_vk", "write_ark_vk",
+           "proofs_from_ark", "proofs_to_ark", "ark_point_bytes"]
 
 FR_MODULUS = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 
@@ -393,6 +395,15 @@ class Proof:
 
     def __repr__(self):
         return f"Proof({self.raw.hex()[:32]}...)"
+
+    def to_ark(self, compressed=True, device=0, lib: Optional[B.Library] = None) -> bytes:
+        """Proof::serialize_compressed / serialize_uncompressed: 128 / 256 bytes (g16_ark_proofs_write)."""
+        return proofs_to_ark([self], compressed=compressed, device=device, lib=lib)
+
+    @staticmethod
+    def from_ark(raw, compressed=True, validate=True, device=0, lib: Optional[B.Library] = None) -> "Proof":
+        """Proof::deserialize_compressed / _uncompressed of one proof (g16_ark_proofs_read)."""
+        return proofs_from_ark(raw, 1, compressed=compressed, validate=validate, device=device, lib=lib)[0]
 
 
 DEFAULT_TABLES = 0     # g16_options.fixed_tables when Prover(tables=None): 0 = the library decides
@@ -1072,6 +1083,203 @@ def check_key_circuit(pk: "ProvingKey", a: Csr, b: Csr, c: Csr, srs: Srs, rho=No
         return CircuitBindingReport("gamma_g2")
     rep = check_contribution(fresh, pk, rho=rho, device=device, max_listed=max_listed, lib=lib)
     return CircuitBindingReport(None if rep.ok else "contribution", rep)
+
+
+# ---- arkworks serialization (include/g16_amd.h) ---------------------------------------------------------------
+def _ark_flags(compressed, validate=False) -> int:
+    return (B.ARK_COMPRESSED if compressed else 0) | (B.ARK_VALIDATE if validate else 0)
+
+
+def _ark_group(group) -> int:
+    g = {"g1": B.POINT_G1, "g2": B.POINT_G2}.get(group, group) if isinstance(group, str) else int(group)
+    if g not in (B.POINT_G1, B.POINT_G2):
+        raise G16Error(B.G16_ERR_INVALID, "group is 'g1' or 'g2'")
+    return g
+
+
+def ark_point_bytes(group, compressed=True) -> int:
+    """bytes of one ark-serialize'd point: G1 32 / 64, G2 64 / 128"""
+    return (64 if _ark_group(group) == B.POINT_G2 else 32) * (1 if compressed else 2)
+
+
+def _strided(data, n, rec, stride, what):
+    """(uint8 array, n) of n records of rec bytes, stride bytes apart (0 = dense)"""
+    buf = np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else \
+        np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    step = stride or rec
+    if step < rec:
+        raise G16Error(B.G16_ERR_INVALID, f"{what}: stride below the record size")
+    if n is None:
+        if stride not in (0, rec) or buf.shape[0] % rec:
+            raise G16Error(B.G16_ERR_INVALID, f"{what}: give n with a stride, or a whole number of records")
+        n = buf.shape[0] // rec
+    if n and buf.shape[0] < (n - 1) * step + rec:
+        raise G16Error(B.G16_ERR_INVALID, f"{what}: {buf.shape[0]} bytes do not hold {n} records")
+    return buf, n
+
+
+def points_from_ark(data, group, n=None, compressed=True, validate=True, in_stride=0, out_stride=0, out=None, device=0,
+                    lib: Optional[B.Library] = None):
+    """G1Affine / G2Affine::deserialize_with_mode of n points on the GPU (g16_points_from_ark): ark-serialize bytes ->
+    (points, reasons, n_bad).  points: the packed Montgomery records of the rest of the package ((n, 64 | 128) uint8,
+    or `out` / a flat array when out_stride is given); reasons: n bytes, 0 or the FIRST failed test (B.KEY_BAD_*:
+    ENCODING, NONCANONICAL, OFF_CURVE, SUBGROUP with validate on G2); a bad point's record is all-zero."""
+    lib = lib or B.load()
+    g = _ark_group(group)
+    rec_in, rec_out = ark_point_bytes(g, compressed), 128 if g == B.POINT_G2 else 64
+    buf, n = _strided(data, n, rec_in, in_stride, "points_from_ark")
+    step = out_stride or rec_out
+    if step < rec_out:
+        raise G16Error(B.G16_ERR_INVALID, "points_from_ark: out_stride below the record size")
+    if out is None:
+        out = np.zeros((n, rec_out) if step == rec_out else (max(n, 1) - 1) * step + rec_out, dtype=np.uint8)
+    elif out.dtype != np.uint8 or not out.flags.c_contiguous or (n and out.size < (n - 1) * step + rec_out):
+        raise G16Error(B.G16_ERR_INVALID, "points_from_ark: out must be a contiguous uint8 array that holds n records")
+    why = np.zeros(n, dtype=np.uint8)
+    bad = C.c_uint64()
+    st = lib.g16_points_from_ark(device, g, _ark_flags(compressed, validate), _np_ptr(buf), in_stride, n, _np_ptr(out),
+                                 out_stride, _np_ptr(why), C.byref(bad))
+    if st != B.G16_OK:
+        raise G16Error(st, "g16_points_from_ark failed")
+    return out, why, bad.value
+
+
+def points_to_ark(points, group, n=None, compressed=True, in_stride=0, out_stride=0, out=None, device=0,
+                  lib: Optional[B.Library] = None):
+    """serialize_with_mode of n packed points on the GPU (g16_points_to_ark) -> uint8 array of ark-serialize records.
+    The points are not tested for the curve; a stored word >= q raises G16Error (status G16_ERR_INVALID)."""
+    lib = lib or B.load()
+    g = _ark_group(group)
+    rec_in, rec_out = 128 if g == B.POINT_G2 else 64, ark_point_bytes(g, compressed)
+    buf, n = _strided(points, n, rec_in, in_stride, "points_to_ark")
+    step = out_stride or rec_out
+    if step < rec_out:
+        raise G16Error(B.G16_ERR_INVALID, "points_to_ark: out_stride below the record size")
+    if out is None:
+        out = np.zeros((max(n, 1) - 1) * step + rec_out if n else 0, dtype=np.uint8)
+    elif out.dtype != np.uint8 or not out.flags.c_contiguous or (n and out.size < (n - 1) * step + rec_out):
+        raise G16Error(B.G16_ERR_INVALID, "points_to_ark: out must be a contiguous uint8 array that holds n records")
+    bad = C.c_uint64()
+    st = lib.g16_points_to_ark(device, g, _ark_flags(compressed), _np_ptr(buf), in_stride, n, _np_ptr(out), out_stride,
+                               C.byref(bad))
+    if st != B.G16_OK:
+        raise G16Error(st, f"g16_points_to_ark failed: {bad.value} point(s) with a word >= q" if bad.value
+                       else "g16_points_to_ark failed")
+    return out
+
+
+def _blob(src) -> np.ndarray:
+    if isinstance(src, (bytes, bytearray, memoryview)):
+        return np.frombuffer(bytes(src), dtype=np.uint8)
+    with open(src, "rb") as f:
+        return np.frombuffer(f.read(), dtype=np.uint8)
+
+
+def _vk_desc(vk: "VerifyingKey"):
+    ic = np.ascontiguousarray(vk.gamma_abc_g1, dtype=np.uint8).reshape(-1, 64)
+    d = B.VkDesc()
+    C.memmove(d.alpha_g1, bytes(vk.alpha_g1), 64)
+    C.memmove(d.beta_g2, bytes(vk.beta_g2), 128)
+    C.memmove(d.gamma_g2, bytes(vk.gamma_g2), 128)
+    C.memmove(d.delta_g2, bytes(vk.delta_g2), 128)
+    d.ic, d.ic_count = ic.ctypes.data, ic.shape[0]
+    return d, ic
+
+
+def read_ark_key(src, compressed=True, validate=True, device=0, lib: Optional[B.Library] = None) -> ProvingKey:
+    """ProvingKey::<Bn254>::deserialize_compressed / _uncompressed (path or bytes) with the points decoded on the GPU
+    (g16_ark_pk_read).  n_vars = len(a_query), n_public = len(gamma_abc_g1) - 1, domain_size = the smallest power of
+    two >= len(h_query); h_query comes back padded with infinity to domain_size (a libsnark key has one point less;
+    the degenerate libsnark key of domain 2 has ONE H point and comes back with domain_size 1).
+    validate: the subgroup test of the G2 points (range and curve are always tested).  A malformed blob or a point
+    that fails to decode raises SerializationError (status G16_ERR_IO) naming the array, the index and the reason."""
+    lib = lib or B.load()
+    buf = _blob(src)
+    h = C.c_void_p()
+    lib.check(lib.g16_ark_pk_read(device, _ark_flags(compressed, validate), _np_ptr(buf), buf.shape[0], C.byref(h)),
+              loader=True)
+    handle = _Handle(lib, h, lib.g16_ark_pk_close)
+    kd, vd = B.KeyDesc(), B.VkDesc()
+    lib.check(lib.g16_ark_pk_key(h, C.byref(kd), C.byref(vd)), loader=True)
+    N, p, n = kd.n_vars, kd.n_public, kd.domain_size
+
+    def view(ptr, count, width):
+        if count == 0:
+            return np.zeros((0, width), dtype=np.uint8)
+        return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(count * width,)).reshape(count, width)
+
+    vk = VerifyingKey(bytes(vd.alpha_g1), bytes(vd.beta_g2), bytes(vd.gamma_g2), bytes(vd.delta_g2),
+                      view(vd.ic, vd.ic_count, 64).copy())
+    return ProvingKey(N, p, n, vk, bytes(kd.beta_g1), bytes(kd.delta_g1), view(kd.a_query, N, 64),
+                      view(kd.b_g1_query, N, 64), view(kd.b_g2_query, N, 128), view(kd.l_query, N - p - 1, 64),
+                      view(kd.h_query, n, 64), keepalive=handle)
+
+
+def write_ark_key(pk: ProvingKey, compressed=True, h_len=None, device=0, lib: Optional[B.Library] = None) -> bytes:
+    """ProvingKey::serialize_compressed / _uncompressed (g16_ark_pk_write).  h_len: points of h_query to write
+    (default domain_size; domain_size - 1 for a key of LibsnarkReduction, so that it round-trips to the same bytes)."""
+    lib = lib or B.load()
+    h_len = pk.domain_size if h_len is None else int(h_len)
+    flags = _ark_flags(compressed)
+    kd = pk.to_c()
+    vd, _ic = _vk_desc(pk.vk)
+    out = np.zeros(lib.g16_ark_pk_size(flags, pk.n_vars, pk.n_public, h_len), dtype=np.uint8)
+    lib.check(lib.g16_ark_pk_write(device, flags, C.byref(kd), C.byref(vd), h_len, _np_ptr(out), out.shape[0]),
+              loader=True)
+    return out.tobytes()
+
+
+def read_ark_vk(src, compressed=True, validate=True, device=0, lib: Optional[B.Library] = None) -> VerifyingKey:
+    """VerifyingKey::<Bn254>::deserialize_compressed / _uncompressed (g16_ark_vk_read)."""
+    lib = lib or B.load()
+    buf = _blob(src)
+    flags = _ark_flags(compressed, validate)
+    lay = B.ArkLayout()
+    lib.check(lib.g16_ark_vk_layout(_np_ptr(buf), buf.shape[0], flags, C.byref(lay)), loader=True)
+    ic = np.zeros((lay.count[4], 64), dtype=np.uint8)
+    vd = B.VkDesc()
+    lib.check(lib.g16_ark_vk_read(device, flags, _np_ptr(buf), buf.shape[0], C.byref(vd), _np_ptr(ic), ic.shape[0]),
+              loader=True)
+    return VerifyingKey(bytes(vd.alpha_g1), bytes(vd.beta_g2), bytes(vd.gamma_g2), bytes(vd.delta_g2), ic)
+
+
+def write_ark_vk(vk: VerifyingKey, compressed=True, device=0, lib: Optional[B.Library] = None) -> bytes:
+    """VerifyingKey::serialize_compressed / _uncompressed (g16_ark_vk_write)."""
+    lib = lib or B.load()
+    flags = _ark_flags(compressed)
+    vd, ic = _vk_desc(vk)
+    out = np.zeros(lib.g16_ark_vk_size(flags, ic.shape[0] - 1), dtype=np.uint8)
+    lib.check(lib.g16_ark_vk_write(device, flags, C.byref(vd), _np_ptr(out), out.shape[0]), loader=True)
+    return out.tobytes()
+
+
+def proofs_from_ark(blob, n=None, compressed=True, validate=True, device=0, lib: Optional[B.Library] = None) -> List[Proof]:
+    """n x Proof::deserialize_compressed / _uncompressed (128 / 256 bytes each) on the GPU (g16_ark_proofs_read).
+    A point that fails to decode raises SerializationError naming the proof, the point and the reason."""
+    lib = lib or B.load()
+    rec = 128 if compressed else 256
+    buf, n = _strided(blob, n, rec, 0, "proofs_from_ark")
+    out = np.zeros(n * B.G16_PROOF_BYTES, dtype=np.uint8)
+    why = np.zeros((n, 3), dtype=np.uint8)
+    bad = C.c_uint64()
+    lib.check(lib.g16_ark_proofs_read(device, _ark_flags(compressed, validate), _np_ptr(buf), n, _np_ptr(out),
+                                      _np_ptr(why), C.byref(bad)), loader=True)
+    raw = out.tobytes()
+    return [Proof(raw[i * B.G16_PROOF_BYTES:(i + 1) * B.G16_PROOF_BYTES]) for i in range(n)]
+
+
+def proofs_to_ark(proofs, compressed=True, device=0, lib: Optional[B.Library] = None) -> bytes:
+    """n x Proof::serialize_compressed / _uncompressed, concatenated (g16_ark_proofs_write)."""
+    lib = lib or B.load()
+    raw = b"".join(p.raw if isinstance(p, Proof) else bytes(p) for p in proofs)
+    n = len(raw) // B.G16_PROOF_BYTES
+    buf = np.frombuffer(raw, dtype=np.uint8)
+    out = np.zeros(n * (128 if compressed else 256), dtype=np.uint8)
+    bad = C.c_uint64()
+    st = lib.g16_ark_proofs_write(device, _ark_flags(compressed), _np_ptr(buf), n, _np_ptr(out), C.byref(bad))
+    if st != B.G16_OK:
+        raise G16Error(st, f"g16_ark_proofs_write failed ({bad.value} point(s) with a word >= q)")
+    return out.tobytes()
 
 
 def _verify_args(vk, proofs, public_inputs, lib):

@@ -75,6 +75,16 @@ KEY_BAD_NONCANONICAL, KEY_BAD_OFF_CURVE, KEY_BAD_SUBGROUP = 1, 2, 4
 KEY_PAIR_BETA, KEY_PAIR_DELTA, KEY_PAIR_B, KEY_VK_MISMATCH = 1, 2, 4, 8
 
 
+# arkworks serialization (include/g16_amd.h): the extra reason bit, the groups, the flags
+KEY_BAD_ENCODING = 8
+POINT_G1, POINT_G2 = 0, 1
+ARK_COMPRESSED, ARK_VALIDATE = 1, 2
+
+
+class ArkLayout(C.Structure):
+    _fields_ = [("offset", C.c_uint64 * 12), ("count", C.c_uint64 * 12), ("total", C.c_uint64)]
+
+
 class KeyBadPoint(C.Structure):
     _fields_ = [("query", C.c_uint32), ("index", C.c_uint32), ("reason", C.c_uint32)]
 
@@ -159,6 +169,9 @@ ABI_SYMBOLS = [
     "g16_srs_create", "g16_srs_desc_of", "g16_srs_destroy", "g16_setup_from_srs", "g16_setup_from_srs_times",
     "g16_srs_check", "g16_ptau_open", "g16_ptau_open_mem", "g16_ptau_close", "g16_ptau_header_get", "g16_ptau_srs",
     "g16_ptau_write", "g16_srs_contribute", "g16_srs_contribute_times",
+    "g16_points_from_ark", "g16_points_to_ark", "g16_ark_proofs_read", "g16_ark_proofs_write", "g16_ark_pk_size",
+    "g16_ark_pk_read", "g16_ark_pk_key", "g16_ark_pk_close", "g16_ark_pk_write", "g16_ark_vk_size", "g16_ark_vk_read",
+    "g16_ark_vk_write", "g16_ark_pk_layout", "g16_ark_vk_layout",
 ]
 
 
@@ -281,6 +294,23 @@ class Library:
             "g16_ptau_header_get": (C.c_int, [vp, C.POINTER(PtauHeader)]),
             "g16_ptau_srs": (C.c_int, [vp, C.POINTER(SrsDesc)]),
             "g16_ptau_write": (C.c_int, [C.c_char_p, C.POINTER(SrsDesc), C.c_uint32]),
+            "g16_points_from_ark": (C.c_int, [C.c_int, C.c_int, C.c_uint32, vp, C.c_size_t, C.c_uint64, vp, C.c_size_t,
+                                              vp, _u64p]),
+            "g16_points_to_ark": (C.c_int, [C.c_int, C.c_int, C.c_uint32, vp, C.c_size_t, C.c_uint64, vp, C.c_size_t,
+                                            _u64p]),
+            "g16_ark_proofs_read": (C.c_int, [C.c_int, C.c_uint32, vp, C.c_uint64, vp, vp, _u64p]),
+            "g16_ark_proofs_write": (C.c_int, [C.c_int, C.c_uint32, vp, C.c_uint64, vp, _u64p]),
+            "g16_ark_pk_size": (C.c_uint64, [C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64]),
+            "g16_ark_pk_read": (C.c_int, [C.c_int, C.c_uint32, vp, C.c_size_t, C.POINTER(vp)]),
+            "g16_ark_pk_key": (C.c_int, [vp, C.POINTER(KeyDesc), C.POINTER(VkDesc)]),
+            "g16_ark_pk_close": (None, [vp]),
+            "g16_ark_pk_write": (C.c_int, [C.c_int, C.c_uint32, C.POINTER(KeyDesc), C.POINTER(VkDesc), C.c_uint64, vp,
+                                           C.c_size_t]),
+            "g16_ark_vk_size": (C.c_uint64, [C.c_uint32, C.c_uint64]),
+            "g16_ark_vk_read": (C.c_int, [C.c_int, C.c_uint32, vp, C.c_size_t, C.POINTER(VkDesc), vp, C.c_uint32]),
+            "g16_ark_vk_write": (C.c_int, [C.c_int, C.c_uint32, C.POINTER(VkDesc), vp, C.c_size_t]),
+            "g16_ark_pk_layout": (C.c_int, [vp, C.c_size_t, C.c_uint32, C.POINTER(ArkLayout)]),
+            "g16_ark_vk_layout": (C.c_int, [vp, C.c_size_t, C.c_uint32, C.POINTER(ArkLayout)]),
         }
         # measurement builds only (make EXTRA=-DG16_DEBUG_ABI; include/g16_amd.h): not an ABI symbol, never "missing"
         optional = {"g16_debug_alu_bench": (C.c_int, [C.c_int, C.c_int, C.c_uint32, C.c_uint32,

@@ -881,4 +881,116 @@ g16_status g16_fr_to_canonical(const uint64_t* in, uint8_t* out, size_t n) {
   return G16_OK;
 }
 
+// ---- arkworks containers: the layout walk (g16_loaders.h) ---------------------------------------
+// Untrusted bytes: every step is checked against what is left of the blob BEFORE it is taken, in u64
+// arithmetic that cannot wrap (count <= left / record size).
+namespace {
+
+const char* const kArkField[G16_ARK_N_FIELDS] = {"vk.alpha_g1", "vk.beta_g2", "vk.gamma_g2", "vk.delta_g2",
+                                                 "vk.gamma_abc_g1", "beta_g1", "delta_g1", "a_query",
+                                                 "b_g1_query", "b_g2_query", "h_query", "l_query"};
+
+struct ArkWalk {
+  const uint8_t* data;
+  uint64_t len, at = 0;
+  uint64_t g1, g2;
+  g16_ark_layout* lay;
+  std::string err;
+
+  bool single(int f, bool is_g2) {
+    const uint64_t rec = is_g2 ? g2 : g1;
+    if (len - at < rec) {
+      err = std::string("truncated in ") + kArkField[f];
+      return false;
+    }
+    lay->offset[f] = at;
+    lay->count[f] = 1;
+    at += rec;
+    return true;
+  }
+  bool vec(int f, bool is_g2) {
+    const uint64_t rec = is_g2 ? g2 : g1;
+    if (len - at < 8) {
+      err = std::string("truncated in the length of ") + kArkField[f];
+      return false;
+    }
+    uint64_t n;
+    memcpy(&n, data + at, 8);
+    at += 8;
+    if (n > (len - at) / rec) {
+      err = std::string("the length of ") + kArkField[f] + " (" + std::to_string(n) + ") overruns the blob";
+      return false;
+    }
+    lay->offset[f] = at;
+    lay->count[f] = n;
+    at += n * rec;
+    return true;
+  }
+  bool vk() {
+    return single(G16_ARK_F_ALPHA_G1, false) && single(G16_ARK_F_BETA_G2, true) && single(G16_ARK_F_GAMMA_G2, true) &&
+           single(G16_ARK_F_DELTA_G2, true) && vec(G16_ARK_F_IC, false);
+  }
+  bool check_vk() {
+    if (lay->count[G16_ARK_F_IC] < 1 || lay->count[G16_ARK_F_IC] > (1ull << 31)) {
+      err = "vk.gamma_abc_g1 must hold between 1 and 2^31 points";
+      return false;
+    }
+    return true;
+  }
+  bool end() {
+    if (at != len) {
+      err = std::to_string(len - at) + " trailing byte(s)";
+      return false;
+    }
+    lay->total = at;
+    return true;
+  }
+};
+
+g16_status ark_layout(const uint8_t* data, size_t len, uint32_t flags, g16_ark_layout* out, bool pk) {
+  if (!out || (len && !data)) return fail(G16_ERR_INVALID, "null argument");
+  memset(out, 0, sizeof *out);
+  const bool comp = (flags & G16_ARK_COMPRESSED) != 0;
+  ArkWalk w{data, (uint64_t)len, 0, comp ? 32u : 64u, comp ? 64u : 128u, out, {}};
+  bool ok = w.vk() && w.check_vk();
+  if (ok && pk) {
+    ok = w.single(G16_ARK_F_BETA_G1, false) && w.single(G16_ARK_F_DELTA_G1, false) && w.vec(G16_ARK_F_A, false) &&
+         w.vec(G16_ARK_F_B1, false) && w.vec(G16_ARK_F_B2, true) && w.vec(G16_ARK_F_H, false) && w.vec(G16_ARK_F_L, false);
+    if (ok) {
+      const uint64_t N = out->count[G16_ARK_F_A], n_ic = out->count[G16_ARK_F_IC];
+      if (out->count[G16_ARK_F_B1] != N || out->count[G16_ARK_F_B2] != N) {
+        w.err = "len(b_g1_query) and len(b_g2_query) must equal len(a_query)";
+        ok = false;
+      } else if (N < n_ic || out->count[G16_ARK_F_L] != N - n_ic) {
+        w.err = "len(l_query) must equal len(a_query) - len(vk.gamma_abc_g1)";
+        ok = false;
+      } else if (N > (1ull << 31) || out->count[G16_ARK_F_H] > (1ull << 31)) {
+        w.err = "more than 2^31 points in a query";
+        ok = false;
+      }
+    }
+  }
+  ok = ok && w.end();
+  if (!ok) {
+    memset(out, 0, sizeof *out);
+    return fail(G16_ERR_IO, std::string(pk ? "ark ProvingKey: " : "ark VerifyingKey: ") + w.err);
+  }
+  return G16_OK;
+}
+
+}  // namespace
+
+g16_status g16_ark_pk_layout(const uint8_t* data, size_t len, uint32_t flags, g16_ark_layout* out) {
+  return ark_layout(data, len, flags, out, true);
+}
+g16_status g16_ark_vk_layout(const uint8_t* data, size_t len, uint32_t flags, g16_ark_layout* out) {
+  return ark_layout(data, len, flags, out, false);
+}
+
 }  // extern "C"
+
+namespace g16 {
+// arkser.hip: its container calls report through g16_loader_last_error, with the one table of field names
+g16_status loader_fail(g16_status code, const std::string& message) { return fail(code, message); }
+const char* ark_field_name(int field) { return field >= 0 && field < G16_ARK_N_FIELDS ? kArkField[field] : "?"; }
+}  // namespace g16

@@ -707,6 +707,95 @@ g16_status g16_srs_contribute(int device, const g16_srs_desc* srs,
                               uint8_t* beta_tau_g1_out, uint8_t beta_g2_out[128]);
 g16_status g16_srs_contribute_times(float* ms, uint32_t cap);
 
+/* ---- arkworks serialization (not on the proving path) ---------------------------------------------- */
+/* Every other entry point takes and returns points in the .zkey encoding (32-byte little-endian MONTGOMERY
+ * coordinates, affine x|y, all-zero = infinity).  arkworks exchanges keys, verifying keys and proofs in
+ * ark-serialize's canonical form (CanonicalSerialize::serialize_compressed / serialize_uncompressed); these calls
+ * translate between the two on the GPU, so that a compressed ProvingKey<Bn254> is loaded without one square root
+ * (and, on G2, one subgroup test) per point on the CPU.
+ *
+ * The format (BN254, ark-serialize 0.4 / 0.5):
+ *   Fq       32 bytes: the CANONICAL integer, little-endian (q has 254 bits: two flag bits are free); Fq2 = c0 | c1
+ *   flags    in the top two bits of the LAST byte of a point's record: 0x80 = "y is negative", 0x40 = infinity,
+ *            both = invalid.  "Negative" is y > -y on canonical integers: y > (q-1)/2 in Fq; in Fq2 lexicographic
+ *            with c1 FIRST (c1 > (q-1)/2, or c1 = 0 and c0 > (q-1)/2)
+ *   G1       compressed: x with flags, 32 bytes; uncompressed: x, then y with flags, 64 bytes
+ *   G2       compressed: x.c0 | x.c1 with flags, 64 bytes; uncompressed: x.c0 | x.c1 | y.c0 | y.c1 with flags, 128
+ *   infinity all-zero coordinates + 0x40.  The writer sets the sign bit in uncompressed form too, the reader
+ *            ignores it there
+ *   Vec<T>   u64 little-endian length, then the items
+ *   VerifyingKey  alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1: Vec<G1>
+ *   ProvingKey    vk, beta_g1, delta_g1, a_query, b_g1_query, b_g2_query, h_query, l_query (h BEFORE l; four Vecs)
+ *   Proof         a (G1), b (G2), c (G1): 128 bytes compressed, 256 uncompressed
+ *
+ * g16_points_from_ark   what G1Affine / G2Affine::deserialize_with_mode does for n points: in = n records in the
+ *   form above, out = n packed points.  Per point, the FIRST test that fails is its reason (g16_key_check's rule):
+ *     G16_KEY_BAD_ENCODING      both flag bits, or the infinity flag with any other bit of the record set
+ *                               (DEVIATION: arkworks ignores those bits; no canonical writer produces them)
+ *     G16_KEY_BAD_NONCANONICAL  a coordinate, flags masked off, is >= q
+ *     G16_KEY_BAD_OFF_CURVE     compressed: x^3 + b has no square root (b = 3, on the twist 3 / (9 + i));
+ *                               uncompressed: y^2 != x^3 + b -- ALWAYS tested, also where arkworks' Validate::No
+ *                               would skip it
+ *     G16_KEY_BAD_SUBGROUP      G2 with G16_ARK_VALIDATE only: [r] P != infinity
+ *   The output record of a bad point is all-zero; a well-formed infinity record decodes to the all-zero record
+ *   with reason 0.  reason_out: n bytes or NULL; *n_bad counts EVERY bad point.  Returns G16_OK when it RAN.
+ * g16_points_to_ark     serialize_with_mode: Montgomery -> canonical, the sign flag, the infinity encoding.  The
+ *   points are not tested for the curve; a stored word >= q is bad (its record is all-zero) and makes the call
+ *   return G16_ERR_INVALID with the count in *n_bad.
+ * group: G16_POINT_G1 / _G2.  flags: G16_ARK_COMPRESSED | G16_ARK_VALIDATE (Compress::Yes, Validate::Yes).
+ * Strides in bytes between consecutive records, 0 = dense; in and out must not overlap.  n == 0: G16_OK.
+ * One lane per point: a compressed G1 point costs one 252-bit exponentiation in Fq, a G2 point two (the norm
+ * method, no inversion); a validated G2 point is dominated by the [r] P test g16_key_check pays as well.
+ * Arrays stream through two page-locked host slots and two device slots of min(2^18, n) points
+ * (G16_ARKSER_CHUNK=<points> overrides, tests).  No atomics: the same bytes and reasons on every run.
+ * Standalone like g16_key_check: no ctx is needed, a ctx alive on the device is left untouched.
+ * G16_ERR_NO_DEVICE without a device: there is no CPU fallback.
+ *
+ * g16_ark_proofs_read / _write   n x Proof::deserialize_with_mode / serialize_with_mode: n arkworks proofs (128 or
+ *   256 bytes each) <-> n x G16_PROOF_BYTES, three strided codec calls.  reason_out: n x 3 bytes (a, b, c) or NULL.
+ *   A container call like the key calls: g16_ark_proofs_read returns G16_ERR_IO when ANY point fails to decode
+ *   (the message names the first proof, point and reason; *n_bad, reason_out and the zeroed records are still
+ *   filled in), so a verifier that looks at the status alone never takes a zeroed point into its batch.
+ * g16_ark_pk_read    ProvingKey::<Bn254>::deserialize_with_mode from memory.  n_vars = len(a_query), n_public =
+ *   len(gamma_abc_g1) - 1, domain_size = the smallest power of two >= len(h_query); the H array is padded with
+ *   infinity up to domain_size (a LibsnarkReduction key has domain_size - 1 points; the degenerate libsnark key
+ *   of domain 2 has ONE H point and therefore reads back with domain_size 1).  The fixed points of a container are
+ *   decoded in one codec call per group, every array in one of its own.  g16_ark_pk_key hands out
+ *   arrays owned by the handle, valid until g16_ark_pk_close.
+ * g16_ark_pk_write   ProvingKey::serialize_with_mode into out (g16_ark_pk_size bytes); the first h_len <=
+ *   domain_size entries of h_query are written, so a libsnark key round-trips to the same bytes.
+ * g16_ark_vk_read / _write   the same for VerifyingKey (g16_ark_vk_size bytes); ic_out receives gamma_abc_g1
+ *   (g16_ark_vk_layout in g16_loaders.h tells how many points), vk->ic points at it afterwards.
+ * G16_ERR_IO with a message in g16_loader_last_error: a truncated blob, a length prefix that overruns it,
+ * inconsistent array lengths, trailing bytes (the layout walk, g16_loaders.h), or a point that fails to decode --
+ * the message names the array, the index and the reason.
+ *
+ * NOT claimed: byte compatibility with arkworks rests on the description above and on known arkworks encodings
+ * of single points (the generators, their negatives, infinity) that the tests pin; no arkworks build was
+ * available to cross-check a whole ProvingKey blob.  ark-serialize 0.3 (a different flag layout) is not supported. */
+enum { G16_KEY_BAD_ENCODING = 8 };   /* per-point reason bit, next to G16_KEY_BAD_* above */
+enum { G16_POINT_G1 = 0, G16_POINT_G2 = 1 };
+enum { G16_ARK_COMPRESSED = 1, G16_ARK_VALIDATE = 2 };
+g16_status g16_points_from_ark(int device, int group, uint32_t flags, const uint8_t* in, size_t in_stride,
+                               uint64_t n, uint8_t* out, size_t out_stride, uint8_t* reason_out, uint64_t* n_bad);
+g16_status g16_points_to_ark(int device, int group, uint32_t flags, const uint8_t* in, size_t in_stride,
+                             uint64_t n, uint8_t* out, size_t out_stride, uint64_t* n_bad);
+g16_status g16_ark_proofs_read(int device, uint32_t flags, const uint8_t* in, uint64_t n, uint8_t* proofs_out,
+                               uint8_t* reason_out, uint64_t* n_bad);
+g16_status g16_ark_proofs_write(int device, uint32_t flags, const uint8_t* proofs, uint64_t n, uint8_t* out,
+                                uint64_t* n_bad);
+typedef struct g16_ark_pk g16_ark_pk;
+uint64_t g16_ark_pk_size(uint32_t flags, uint64_t n_vars, uint64_t n_public, uint64_t h_len);
+g16_status g16_ark_pk_read(int device, uint32_t flags, const uint8_t* data, size_t len, g16_ark_pk** out);
+g16_status g16_ark_pk_key(const g16_ark_pk* h, g16_key_desc* key, g16_vk_desc* vk);
+void g16_ark_pk_close(g16_ark_pk* h);
+g16_status g16_ark_pk_write(int device, uint32_t flags, const g16_key_desc* key, const g16_vk_desc* vk,
+                            uint64_t h_len, uint8_t* out, size_t cap);
+uint64_t g16_ark_vk_size(uint32_t flags, uint64_t n_public);
+g16_status g16_ark_vk_read(int device, uint32_t flags, const uint8_t* data, size_t len, g16_vk_desc* vk,
+                           uint8_t* ic_out, uint32_t ic_cap);
+g16_status g16_ark_vk_write(int device, uint32_t flags, const g16_vk_desc* vk, uint8_t* out, size_t cap);
+
 /* ---- loaders (host side, C++): see g16_loaders.h ---------------------------------------------- */
 
 #ifdef __cplusplus

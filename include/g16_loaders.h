@@ -89,6 +89,26 @@ g16_status g16_ptau_srs(const g16_ptau* p, g16_srs_desc* out);
  * dropped); ceremony_power = power                                                                       */
 g16_status g16_ptau_write(const char* path, const g16_srs_desc* srs, uint32_t power);
 
+/* ------------------------------------------------ arkworks containers: the layout walk -------- */
+/* Where the fields of an ark-serialize'd ProvingKey<Bn254> / VerifyingKey<Bn254> lie (the format: g16_amd.h,
+ * "arkworks serialization"; flags: G16_ARK_COMPRESSED decides the record sizes).  Pure host code over untrusted
+ * bytes: nothing beyond data[len) is dereferenced, no point is looked at.  offset[f] is where the first point of
+ * field f starts (behind the length prefix of a Vec), count[f] its points (1 for the single ones), total the
+ * length the blob must have.  G16_ERR_IO with a message in g16_loader_last_error: a truncated blob; a length
+ * prefix that overruns the blob or overflows; len(b_g1_query) or len(b_g2_query) != len(a_query),
+ * len(gamma_abc_g1) < 1, len(l_query) != len(a_query) - len(gamma_abc_g1), len(h_query) > 2^31; trailing bytes.
+ * g16_ark_vk_layout fills the first five fields and leaves the others zero.                                */
+enum { G16_ARK_F_ALPHA_G1 = 0, G16_ARK_F_BETA_G2, G16_ARK_F_GAMMA_G2, G16_ARK_F_DELTA_G2, G16_ARK_F_IC,
+       G16_ARK_F_BETA_G1, G16_ARK_F_DELTA_G1, G16_ARK_F_A, G16_ARK_F_B1, G16_ARK_F_B2, G16_ARK_F_H, G16_ARK_F_L,
+       G16_ARK_N_FIELDS };
+typedef struct {
+  uint64_t offset[G16_ARK_N_FIELDS];
+  uint64_t count[G16_ARK_N_FIELDS];
+  uint64_t total;
+} g16_ark_layout;
+g16_status g16_ark_pk_layout(const uint8_t* data, size_t len, uint32_t flags, g16_ark_layout* out);
+g16_status g16_ark_vk_layout(const uint8_t* data, size_t len, uint32_t flags, g16_ark_layout* out);
+
 /* ---------------------------------------------------------------- .r1cs ---------------------- */
 typedef struct g16_r1cs g16_r1cs;
 

@@ -72,6 +72,26 @@ pub struct g16_r1cs {
 pub struct g16_ptau {
     _private: [u8; 0],
 }
+#[repr(C)]
+pub struct g16_ark_pk {
+    _private: [u8; 0],
+}
+
+// arkworks serialization (include/g16_amd.h): the extra per-point reason bit, the groups, the flags
+pub const G16_KEY_BAD_ENCODING: u32 = 8;
+pub const G16_POINT_G1: c_int = 0;
+pub const G16_POINT_G2: c_int = 1;
+pub const G16_ARK_COMPRESSED: u32 = 1;
+pub const G16_ARK_VALIDATE: u32 = 2;
+pub const G16_ARK_N_FIELDS: usize = 12;
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct g16_ark_layout {
+    pub offset: [u64; G16_ARK_N_FIELDS],
+    pub count: [u64; G16_ARK_N_FIELDS],
+    pub total: u64,
+}
 
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -308,9 +328,23 @@ extern "C" {
     pub fn g16_srs_check(device: c_int, srs: *const g16_srs_desc, rho: *const u64, bad_out: *mut g16_key_bad_point, bad_cap: u32, report: *mut g16_srs_report) -> g16_status;
     pub fn g16_srs_contribute(device: c_int, srs: *const g16_srs_desc, secrets: *const u64, tau_g1_out: *mut u8, tau_g2_out: *mut u8, alpha_tau_g1_out: *mut u8, beta_tau_g1_out: *mut u8, beta_g2_out: *mut u8) -> g16_status;
     pub fn g16_srs_contribute_times(ms: *mut c_float, cap: u32) -> g16_status;
+    pub fn g16_points_from_ark(device: c_int, group: c_int, flags: u32, input: *const u8, in_stride: usize, n: u64, out: *mut u8, out_stride: usize, reason_out: *mut u8, n_bad: *mut u64) -> g16_status;
+    pub fn g16_points_to_ark(device: c_int, group: c_int, flags: u32, input: *const u8, in_stride: usize, n: u64, out: *mut u8, out_stride: usize, n_bad: *mut u64) -> g16_status;
+    pub fn g16_ark_proofs_read(device: c_int, flags: u32, input: *const u8, n: u64, proofs_out: *mut u8, reason_out: *mut u8, n_bad: *mut u64) -> g16_status;
+    pub fn g16_ark_proofs_write(device: c_int, flags: u32, proofs: *const u8, n: u64, out: *mut u8, n_bad: *mut u64) -> g16_status;
+    pub fn g16_ark_pk_size(flags: u32, n_vars: u64, n_public: u64, h_len: u64) -> u64;
+    pub fn g16_ark_pk_read(device: c_int, flags: u32, data: *const u8, len: usize, out: *mut *mut g16_ark_pk) -> g16_status;
+    pub fn g16_ark_pk_key(h: *const g16_ark_pk, key: *mut g16_key_desc, vk: *mut g16_vk_desc) -> g16_status;
+    pub fn g16_ark_pk_close(h: *mut g16_ark_pk);
+    pub fn g16_ark_pk_write(device: c_int, flags: u32, key: *const g16_key_desc, vk: *const g16_vk_desc, h_len: u64, out: *mut u8, cap: usize) -> g16_status;
+    pub fn g16_ark_vk_size(flags: u32, n_public: u64) -> u64;
+    pub fn g16_ark_vk_read(device: c_int, flags: u32, data: *const u8, len: usize, vk: *mut g16_vk_desc, ic_out: *mut u8, ic_cap: u32) -> g16_status;
+    pub fn g16_ark_vk_write(device: c_int, flags: u32, vk: *const g16_vk_desc, out: *mut u8, cap: usize) -> g16_status;
 
     // ---- include/g16_loaders.h -----------------------------------------------------------------
     pub fn g16_loader_last_error() -> *const c_char;
+    pub fn g16_ark_pk_layout(data: *const u8, len: usize, flags: u32, out: *mut g16_ark_layout) -> g16_status;
+    pub fn g16_ark_vk_layout(data: *const u8, len: usize, flags: u32, out: *mut g16_ark_layout) -> g16_status;
     pub fn g16_ptau_open(path: *const c_char, out: *mut *mut g16_ptau) -> g16_status;
     pub fn g16_ptau_open_mem(data: *const u8, len: usize, out: *mut *mut g16_ptau) -> g16_status;
     pub fn g16_ptau_close(p: *mut g16_ptau);

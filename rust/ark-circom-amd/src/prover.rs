@@ -7,6 +7,7 @@ use std::os::raw::c_int;
 use ark_bn254::{Bn254, Fr};
 use ark_groth16::{Proof, ProvingKey};
 use ark_relations::r1cs::{ConstraintMatrices, SynthesisError};
+use ark_serialize::{Compress, Validate};
 use ark_std::rand::Rng;
 use ark_std::UniformRand;
 
@@ -375,6 +376,59 @@ impl GpuProver {
         }
         bad.truncate(report.n_listed as usize);
         Ok((report, bad))
+    }
+
+    /// A prover straight from `ProvingKey::<Bn254>::serialize_with_mode` bytes (`g16_ark_pk_read`,
+    /// include/g16_amd.h): the points are decompressed, range-, curve- and (with `Validate::Yes`, on G2)
+    /// subgroup-tested on the GPU and handed to the ctx in the packed form they come out in -- no
+    /// `ProvingKey::deserialize_with_mode` on the CPU, no `pack_*`.  A malformed blob or a point that fails
+    /// to decode is `GpuError::Library(G16_ERR_IO, message)`; the message names the array and the index.
+    /// `matrices` are those of the circuit the key belongs to (a `ProvingKey` carries none).  The H query is
+    /// padded with infinity to the domain, so a `LibsnarkReduction` key loads as it is.
+    pub fn from_serialized(
+        bytes: &[u8],
+        compress: Compress,
+        validate: Validate,
+        matrices: &ConstraintMatrices<Fr>,
+        reduction: Reduction,
+        device: i32,
+    ) -> Result<Self, GpuError> {
+        let flags = if compress == Compress::Yes { ffi::G16_ARK_COMPRESSED } else { 0 }
+            | if validate == Validate::Yes { ffi::G16_ARK_VALIDATE } else { 0 };
+        let loader_error = || unsafe { CStr::from_ptr(ffi::g16_loader_last_error()).to_string_lossy().into_owned() };
+        let mut h: *mut ffi::g16_ark_pk = std::ptr::null_mut();
+        let st = unsafe { ffi::g16_ark_pk_read(device as c_int, flags, bytes.as_ptr(), bytes.len(), &mut h) };
+        if st != ffi::G16_OK {
+            return Err(GpuError::Library(st, loader_error()));
+        }
+        struct Close(*mut ffi::g16_ark_pk);
+        impl Drop for Close {
+            fn drop(&mut self) {
+                unsafe { ffi::g16_ark_pk_close(self.0) }
+            }
+        }
+        let _close = Close(h);
+        let mut key: ffi::g16_key_desc = unsafe { std::mem::zeroed() };
+        let st = unsafe { ffi::g16_ark_pk_key(h, &mut key, std::ptr::null_mut()) };
+        if st != ffi::G16_OK {
+            return Err(GpuError::Library(st, "g16_ark_pk_key failed".into()));
+        }
+        let need = (matrices.num_constraints + matrices.num_instance_variables).next_power_of_two();
+        if need != key.domain_size as usize || matrices.num_instance_variables != key.n_public as usize + 1 {
+            return Err(GpuError::Library(ffi::G16_ERR_INVALID, "the key does not have the sizes of these matrices".into()));
+        }
+        let (ca, cb): (Csr, Csr) = pack::matrices_to_csr(matrices);
+        let (va, vb) = (ca.view(), cb.view());
+        let opt = ffi::g16_options {
+            device: device as c_int,
+            reduction: if reduction == Reduction::Libsnark { ffi::G16_REDUCTION_LIBSNARK } else { ffi::G16_REDUCTION_CIRCOM },
+            ..Default::default()
+        };
+        let mut ctx: *mut ffi::g16_ctx = std::ptr::null_mut();
+        // the ctx copies the key to the device: the handle's arrays are needed only for this call
+        let st = unsafe { ffi::g16_ctx_create(&key, &va, &vb, matrices.num_constraints as u32, &opt, &mut ctx) };
+        check(std::ptr::null(), st)?;
+        Ok(GpuProver { ctx, n_vars: key.n_vars as usize, num_inputs: matrices.num_instance_variables, num_constraints: matrices.num_constraints })
     }
 
     /// packs the key and the matrices once and hands them to `make` (g16_ctx_create / _multi)
