@@ -298,6 +298,82 @@ struct F29 {
   static G16_HD F29 mul_sub(const F29& a, const F29& b, const F29& c, const F29& d) {
     return mul2(a, b, c.neg(), d);
   }
+  // Same value, limbs 0..7 moved to the CENTRED range: one parallel carry step around 2^28 instead of 0.
+  //   input  : limbs 0..7 within +-(2^29 + 2^4) (any class of ec29.h)
+  //   output : limbs 0..7 in [-2^28 - 1, 2^28], top limb moved by at most 1
+  // The low part of a limb is its sign-extended 29-bit field (v_bfe_i32), the carry what is left: -1, 0 or 1.
+  // Halves the limb bound of one side of a product, which is what lets mul4 put 36 products into one column.
+  G16_HD F29 recentre() const {
+    constexpr int N = f29::N;
+#ifdef F29_CHECK
+    for (int i = 0; i < N - 1; ++i) assert(l[i] >= -(1 << 29) - 16 && l[i] <= (1 << 29) + 16 && "F29 recentre: limb out of range");
+#endif
+    int32_t lo[N - 1], hi[N - 1];
+#pragma unroll
+    for (int i = 0; i < N - 1; ++i) {
+      lo[i] = (int32_t)((uint32_t)l[i] << 3) >> 3;  // in [-2^28, 2^28), == l[i] mod 2^29
+      hi[i] = (l[i] - lo[i]) >> 29;
+    }
+    F29 r;
+    r.l[0] = lo[0];
+#pragma unroll
+    for (int i = 1; i < N - 1; ++i) r.l[i] = lo[i] + hi[i - 1];
+    r.l[N - 1] = l[N - 1] + hi[N - 2];
+    return r;
+  }
+  // (a b + c d + e f + g h) / 2^261 with ONE reduction: 36 products per column.
+  //   inputs : sum_i |a_i b_(k-i)| + |c_i d_(k-i)| + |e_i f_(k-i)| + |g_i h_(k-i)| < 2^62.5 for every column k, as for
+  //            mul -- with a, c, e, g re-centred (|limb| <= 2^28 + 1) against limbs within +-(2^29 + 2^4) that is
+  //            36 * 2^57.01 = 2^62.18, and with the 9 m_i p_j < 2^58 of the reduction and the carry 2^62.76 < 2^63;
+  //            |value(a) value(b)| + ... + |value(g) value(h)| < 337 p^2
+  //   output : limbs 0..7 in [0, 2^29), |top limb| < 2^24, value in (-2p, 3p): T / 2^261 < 2 p for
+  //            T < 337.8 p^2, and the reduction adds less than p (the stored-y class of ec29.h; inside (-p, 2p)
+  //            when the value sum is below 168.9 p^2 as for mul)
+  static G16_HD F29 mul4(const F29& a, const F29& b, const F29& c, const F29& d, const F29& e, const F29& f,
+                         const F29& g, const F29& h) {
+    constexpr int N = f29::N;
+#ifdef F29_CHECK
+    check_mul4_inputs(a, b, c, d, e, f, g, h);
+#endif
+    int64_t acc = 0;
+    int32_t m[N];
+    F29 r;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+#pragma unroll
+      for (int i = 0; i <= k; ++i) {
+        F29_MAD(acc, a.l[i], b.l[k - i]);
+        F29_MAD(acc, c.l[i], d.l[k - i]);
+        F29_MAD(acc, e.l[i], f.l[k - i]);
+        F29_MAD(acc, g.l[i], h.l[k - i]);
+      }
+#pragma unroll
+      for (int i = 0; i < k; ++i) F29_MAD_C(acc, m[i], C::MOD.v[k - i]);
+      m[k] = (int32_t)(((uint32_t)acc * C::NINV) & f29::MASK);
+      F29_MAD_C(acc, m[k], C::MOD.v[0]);
+      acc >>= 29;
+    }
+#pragma unroll
+    for (int k = N; k < 2 * N - 1; ++k) {
+#pragma unroll
+      for (int i = k - N + 1; i < N; ++i) {
+        F29_MAD(acc, a.l[i], b.l[k - i]);
+        F29_MAD(acc, c.l[i], d.l[k - i]);
+        F29_MAD(acc, e.l[i], f.l[k - i]);
+        F29_MAD(acc, g.l[i], h.l[k - i]);
+      }
+#pragma unroll
+      for (int i = k - N + 1; i < N; ++i) F29_MAD_C(acc, m[i], C::MOD.v[k - i]);
+      r.l[k - N] = (int32_t)((uint32_t)acc & f29::MASK);
+      acc >>= 29;
+    }
+    r.l[N - 1] = (int32_t)acc;
+#ifdef F29_CHECK
+    assert(acc > -(1 << 24) && acc < (1 << 24) && "F29 mul4: top limb");
+    assert(fabsl(approx_over_p(r) - 0.5L) < 2.5L && "F29 mul4: result outside (-2p, 3p)");
+#endif
+    return r;
+  }
   // a^2 / 2^261: the cross terms a_i a_j (i < j) are formed once against the doubled limb
   G16_HD F29 sqr() const {
     constexpr int N = f29::N;
@@ -465,6 +541,28 @@ struct F29 {
     long double v = fabsl(approx_over_p(a) * approx_over_p(b)) + fabsl(approx_over_p(c) * approx_over_p(d));
     assert(v < 168.9L && "F29 mul2: value bound exceeded");
   }
+  static void check_mul4_inputs(const F29& a, const F29& b, const F29& c, const F29& d, const F29& e, const F29& f,
+                                const F29& g, const F29& h) {
+    const F29* u[4] = {&a, &c, &e, &g};
+    const F29* v[4] = {&b, &d, &f, &h};
+    for (int k = 0; k < 2 * f29::N - 1; ++k) {
+      __int128 s = 0;
+      for (int i = 0; i < f29::N; ++i) {
+        const int j = k - i;
+        if (j < 0 || j >= f29::N) continue;
+        for (int q = 0; q < 4; ++q) {
+          __int128 x = (__int128)u[q]->l[i] * v[q]->l[j];
+          s += x < 0 ? -x : x;
+        }
+      }
+      s += (__int128)9 << 58;
+      s += (__int128)1 << 36;
+      assert(s < ((__int128)1 << 63) && "F29 mul4: column overflow");
+    }
+    long double t = 0;
+    for (int q = 0; q < 4; ++q) t += fabsl(approx_over_p(*u[q]) * approx_over_p(*v[q]));
+    assert(t < 337.0L && "F29 mul4: value bound exceeded");
+  }
   static void check_mul_inputs(const F29& a, const F29& b) {
     {
       long double v = fabsl(approx_over_p(a) * approx_over_p(b));
@@ -618,10 +716,35 @@ struct F29x2 {
   // too wide for BOTH sides of a product (9 x 2^60 > 2^62.9).  The sum is carried (27 cheap 32-bit operations):
   // limbs 0..7 back in [-4, 2^29 + 4), columns below 9 x 2^59.01.
   G16_HD F29x2 sqr() const { return F29x2{(c0 + c1).carry() * (c0 - c1), c0.dbl() * c1}; }
-  // a b - c d; components carried (two separate reductions per component would overflow the
-  // 64-bit columns if merged: 36 products)
-  static G16_HD F29x2 mul_sub(const F29x2& a, const F29x2& b, const F29x2& c, const F29x2& d) {
+  // a b - c d, the Y3 of every G2 addition and doubling (ec29.h).  mul_sub_merged: ONE reduction per component,
+  //   c0 = a0 b0 - a1 b1 - c0 d0 + c1 d1,   c1 = a0 b1 + a1 b0 - c0 d1 - c1 d0      (B::mul4, 36 products per column)
+  // where (a b - c d).carry() paid four (two full Fq2 products).  36 products of limbs within +-(2^29 + 2^4) would
+  // overflow the 64-bit column (36 * 2^58.01 > 2^63), so the LEFT operand of every product -- the components of a
+  // and of -c, 4 x 9 limbs, shared by both components of the result -- is re-centred first (B::recentre, 32-bit
+  // operations): |limb| <= 2^28 + 1 against +-(2^29 + 2^4) is 36 * 2^57.01 + 9 * 2^58 + carry < 2^62.76.
+  //   inputs : all limbs 0..7 within +-(2^29 + 2^4); |a0 b0| + |a1 b1| + |c0 d0| + |c1 d1| < 337 p^2 and the same
+  //            for the crossed pairs (ec29.h's worst: R, Pp below 10 p against Q - X3 below 9 p, y below 3 p against
+  //            PPP below 2 p: 2 * 90 + 2 * 6 = 192 p^2)
+  //   output : limbs 0..7 in [0, 2^29), components in (-2p, 3p) -- inside the class of the carried difference of two
+  //            products (limbs in [-1, 2^29], value in (-3p, 3p)) that the split form returns.
+  // mul_sub itself is still the split form: F29X2_MULSUB_MERGED (variant builds, A/B) selects the merged one.  The two
+  // agree mod p but not as integers -- the merged result is the split one or that + p, whichever way the two
+  // reductions' multiples of p happen to differ -- and tests/test_lazy_field.py pins the split form's integer
+  // (measured: -0.3 ms of a 35.5 ms 2^22 proof, profiles/r08_acc_trim_ab.txt).
+  static G16_HD F29x2 mul_sub_merged(const F29x2& a, const F29x2& b, const F29x2& c, const F29x2& d) {
+    const B a0 = a.c0.recentre(), a1 = a.c1.recentre(), n0 = c.c0.neg().recentre(), n1 = c.c1.neg().recentre();
+    return F29x2{B::mul4(a0, b.c0, a1.neg(), b.c1, n0, d.c0, n1.neg(), d.c1),
+                 B::mul4(a0, b.c1, a1, b.c0, n0, d.c1, n1, d.c0)};
+  }
+  static G16_HD F29x2 mul_sub_split(const F29x2& a, const F29x2& b, const F29x2& c, const F29x2& d) {
     return (a * b - c * d).carry();
+  }
+  static G16_HD F29x2 mul_sub(const F29x2& a, const F29x2& b, const F29x2& c, const F29x2& d) {
+#ifdef F29X2_MULSUB_MERGED
+    return mul_sub_merged(a, b, c, d);
+#else
+    return mul_sub_split(a, b, c, d);
+#endif
   }
   G16_HD bool is_zero_mod_p() const { return c0.is_zero_mod_p() && c1.is_zero_mod_p(); }
   G16_HD bool maybe_zero_mod_p() const { return c0.maybe_zero_mod_p() && c1.maybe_zero_mod_p(); }

@@ -29,6 +29,12 @@ inline bool acc_fast() {
 }
 // (the optimistic kernel for the G2 launch was built and measured in round 3: 13.5-13.7 against
 // 12.2-12.3 ms per launch, DESIGN.md section 5 -- G2 keeps the exact kernel, the variant is not compiled)
+// G16_PAIR_MAP=0 (diagnostic, A/B): the pair launch with one WAVE per half of the records instead of one
+// half-wave (k_bucket_accumulate)
+inline uint32_t pair_map() {
+  static const uint32_t v = [] { const char* e = getenv("G16_PAIR_MAP"); return !e || atoi(e) != 0 ? 1u : 0u; }();
+  return v;
+}
 template <class F>
 constexpr bool acc_is_g1() { return sizeof(F) == sizeof(Fq); }
 constexpr int COMB_THREADS = 64;
@@ -199,9 +205,12 @@ __device__ __forceinline__ void acc_way_commit(AccWay<F>& w, bool step,
 // two segments per lane in one basic block was measured and lost: ~450 VGPRs (1 wave per SIMD),
 // 21.4 vs 17.5 ms for the four G1 MSMs of a 2^22 proof; capped at 256 VGPRs it spills.
 // PS = record stride in points (2: this query is one half of an interleaved pair,
-// MsmPoints::init_pair).  PAIR: both halves in one launch -- the two waves of a workgroup walk the SAME 64 segments, wave h over half h
-// of every 128-byte record into partial set h -- identical control flow, so the waves stay within an
-// iteration or two of each other and the later one finds the line in the cache.
+// MsmPoints::init_pair).  PAIR: both halves in one launch -- a workgroup walks 64 segments twice, over half h of
+// every 128-byte record into partial set h.  Each wave takes 32 segments, lanes l and l + 32 the two halves of
+// the same one: identical control flow in both half-waves (same segment, same bucket boundaries), and both
+// halves of a record are asked for by the SAME load instruction.  (With one wave per half, pair_map = 0, the
+// later wave was expected to find the line in the cache; TCC_EA0_RDREQ_128B says 1.9 line reads per record:
+// 104.0 M per launch at 2^22 against 62.9 M with half-waves, profiles/r08_pmc_k22_pair.txt.)
 // FAST (G1): optimistic kernel, see acc_way_commit; !FAST with a list: the exact kernel launched
 // behind it, which returns at once unless the list overflowed (fix->overflow, set by k_acc_fixup).
 #ifdef G16_ACC_WAVES2  // experiment: cap the kernel at 256 VGPRs (two waves per SIMD for the G2 optimistic variant)
@@ -214,7 +223,8 @@ __global__ void __launch_bounds__(ACC_THREADS) G16_ACC_ATTR
     k_bucket_accumulate(const Affine<F>* __restrict__ pts, uint32_t npts, uint32_t idx_min,
                         uint32_t idx_bits, const uint32_t* __restrict__ entries,
                         const uint32_t* __restrict__ offset, uint32_t nb, uint32_t lanes,
-                        MsmAcc<F>* __restrict__ partial, size_t slot_stride, MsmFixList* fix) {
+                        MsmAcc<F>* __restrict__ partial, size_t slot_stride, MsmFixList* fix,
+                        uint32_t pair_map) {
   using LF = typename Lazy<F>::type;
   if (!FAST && fix && fix->overflow == 0) return;
   const uint32_t M = offset[nb];
@@ -222,11 +232,16 @@ __global__ void __launch_bounds__(ACC_THREADS) G16_ACC_ATTR
   uint32_t nthreads = gridDim.x * blockDim.x, t0 = blockIdx.x * blockDim.x + threadIdx.x;
   uint32_t half = 0;
   if (PAIR) {
-    half = threadIdx.x / (ACC_THREADS / 2);
+    if (pair_map) {  // half-waves: lanes l and l + 32 fetch the two halves of one record with the same instruction
+      half = (threadIdx.x >> 5) & 1u;
+      t0 = blockIdx.x * (ACC_THREADS / 2) + (threadIdx.x >> 6) * 32 + (threadIdx.x & 31);
+    } else {  // G16_PAIR_MAP=0: wave h over half h
+      half = threadIdx.x / (ACC_THREADS / 2);
+      t0 = blockIdx.x * (ACC_THREADS / 2) + threadIdx.x % (ACC_THREADS / 2);
+    }
     pts += half;
     partial += (size_t)half * slot_stride;
     nthreads /= 2;
-    t0 = blockIdx.x * (ACC_THREADS / 2) + threadIdx.x % (ACC_THREADS / 2);
   }
   for (; t0 < lanes; t0 += nthreads) {
     AccWay<F> w;
@@ -583,10 +598,10 @@ void msm_accumulate(const MsmSort& s, const MsmPoints<F>& P, uint32_t idx_min, M
       MsmFixList* fix = work.fix.p + slot;
       if (P.stride == 2)
         G16_LAUNCH((k_bucket_accumulate<F, 2, false, true>), grid, ACC_THREADS, 0, stream, P.data() + P.off,
-                   P.count, idx_min, cfg.idx_bits, en, of, nb, lanes, out, (size_t)0, fix);
+                   P.count, idx_min, cfg.idx_bits, en, of, nb, lanes, out, (size_t)0, fix, 0u);
       else
         G16_LAUNCH((k_bucket_accumulate<F, 1, false, true>), grid, ACC_THREADS, 0, stream, P.data(), P.count,
-                   idx_min, cfg.idx_bits, en, of, nb, lanes, out, (size_t)0, fix);
+                   idx_min, cfg.idx_bits, en, of, nb, lanes, out, (size_t)0, fix, 0u);
       if (tm) tm->end(id, stream);
       if (fixup) msm_fixup<F>(s, P, idx_min, work, slot, stream, tm);
       return;
@@ -594,10 +609,10 @@ void msm_accumulate(const MsmSort& s, const MsmPoints<F>& P, uint32_t idx_min, M
   }
   if (P.stride == 2)
     G16_LAUNCH((k_bucket_accumulate<F, 2, false, false>), grid, ACC_THREADS, 0, stream, P.data() + P.off,
-               P.count, idx_min, cfg.idx_bits, en, of, nb, lanes, out, (size_t)0, (MsmFixList*)nullptr);
+               P.count, idx_min, cfg.idx_bits, en, of, nb, lanes, out, (size_t)0, (MsmFixList*)nullptr, 0u);
   else
     G16_LAUNCH((k_bucket_accumulate<F, 1, false, false>), grid, ACC_THREADS, 0, stream, P.data(), P.count,
-               idx_min, cfg.idx_bits, en, of, nb, lanes, out, (size_t)0, (MsmFixList*)nullptr);
+               idx_min, cfg.idx_bits, en, of, nb, lanes, out, (size_t)0, (MsmFixList*)nullptr, 0u);
   if (tm) tm->end(id, stream);
 }
 
@@ -628,11 +643,11 @@ void msm_fixup(const MsmSort& s, const MsmPoints<F>& P, uint32_t idx_min, MsmWor
   if (P.stride == 2) {
     G16_LAUNCH((k_acc_fixup<F, 2>), 1, 256, 0, stream, P.data() + P.off, P.count, idx_min, cfg.idx_bits, fix, out, (size_t)0);
     G16_LAUNCH((k_bucket_accumulate<F, 2, false, false>), grid_x, ACC_THREADS, 0, stream, P.data() + P.off,
-               P.count, idx_min, cfg.idx_bits, en, of, nb, lanes, out, (size_t)0, fix);
+               P.count, idx_min, cfg.idx_bits, en, of, nb, lanes, out, (size_t)0, fix, 0u);
   } else {
     G16_LAUNCH((k_acc_fixup<F, 1>), 1, 256, 0, stream, P.data(), P.count, idx_min, cfg.idx_bits, fix, out, (size_t)0);
     G16_LAUNCH((k_bucket_accumulate<F, 1, false, false>), grid_x, ACC_THREADS, 0, stream, P.data(), P.count,
-               idx_min, cfg.idx_bits, en, of, nb, lanes, out, (size_t)0, fix);
+               idx_min, cfg.idx_bits, en, of, nb, lanes, out, (size_t)0, fix, 0u);
   }
   if (tm) tm->end(tid, stream);
   }
@@ -657,14 +672,14 @@ void msm_accumulate_pair(const MsmSort& s, const MsmPoints<F>& A, const MsmPoint
   if constexpr (sizeof(F) == sizeof(Fq)) {
     if (acc_fast()) {
       G16_LAUNCH((k_bucket_accumulate<F, 2, true, true>), grid, ACC_THREADS, 0, stream, A.data(), A.count, 0u,
-                 cfg.idx_bits, en, of, nb, cfg.lanes, out, (size_t)work.slots, work.fix.p + slot);
+                 cfg.idx_bits, en, of, nb, cfg.lanes, out, (size_t)work.slots, work.fix.p + slot, pair_map());
       if (tm) tm->end(id, stream);
       if (fixup) msm_fixup_pair<F>(s, A, B, work, slot, stream, tm);
       return;
     }
   }
   G16_LAUNCH((k_bucket_accumulate<F, 2, true, false>), grid, ACC_THREADS, 0, stream, A.data(), A.count, 0u,
-             cfg.idx_bits, en, of, nb, cfg.lanes, out, (size_t)work.slots, (MsmFixList*)nullptr);
+             cfg.idx_bits, en, of, nb, cfg.lanes, out, (size_t)work.slots, (MsmFixList*)nullptr, pair_map());
   if (tm) tm->end(id, stream);
 }
 
@@ -684,7 +699,7 @@ void msm_fixup_pair(const MsmSort& s, const MsmPoints<F>& A, const MsmPoints<F>&
     G16_LAUNCH((k_acc_fixup<F, 2>), 1, 256, 0, stream, A.data(), A.count, 0u, cfg.idx_bits, fix, out, (size_t)work.slots);
     G16_LAUNCH((k_bucket_accumulate<F, 2, true, false>), grid_x, ACC_THREADS, 0, stream, A.data(), A.count, 0u,
                cfg.idx_bits, (const uint32_t*)s.entries.p, (const uint32_t*)s.offset.p, nb, cfg.lanes, out,
-               (size_t)work.slots, fix);
+               (size_t)work.slots, fix, pair_map());
     if (tm) tm->end(tid, stream);
   }
 }
