@@ -37,7 +37,7 @@ __all__ = ["read_zkey", "R1CSFile", "R1CS", "CircomCircuit", "CircomBuilder", "C
            "Prover", "ProvingKey", "VerifyingKey", "ConstraintMatrices", "Proof", "G16Error",
            "SynthesisError", "SerializationError", "fr_from_ints", "fr_to_ints", "read_wtns",
            "trapdoor_setup", "Csr", "write_zkey", "device_tensor", "verify_batch", "verify_aggregate",
-           "verify_batch_fast", "check_key", "KeyReport", "contribute_key", "check_contribution",
+           "verify_batch_fast", "verify_aggregate_keys", "verify_batch_keys", "verify_batch_fast_keys", "check_key", "KeyReport", "contribute_key", "check_contribution",
            "ContributionReport", "Srs", "trapdoor_srs", "setup_from_srs", "check_key_circuit",
            "CircuitBindingReport", "read_ptau", "write_ptau", "check_srs", "SrsReport", "contribute_srs", "new_srs",
            "points_from_ark", "points_to_ark", "read_ark_key", "write_ark_key", "read_ark_vk", "write_ark_vk",
@@ -1549,6 +1549,90 @@ def verify_batch_fast(vk: "VerifyingKey", proofs, public_inputs, device=0, lib: 
         for i, v in zip(rest, verify_batch(vk, [proofs[i] for i in rest], [public_inputs[i] for i in rest],
                                            device=device, lib=lib)):
             out[i] = v
+    return out
+
+
+def _verify_groups_args(groups, lib):
+    """groups of (vk, proofs, public_inputs) packed as the *_keys entry points take them: (array of vk
+    descriptor pointers, counts, proof bytes, public inputs, keepalive)"""
+    packed = [_verify_args(vk, proofs, public_inputs, lib) for vk, proofs, public_inputs in groups]
+    counts = np.array([p[3] for p in packed], dtype=np.uint32)
+    vks = (C.POINTER(B.VkDesc) * max(len(packed), 1))(*[C.pointer(p[0]) for p in packed])
+    buf = np.concatenate([p[1] for p in packed]) if packed else np.zeros(0, np.uint8)
+    rows = [np.asarray(p[2], dtype=np.uint64).reshape(-1, 4) for p in packed if len(p[2])]
+    pubs = np.ascontiguousarray(np.concatenate(rows)) if rows else np.zeros((0, 4), np.uint64)
+    return vks, counts, np.ascontiguousarray(buf), pubs, packed
+
+
+def verify_aggregate_keys(groups, rho=None, device=0, lib: Optional[B.Library] = None, return_structural=False):
+    """Proofs under MANY keys in one pass (g16_verify_aggregate_keys).  groups: a sequence of
+    (vk, proofs, public_inputs), each as verify_aggregate takes them.  Returns one bool per group: exactly
+    verify_aggregate's verdict on that group alone (an empty group is True) -- groups are independent, nothing
+    is combined across keys -- for about the cost of ONE verify_aggregate call whatever the number of keys.
+    rho: None (drawn by the library) or one list per group, under verify_aggregate's rules.
+    return_structural=True returns (verdicts, [[proof i of group k is well formed]])."""
+    lib = lib or B.load()
+    groups = list(groups)
+    vks, counts, buf, pubs, keep = _verify_groups_args(groups, lib)
+    n = int(counts.sum())
+    rho_arr = None
+    if rho is not None:
+        rho = [[int(x) for x in r] for r in rho]
+        if len(rho) != len(groups) or any(len(r) != c for r, c in zip(rho, counts)):
+            raise G16Error(B.G16_ERR_INVALID, "one list of coefficients per group, one coefficient per proof")
+        flat = [x for r in rho for x in r]
+        if any(not 0 <= x < 1 << 128 for x in flat):
+            raise G16Error(B.G16_ERR_INVALID, "coefficients are integers in [1, 2^128)")
+        rho_arr = np.array([[x & 0xFFFFFFFFFFFFFFFF, x >> 64] for x in flat], dtype=np.uint64).reshape(n, 2)
+    ok = np.zeros(max(len(groups), 1), dtype=np.uint8)
+    structural = np.zeros(max(n, 1), dtype=np.uint8)
+    st = lib.g16_verify_aggregate_keys(device, vks, _np_ptr(counts), len(groups), _np_ptr(buf), _np_ptr(pubs),
+                                       _np_ptr(rho_arr) if rho_arr is not None and n else None, _np_ptr(ok),
+                                       _np_ptr(structural))
+    if st != B.G16_OK:
+        raise G16Error(st, "g16_verify_aggregate_keys failed")
+    verdicts = [bool(x) for x in ok[:len(groups)]]
+    if return_structural:
+        ends = np.cumsum(counts)
+        return verdicts, [[bool(x) for x in structural[e - c:e]] for e, c in zip(ends, counts)]
+    return verdicts
+
+
+def verify_batch_keys(groups, device=0, lib: Optional[B.Library] = None):
+    """verify_batch for proofs under MANY keys in one pass (g16_verify_batch_keys).  groups as
+    verify_aggregate_keys takes them; returns one list of bools per group, verify_batch's on that group."""
+    lib = lib or B.load()
+    groups = list(groups)
+    vks, counts, buf, pubs, keep = _verify_groups_args(groups, lib)
+    n = int(counts.sum())
+    ok = np.zeros(max(n, 1), dtype=np.uint8)
+    st = lib.g16_verify_batch_keys(device, vks, _np_ptr(counts), len(groups), _np_ptr(buf), _np_ptr(pubs),
+                                   _np_ptr(ok))
+    if st != B.G16_OK:
+        raise G16Error(st, "g16_verify_batch_keys failed")
+    ends = np.cumsum(counts)
+    return [[bool(x) for x in ok[e - c:e]] for e, c in zip(ends, counts)]
+
+
+def verify_batch_fast_keys(groups, device=0, lib: Optional[B.Library] = None):
+    """verify_batch_keys' lists at the cost of one aggregate pass when every proof is valid: ONE
+    verify_aggregate_keys call with fresh coefficients; then ONE verify_batch_keys call over the well-formed
+    proofs of the rejected groups only (malformed proofs are False).  At most two library calls whatever the
+    number of keys; equal to verify_batch_keys up to the 2^-127 soundness error per group."""
+    lib = lib or B.load()
+    groups = [(vk, list(proofs), list(public_inputs)) for vk, proofs, public_inputs in groups]
+    ok, structural = verify_aggregate_keys(groups, device=device, lib=lib, return_structural=True)
+    out = [[v] * len(s) for v, s in zip(ok, structural)]
+    again = []                                    # (group, indices of its well-formed proofs)
+    for k, (v, s) in enumerate(zip(ok, structural)):
+        rest = [i for i, w in enumerate(s) if w]
+        if not v and rest:
+            again.append((k, rest))
+    if again:
+        sub = [(groups[k][0], [groups[k][1][i] for i in rest], [groups[k][2][i] for i in rest]) for k, rest in again]
+        for (k, rest), got in zip(again, verify_batch_keys(sub, device=device, lib=lib)):
+            for i, v in zip(rest, got):
+                out[k][i] = v
     return out
 
 

@@ -172,6 +172,7 @@ ABI_SYMBOLS = [
     "g16_points_from_ark", "g16_points_to_ark", "g16_ark_proofs_read", "g16_ark_proofs_write", "g16_ark_pk_size",
     "g16_ark_pk_read", "g16_ark_pk_key", "g16_ark_pk_close", "g16_ark_pk_write", "g16_ark_vk_size", "g16_ark_vk_read",
     "g16_ark_vk_write", "g16_ark_pk_layout", "g16_ark_vk_layout",
+    "g16_verify_aggregate_keys", "g16_verify_batch_keys",
 ]
 
 
@@ -228,6 +229,9 @@ class Library:
             "g16_witness_host_buffer": (vp, [vp]),
             "g16_verify_batch": (C.c_int, [C.c_int, C.POINTER(VkDesc), vp, vp, C.c_uint32, vp]),
             "g16_verify_aggregate": (C.c_int, [C.c_int, C.POINTER(VkDesc), vp, vp, C.c_uint32, vp, vp, vp]),
+            "g16_verify_aggregate_keys": (C.c_int, [C.c_int, C.POINTER(C.POINTER(VkDesc)), vp, C.c_uint32, vp, vp,
+                                                    vp, vp, vp]),
+            "g16_verify_batch_keys": (C.c_int, [C.c_int, C.POINTER(C.POINTER(VkDesc)), vp, C.c_uint32, vp, vp, vp]),
             "g16_key_check": (C.c_int, [C.c_int, C.POINTER(KeyDesc), C.POINTER(VkDesc), vp, C.POINTER(KeyBadPoint),
                                         C.c_uint32, C.POINTER(KeyReportC)]),
             "g16_key_contribute": (C.c_int, [C.c_int, C.POINTER(KeyDesc), vp, vp, vp, vp, vp]),

@@ -22,6 +22,7 @@
 #include <memory>
 
 #include "pairing.h"
+#include "verify_agg.h"
 
 namespace g16 {
 namespace {
@@ -90,26 +91,7 @@ __global__ void __launch_bounds__(64) k_verify_batch(const VkDev* vk, const G1Af
 //   k_agg_tail    product of the per-block products, AND of the structural flags, final
 //                 exponentiation in one lane
 // No atomics: every reduction is a fixed tree, so the result does not depend on scheduling.
-constexpr uint32_t AGG_BLOCK = 64;
-
-struct AggKey {
-  G1Affine p[3];  // G1 sides paired with beta, gamma, delta
-};
-
-// sh[0] <- sum of sh[0 .. AGG_BLOCK): every lane of the block calls it, v = the lane's own term
-__device__ __forceinline__ void block_sum_g1(G1XYZZ* sh, G1XYZZ v) {
-  const uint32_t t = threadIdx.x;
-  sh[t] = v;
-#pragma unroll 1
-  for (uint32_t s = AGG_BLOCK / 2; s > 0; s >>= 1) {
-    __syncthreads();  // lanes < s read the upper half [s, 2s) and write the lower: one barrier per round
-    if (t < s) {
-      v.add(sh[t + s]);
-      sh[t] = v;
-    }
-  }
-  __syncthreads();
-}
+// AGG_BLOCK lanes per block, AggKey and block_sum_g1: verify_agg.h (shared with verify_keys.hip)
 
 __global__ void __launch_bounds__(AGG_BLOCK) k_agg_front(const VkDev* vk, uint32_t n_pub, const uint8_t* proofs,
                                                          const Fr* pubs, const uint64_t* rho, uint32_t n,

@@ -356,6 +356,40 @@ g16_status g16_verify_aggregate(int device, const g16_vk_desc* vk, const uint8_t
                                 const uint64_t* public_inputs, uint32_t n_proofs,
                                 const uint64_t* rho, uint8_t* ok_out, uint8_t* structural_out);
 
+/* Proofs under MANY keys in one pass.  A GROUP is one key together with the proofs under it: group k is
+ * vks[k] with counts[k] proofs.  The two calls above cost a serial chain (front, one Miller loop, one
+ * final exponentiation) that is almost flat in the batch size; a caller with n_keys keys pays it n_keys
+ * times, one key after the other.  Here all groups share every kernel launch and the final
+ * exponentiations of the groups run side by side, so n_keys groups cost about what one does.  The number
+ * of launches, allocations, copies and synchronisations does not depend on n_keys.
+ * proofs: N = sum_k counts[k] records of G16_PROOF_BYTES, group after group.
+ * public_inputs: the groups' blocks one after the other, group k's being counts[k] x (vks[k]->ic_count - 1)
+ *      x 4 u64 Montgomery Fr.  Keys may have different numbers of public inputs, including none.
+ * The same key may appear in several groups; the groups stay separate.  One device; nothing is combined
+ * across groups: there is no verdict "all groups hold" other than the AND of the per-group verdicts.
+ *
+ * g16_verify_aggregate_keys: ok_out[k] (n_keys bytes) is exactly what
+ *   g16_verify_aggregate(device, vks[k], group k's proofs, its public inputs, counts[k], its slice of rho, ..)
+ * writes to *ok_out: the same combined equation over group k ALONE, the same structural rules, the same
+ * treatment of infinity; an empty group gives 1.  Each group has its own 2^-127 bound.  Sums never cross
+ * a group boundary: the forged pair described above, split over two groups of the same key, fails both.
+ * rho: N x 2 u64 in the encoding of g16_verify_aggregate, every one non-zero, or NULL: drawn from the
+ *      operating system's CSPRNG exactly as that call does (no fixed fallback).
+ * structural_out: NULL, or N bytes as in that call, indexed over all N proofs.
+ *
+ * g16_verify_batch_keys: ok_out[i] (N bytes) is what g16_verify_batch writes for proof i under its
+ * group's key.
+ *
+ * G16_ERR_INVALID: a NULL where data is needed, vks[k] NULL, ic NULL or ic_count < 1 in any key, a zero
+ * rho entry, N + 3 n_keys not fitting 32 bits.  n_keys == 0: G16_OK, nothing is written.               */
+g16_status g16_verify_aggregate_keys(int device, const g16_vk_desc* const* vks, const uint32_t* counts,
+                                     uint32_t n_keys, const uint8_t* proofs, const uint64_t* public_inputs,
+                                     const uint64_t* rho, uint8_t* ok_out /* n_keys */,
+                                     uint8_t* structural_out /* sum(counts) or NULL */);
+g16_status g16_verify_batch_keys(int device, const g16_vk_desc* const* vks, const uint32_t* counts,
+                                 uint32_t n_keys, const uint8_t* proofs, const uint64_t* public_inputs,
+                                 uint8_t* ok_out /* sum(counts) */);
+
 /* ---- proving-key validation (not on the proving path) ------------------------------------------- */
 /* The loaders (g16_zkey_open, like the reference's deserialize_g1 / deserialize_g2, src/zkey.rs:328-360:
  * `new_unchecked`) copy the point sections of a key as they come, and g16_ctx_create builds tables from

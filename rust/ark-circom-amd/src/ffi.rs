@@ -309,6 +309,8 @@ extern "C" {
     pub fn g16_check_satisfied(device: c_int, a: *const g16_csr, b: *const g16_csr, c: *const g16_csr, num_constraints: u32, w: *const u64, n_vars: usize, first_unsatisfied: *mut i64) -> g16_status;
     pub fn g16_verify_batch(device: c_int, vk: *const g16_vk_desc, proofs: *const u8, public_inputs: *const u64, n_proofs: u32, ok_out: *mut u8) -> g16_status;
     pub fn g16_verify_aggregate(device: c_int, vk: *const g16_vk_desc, proofs: *const u8, public_inputs: *const u64, n_proofs: u32, rho: *const u64, ok_out: *mut u8, structural_out: *mut u8) -> g16_status;
+    pub fn g16_verify_aggregate_keys(device: c_int, vks: *const *const g16_vk_desc, counts: *const u32, n_keys: u32, proofs: *const u8, public_inputs: *const u64, rho: *const u64, ok_out: *mut u8, structural_out: *mut u8) -> g16_status;
+    pub fn g16_verify_batch_keys(device: c_int, vks: *const *const g16_vk_desc, counts: *const u32, n_keys: u32, proofs: *const u8, public_inputs: *const u64, ok_out: *mut u8) -> g16_status;
     pub fn g16_key_check(device: c_int, key: *const g16_key_desc, vk: *const g16_vk_desc, rho: *const u64, bad_out: *mut g16_key_bad_point, bad_cap: u32, report: *mut g16_key_report) -> g16_status;
     pub fn g16_key_contribute(device: c_int, key: *const g16_key_desc, d: *const u64, l_out: *mut u8, h_out: *mut u8, delta_g1_out: *mut u8, delta_g2_out: *mut u8) -> g16_status;
     pub fn g16_key_contribution_check(device: c_int, before: *const g16_key_desc, after: *const g16_key_desc, rho: *const u64, bad_out: *mut g16_key_bad_point, bad_cap: u32, report: *mut g16_contribution_report) -> g16_status;

@@ -26,7 +26,7 @@ mod verify;
 pub use ark_circom::{circom, read_zkey, CircomBuilder, CircomCircuit, CircomConfig, CircomReduction, Wasm, WitnessCalculator};
 pub use prover::{GpuError, GpuProver, Reduction, Shard};
 pub use reduction::GpuCircomReduction;
-pub use verify::{verify_aggregate, verify_batch};
+pub use verify::{verify_aggregate, verify_aggregate_keys, verify_batch, KeyGroup};
 
 use ark_bn254::{Bn254, Fr};
 use ark_groth16::Proof;
@@ -113,5 +113,12 @@ impl Groth16Gpu {
         let r = Fr::rand(rng);
         let s = Fr::rand(rng);
         prover.create_proof(r, s, &assignment)
+    }
+
+    /// Self-check of what several provers made, in one pass: `out[k]` = do all proofs of group k verify
+    /// under its key (`verify::verify_aggregate_keys`, coefficients drawn by the library)?  Groups are
+    /// independent; one device.
+    pub fn verify_aggregate_keys(groups: &[verify::KeyGroup], device: i32) -> Result<Vec<bool>, GpuError> {
+        verify::verify_aggregate_keys(groups, None, device)
     }
 }

@@ -98,3 +98,34 @@ pub fn verify_aggregate(
     }
     Ok(ok != 0)
 }
+
+/// One group of `verify_aggregate_keys`: a key with the proofs under it and their public inputs.
+pub type KeyGroup<'a> = (&'a VerifyingKey<Bn254>, &'a [Vec<Fr>], &'a [Proof<Bn254>]);
+
+/// Proofs under MANY keys in one pass (`g16_verify_aggregate_keys`): `out[k]` is what
+/// `verify_aggregate(groups[k].0, groups[k].1, groups[k].2, rho[k], device)` returns -- the combined
+/// check over group k alone, nothing is summed across groups -- for about the cost of one such call,
+/// whatever the number of keys.  `rho`: `None` (drawn by the library) or one slice per group, under
+/// the rules of `verify_aggregate`.
+pub fn verify_aggregate_keys(groups: &[KeyGroup], rho: Option<&[&[u128]]>, device: i32) -> Result<Vec<bool>, GpuError> {
+    if let Some(r) = rho {
+        if r.len() != groups.len() || r.iter().zip(groups).any(|(r, g)| r.len() != g.2.len()) {
+            return Err(GpuError::Library(ffi::G16_ERR_INVALID, "one coefficient per proof".into()));
+        }
+    }
+    let packed: Vec<Packed> = groups.iter().map(|(vk, inputs, proofs)| pack_batch(vk, inputs, proofs)).collect::<Result<_, _>>()?;
+    let descs: Vec<*const ffi::g16_vk_desc> = packed.iter().map(|p| &p.desc as *const _).collect();
+    let counts: Vec<u32> = groups.iter().map(|g| g.2.len() as u32).collect();
+    let raw: Vec<u8> = packed.iter().flat_map(|p| p.raw.iter().copied()).collect();
+    let pubs: Vec<u64> = packed.iter().flat_map(|p| p.pubs.iter().copied()).collect();
+    let words: Option<Vec<u64>> = rho.map(|r| r.iter().flat_map(|g| g.iter().flat_map(|x| [*x as u64, (*x >> 64) as u64])).collect());
+    let rho_ptr = words.as_ref().map_or(std::ptr::null(), |w| w.as_ptr());
+    let mut ok = vec![0u8; groups.len()];
+    let st = unsafe {
+        ffi::g16_verify_aggregate_keys(device, descs.as_ptr(), counts.as_ptr(), groups.len() as u32, raw.as_ptr(), pubs.as_ptr(), rho_ptr, ok.as_mut_ptr(), std::ptr::null_mut())
+    };
+    if st != ffi::G16_OK {
+        return Err(GpuError::Library(st, "g16_verify_aggregate_keys failed".into()));
+    }
+    Ok(ok.into_iter().map(|b| b != 0).collect())
+}
