@@ -41,7 +41,8 @@ __all__ = ["read_zkey", "R1CSFile", "R1CS", "CircomCircuit", "CircomBuilder", "C
            "ContributionReport", "Srs", "trapdoor_srs", "setup_from_srs", "check_key_circuit",
            "CircuitBindingReport", "read_ptau", "write_ptau", "check_srs", "SrsReport", "contribute_srs", "new_srs",
            "points_from_ark", "points_to_ark", "read_ark_key", "write_ark_key", "read_ark_vk", "write_ark_vk",
-           "proofs_from_ark", "proofs_to_ark", "ark_point_bytes"]
+           "proofs_from_ark", "proofs_to_ark", "ark_point_bytes", "rerandomize", "rerandomize_keys",
+           "rerandomize_times"]
 
 FR_MODULUS = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 
@@ -404,6 +405,13 @@ class Proof:
     def from_ark(raw, compressed=True, validate=True, device=0, lib: Optional[B.Library] = None) -> "Proof":
         """Proof::deserialize_compressed / _uncompressed of one proof (g16_ark_proofs_read)."""
         return proofs_from_ark(raw, 1, compressed=compressed, validate=validate, device=device, lib=lib)[0]
+
+    def rerandomize(self, vk, r1=None, r2=None, device=0, lib: Optional[B.Library] = None) -> "Proof":
+        """Groth16::rerandomize_proof of this proof (rerandomize): r1 in [1, r) and r2 in [0, r) as ints, or both
+        None: drawn by the library from the OS CSPRNG."""
+        if (r1 is None) != (r2 is None):
+            raise G16Error(B.G16_ERR_INVALID, "give r1 and r2, or neither")
+        return rerandomize(vk, [self], None if r1 is None else [(r1, r2)], device=device, lib=lib)[0]
 
 
 DEFAULT_TABLES = 0     # g16_options.fixed_tables when Prover(tables=None): 0 = the library decides
@@ -1636,6 +1644,110 @@ def verify_batch_fast_keys(groups, device=0, lib: Optional[B.Library] = None):
     return out
 
 
+def _delta_bytes(vk) -> bytes:
+    """delta in G2 of a VerifyingKey, or 128 bytes of it"""
+    d = bytes(vk.delta_g2) if hasattr(vk, "delta_g2") else bytes(vk)
+    if len(d) != 128:
+        raise G16Error(B.G16_ERR_INVALID, "vk is a VerifyingKey or the 128 bytes of delta_g2")
+    return d
+
+
+def _rerandomize_scalars(scalars, n, lib):
+    """[(r1, r2)] as ints -> (2n, 4) Montgomery rows, refusing what the library would refuse"""
+    if scalars is None:
+        return None
+    scalars = [(int(r1), int(r2)) for r1, r2 in scalars]
+    if len(scalars) != n:
+        raise G16Error(B.G16_ERR_INVALID, "one (r1, r2) per proof")
+    if any(not 0 < r1 < FR_MODULUS or not 0 <= r2 < FR_MODULUS for r1, r2 in scalars):
+        raise G16Error(B.G16_ERR_INVALID, "r1 is an integer in [1, r), r2 in [0, r)")
+    return fr_from_ints([x for pair in scalars for x in pair], lib) if n else None
+
+
+def rerandomize_keys(groups, scalars=None, device=0, lib: Optional[B.Library] = None, return_ok=False):
+    """Groth16::rerandomize_proof for proofs under MANY keys in one pass (g16_proofs_rerandomize_keys):
+      A' = r1^-1 A,  B' = r1 B + (r1 r2) delta,  C' = C + r2 A.
+    groups: a sequence of (vk, proofs); vk a VerifyingKey or the 128 bytes of its delta_g2, proofs Proof objects
+    or 256-byte strings.  Groups may be empty and a key may appear twice.  scalars: None (every (r1, r2) is drawn
+    by the library from the OS CSPRNG, never returned and wiped before the call returns) or one list of (r1, r2)
+    ints per group, r1 in [1, r), r2 in [0, r).  Returns one list of Proof per group; return_ok=True returns
+    (lists, [[proof i of group k passed the structural tests]]).  A proof that fails them (a coordinate >= q, A or
+    C off the curve, B off the twist) comes back as the all-zero record.  The subgroup test of B is NOT applied
+    and nothing is verified: the new proof is valid exactly when the old one was -- verify before or after."""
+    lib = lib or B.load()
+    groups = [(vk, list(proofs)) for vk, proofs in groups]
+    raws = [b"".join(p.raw if isinstance(p, Proof) else bytes(p) for p in proofs) for _, proofs in groups]
+    if any(len(r) % B.G16_PROOF_BYTES for r in raws):
+        raise G16Error(B.G16_ERR_INVALID, "a proof is 256 bytes")
+    counts = np.array([len(r) // B.G16_PROOF_BYTES for r in raws], dtype=np.uint32)
+    n = int(counts.sum())
+    sc = None
+    if scalars is not None:
+        scalars = [list(s) for s in scalars]
+        if len(scalars) != len(groups) or any(len(s) != c for s, c in zip(scalars, counts)):
+            raise G16Error(B.G16_ERR_INVALID, "one list of (r1, r2) per group, one pair per proof")
+        sc = _rerandomize_scalars([x for s in scalars for x in s], n, lib)
+    deltas = np.frombuffer(b"".join(_delta_bytes(vk) for vk, _ in groups), dtype=np.uint8)
+    buf = np.frombuffer(b"".join(raws), dtype=np.uint8)
+    out = np.zeros(max(n, 1) * B.G16_PROOF_BYTES, dtype=np.uint8)
+    ok = np.zeros(max(n, 1), dtype=np.uint8)
+    st = lib.g16_proofs_rerandomize_keys(device, _np_ptr(deltas) if len(groups) else None, _np_ptr(counts),
+                                         len(groups), _np_ptr(buf) if n else None,
+                                         _np_ptr(sc) if sc is not None else None, _np_ptr(out), _np_ptr(ok))
+    if st != B.G16_OK:
+        raise G16Error(st, "g16_proofs_rerandomize_keys failed")
+    raw = out.tobytes()
+    ends = [int(e) for e in np.cumsum(counts)]
+    res = [[Proof(raw[i * B.G16_PROOF_BYTES:(i + 1) * B.G16_PROOF_BYTES]) for i in range(e - int(c), e)]
+           for e, c in zip(ends, counts)]
+    if return_ok:
+        return res, [[bool(x) for x in ok[e - int(c):e]] for e, c in zip(ends, counts)]
+    return res
+
+
+def rerandomize(vk, proofs, scalars=None, device=0, lib: Optional[B.Library] = None, return_ok=False):
+    """Groth16::rerandomize_proof(vk, proof, rng) for a batch under one key on the GPU (g16_proofs_rerandomize),
+    one lane per proof:  A' = r1^-1 A,  B' = r1 B + (r1 r2) delta,  C' = C + r2 A.  The result verifies for exactly
+    the public inputs the input verifies for and is unlinkable to it; no witness and no proving key are needed.
+    vk: a VerifyingKey or the 128 bytes of its delta_g2; proofs: Proof objects or 256-byte strings; scalars: None
+    (drawn by the library from the OS CSPRNG, never returned) or one (r1, r2) of ints per proof, r1 in [1, r),
+    r2 in [0, r).  Returns a list of Proof; return_ok=True returns (proofs, [passed the structural tests]).
+    rerandomize_keys tells what is and what is not tested."""
+    lib = lib or B.load()
+    proofs = list(proofs)
+    raw = b"".join(p.raw if isinstance(p, Proof) else bytes(p) for p in proofs)
+    if len(raw) % B.G16_PROOF_BYTES:
+        raise G16Error(B.G16_ERR_INVALID, "a proof is 256 bytes")
+    n = len(raw) // B.G16_PROOF_BYTES
+    sc = _rerandomize_scalars(scalars, n, lib)
+    delta = np.frombuffer(_delta_bytes(vk), dtype=np.uint8)
+    buf = np.frombuffer(raw, dtype=np.uint8)
+    out = np.zeros(max(n, 1) * B.G16_PROOF_BYTES, dtype=np.uint8)
+    ok = np.zeros(max(n, 1), dtype=np.uint8)
+    st = lib.g16_proofs_rerandomize(device, _np_ptr(delta), _np_ptr(buf) if n else None, n,
+                                    _np_ptr(sc) if sc is not None else None, _np_ptr(out), _np_ptr(ok))
+    if st != B.G16_OK:
+        raise G16Error(st, "g16_proofs_rerandomize failed")
+    got = out.tobytes()
+    res = [Proof(got[i * B.G16_PROOF_BYTES:(i + 1) * B.G16_PROOF_BYTES]) for i in range(n)]
+    if return_ok:
+        return res, [bool(x) for x in ok[:n]]
+    return res
+
+
+RERANDOMIZE_PHASES = ("upload", "prepare", "mul_g1", "mul_g2", "affine", "download")
+
+
+def rerandomize_times(lib: Optional[B.Library] = None) -> dict:
+    """milliseconds of device time per phase of this thread's last rerandomize / rerandomize_keys
+    (g16_proofs_rerandomize_times): prepare = structural tests + scalars; mul_g1 and mul_g2 run side by side on two
+    streams, so the sum exceeds the wall time"""
+    lib = lib or B.load()
+    ms = (C.c_float * len(RERANDOMIZE_PHASES))()
+    lib.check(lib.g16_proofs_rerandomize_times(ms, len(RERANDOMIZE_PHASES)))
+    return dict(zip(RERANDOMIZE_PHASES, (float(x) for x in ms)))
+
+
 class _Reduction:
     """R1CSToQAP::witness_map_from_matrices on the GPU; the subclass names the QAP."""
     NAME = "circom"
@@ -1692,6 +1804,13 @@ class Groth16:
     def verify(vk: "VerifyingKey", public_inputs, proof, **kw) -> bool:
         """Groth16::verify_with_processed_vk(&process_vk(&vk), inputs, &proof) on the GPU"""
         return verify_batch(vk, [proof], [list(public_inputs)], **kw)[0]
+
+    @staticmethod
+    def rerandomize_proof(vk: "VerifyingKey", proof, rng=None, **kw) -> Proof:
+        """Groth16::rerandomize_proof(&vk, &proof, rng) on the GPU: r1 != 0 and r2 from rng (anything with
+        randrange); rng=None lets the library draw them from the OS CSPRNG.  rerandomize does a batch."""
+        scalars = None if rng is None else [(rng.randrange(1, FR_MODULUS), rng.randrange(FR_MODULUS))]
+        return rerandomize(vk, [proof], scalars, **kw)[0]
 
     @staticmethod
     def create_proof_with_reduction_and_matrices(pk: ProvingKey, r, s, matrices: ConstraintMatrices,

@@ -173,6 +173,7 @@ ABI_SYMBOLS = [
     "g16_ark_pk_read", "g16_ark_pk_key", "g16_ark_pk_close", "g16_ark_pk_write", "g16_ark_vk_size", "g16_ark_vk_read",
     "g16_ark_vk_write", "g16_ark_pk_layout", "g16_ark_vk_layout",
     "g16_verify_aggregate_keys", "g16_verify_batch_keys",
+    "g16_proofs_rerandomize", "g16_proofs_rerandomize_keys", "g16_proofs_rerandomize_times",
 ]
 
 
@@ -315,6 +316,9 @@ class Library:
             "g16_ark_vk_write": (C.c_int, [C.c_int, C.c_uint32, C.POINTER(VkDesc), vp, C.c_size_t]),
             "g16_ark_pk_layout": (C.c_int, [vp, C.c_size_t, C.c_uint32, C.POINTER(ArkLayout)]),
             "g16_ark_vk_layout": (C.c_int, [vp, C.c_size_t, C.c_uint32, C.POINTER(ArkLayout)]),
+            "g16_proofs_rerandomize": (C.c_int, [C.c_int, vp, vp, C.c_uint32, vp, vp, vp]),
+            "g16_proofs_rerandomize_keys": (C.c_int, [C.c_int, vp, vp, C.c_uint32, vp, vp, vp, vp]),
+            "g16_proofs_rerandomize_times": (C.c_int, [C.POINTER(C.c_float), C.c_uint32]),
         }
         # measurement builds only (make EXTRA=-DG16_DEBUG_ABI; include/g16_amd.h): not an ABI symbol, never "missing"
         optional = {"g16_debug_alu_bench": (C.c_int, [C.c_int, C.c_int, C.c_uint32, C.c_uint32,

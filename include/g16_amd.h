@@ -830,6 +830,61 @@ g16_status g16_ark_vk_read(int device, uint32_t flags, const uint8_t* data, size
                            uint8_t* ic_out, uint32_t ic_cap);
 g16_status g16_ark_vk_write(int device, uint32_t flags, const g16_vk_desc* vk, uint8_t* out, size_t cap);
 
+/* ---- proof re-randomisation (not on the proving path) ----------------------------------------------- */
+/* g16_proofs_rerandomize is ark_groth16::Groth16::rerandomize_proof(vk, proof, rng) for n_proofs proofs under
+ * one key, one GPU lane per proof.  For a proof (A, B, C), the key's delta in G2, and r1 != 0, r2 in Fr:
+ *   A' = r1^-1 A        B' = r1 B + (r1 r2) delta        C' = C + r2 A
+ * (A', B', C') verifies for exactly the public inputs (A, B, C) verifies for and, for uniform (r1, r2), is
+ * uniformly distributed among the proofs that do: a relayer makes a proof unlinkable to the one it received
+ * without knowing the witness.  An invalid proof stays invalid.  Only delta_g2 of the key is used.
+ *
+ * proofs / proofs_out: n_proofs x G16_PROOF_BYTES (A | B | C as g16_prove writes them).  proofs_out may be
+ *          exactly proofs (in place); any other overlap is unsupported.
+ * scalars: n_proofs x 2 x 4 u64 Montgomery Fr, (r1, r2) per proof, r1 in [1, r), r2 in [0, r).  r1 == 0, or any
+ *          value whose words are not below r: G16_ERR_INVALID, decided before any output byte is written.
+ *          NULL: every r1 is drawn uniformly from [1, r) and every r2 from [0, r) from the operating system's
+ *          CSPRNG by rejection; a failure to get randomness is G16_ERR_INTERNAL, never a fixed fallback.
+ *          Given or drawn, the scalars and everything derived from them are wiped on the host and zeroed on
+ *          the device before the call returns; drawn scalars are never returned.
+ * ok_out:  NULL, or n_proofs bytes: 1 where proof i passed the structural tests, applied before any arithmetic
+ *          on it: every stored coordinate canonical (< q), A and C on the curve, B on the twist.  A proof that
+ *          fails gets ok_out[i] = 0 and an all-zero 256-byte record; its neighbours are unaffected.
+ *          NOT applied: the prime-order subgroup test of B ([r] B = infinity, which g16_verify_batch applies).
+ *          It would cost a third G2 ladder per proof, and the map above is well defined on the whole twist: a B
+ *          outside G2 is transformed like any other (ok = 1) and the result fails verification as the input
+ *          does.  A caller that forwards untrusted proofs verifies them first or afterwards; ok = 1 says
+ *          nothing about validity.  delta_g2 comes from the caller's own key and is not tested.
+ * The all-zero encoding is the point at infinity and is an operand like any other, in the proof or as delta;
+ * equal and opposite operands (B = +-delta, C = +-A) take the doubling and cancelling branches of the addition.
+ * n_proofs == 0: G16_OK, nothing is written.  A NULL where data is needed (delta_g2, proofs, proofs_out), a
+ * device out of range, more than 2^24 - 1 proofs: G16_ERR_INVALID, nothing is written.
+ *
+ * g16_proofs_rerandomize_keys: proofs under MANY keys in the same launches.  Group k is counts[k] consecutive
+ * proofs under delta_g2s[k] (n_keys x 128 bytes); proofs, scalars, proofs_out and ok_out run over all
+ * N = sum_k counts[k] proofs, group after group.  Groups may be empty and the same delta may appear twice.  The
+ * result is the concatenation of the one-key calls on the groups with the matching scalar slices; the number
+ * of launches, allocations and copies does not depend on n_keys (g16_proofs_rerandomize is its n_keys == 1
+ * case).  n_keys == 0 or N == 0: G16_OK, nothing is written.  counts NULL: G16_ERR_INVALID.
+ *
+ * One lane per proof: A' and C' are two 256-position ladders over Fq with a mixed addition of the affine A on
+ * the lane's own bit (C is added at the end); B' is ONE joint ladder over Fq2 -- one doubling chain, a mixed
+ * addition of B on the bit of r1 and one of delta on the bit of r1 r2 -- with delta, the same for every lane of
+ * a block, held outside the lanes' registers.  r1^-1 is computed on the device.  One shared inversion per 8
+ * points brings the results back to affine.  The G1 and the G2 kernels run on two streams.  Standalone like
+ * g16_verify_batch: no ctx is needed, a ctx alive on the device is left untouched.  No atomics: with given
+ * scalars the same bytes on every run.  G16_ERR_NO_DEVICE without a device: there is no CPU fallback.
+ *
+ * g16_proofs_rerandomize_times: milliseconds of device time the calling thread's last call spent in 0 upload,
+ * 1 structural tests + scalar preparation, 2 G1 ladders, 3 the G2 ladder, 4 affine passes (G1 + G2), 5 download;
+ * 2 and 3 run side by side, so the sum exceeds the wall time; entries from 6 on are 0. */
+g16_status g16_proofs_rerandomize(int device, const uint8_t delta_g2[128], const uint8_t* proofs, uint32_t n_proofs,
+                                  const uint64_t* scalars /* n x 2 x 4 u64 Montgomery Fr (r1, r2), or NULL */,
+                                  uint8_t* proofs_out, uint8_t* ok_out /* n bytes or NULL */);
+g16_status g16_proofs_rerandomize_keys(int device, const uint8_t* delta_g2s /* n_keys x 128 */, const uint32_t* counts,
+                                       uint32_t n_keys, const uint8_t* proofs, const uint64_t* scalars,
+                                       uint8_t* proofs_out, uint8_t* ok_out);
+g16_status g16_proofs_rerandomize_times(float* ms, uint32_t cap);   /* per-phase device ms of the last call on this thread */
+
 /* ---- loaders (host side, C++): see g16_loaders.h ---------------------------------------------- */
 
 #ifdef __cplusplus

@@ -342,6 +342,9 @@ extern "C" {
     pub fn g16_ark_vk_size(flags: u32, n_public: u64) -> u64;
     pub fn g16_ark_vk_read(device: c_int, flags: u32, data: *const u8, len: usize, vk: *mut g16_vk_desc, ic_out: *mut u8, ic_cap: u32) -> g16_status;
     pub fn g16_ark_vk_write(device: c_int, flags: u32, vk: *const g16_vk_desc, out: *mut u8, cap: usize) -> g16_status;
+    pub fn g16_proofs_rerandomize(device: c_int, delta_g2: *const u8, proofs: *const u8, n_proofs: u32, scalars: *const u64, proofs_out: *mut u8, ok_out: *mut u8) -> g16_status;
+    pub fn g16_proofs_rerandomize_keys(device: c_int, delta_g2s: *const u8, counts: *const u32, n_keys: u32, proofs: *const u8, scalars: *const u64, proofs_out: *mut u8, ok_out: *mut u8) -> g16_status;
+    pub fn g16_proofs_rerandomize_times(ms: *mut c_float, cap: u32) -> g16_status;
 
     // ---- include/g16_loaders.h -----------------------------------------------------------------
     pub fn g16_loader_last_error() -> *const c_char;

@@ -26,7 +26,7 @@ mod verify;
 pub use ark_circom::{circom, read_zkey, CircomBuilder, CircomCircuit, CircomConfig, CircomReduction, Wasm, WitnessCalculator};
 pub use prover::{GpuError, GpuProver, Reduction, Shard};
 pub use reduction::GpuCircomReduction;
-pub use verify::{verify_aggregate, verify_aggregate_keys, verify_batch, KeyGroup};
+pub use verify::{rerandomize_proofs, verify_aggregate, verify_aggregate_keys, verify_batch, KeyGroup};
 
 use ark_bn254::{Bn254, Fr};
 use ark_groth16::Proof;
@@ -120,5 +120,30 @@ impl Groth16Gpu {
     /// independent; one device.
     pub fn verify_aggregate_keys(groups: &[verify::KeyGroup], device: i32) -> Result<Vec<bool>, GpuError> {
         verify::verify_aggregate_keys(groups, None, device)
+    }
+
+    /// `Groth16::<Bn254>::rerandomize_proof(&vk, &proof, rng)` on the GPU: `r1 != 0` and `r2` from `rng`.
+    pub fn rerandomize_proof<R: Rng>(
+        vk: &ark_groth16::VerifyingKey<Bn254>,
+        proof: &Proof<Bn254>,
+        rng: &mut R,
+        device: i32,
+    ) -> Result<Proof<Bn254>, GpuError> {
+        let mut r1 = Fr::rand(rng);
+        while r1 == Fr::from(0u64) {
+            r1 = Fr::rand(rng);
+        }
+        let r2 = Fr::rand(rng);
+        Ok(verify::rerandomize_proofs(vk, std::slice::from_ref(proof), Some(&[(r1, r2)][..]), device)?.remove(0))
+    }
+
+    /// A whole batch under one key in one pass (`g16_proofs_rerandomize`); every `(r1, r2)` is drawn by the
+    /// library from the operating system's CSPRNG, never returned and wiped before the call returns.
+    pub fn rerandomize_proofs(
+        vk: &ark_groth16::VerifyingKey<Bn254>,
+        proofs: &[Proof<Bn254>],
+        device: i32,
+    ) -> Result<Vec<Proof<Bn254>>, GpuError> {
+        verify::rerandomize_proofs(vk, proofs, None, device)
     }
 }

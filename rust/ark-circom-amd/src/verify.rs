@@ -129,3 +129,45 @@ pub fn verify_aggregate_keys(groups: &[KeyGroup], rho: Option<&[&[u128]]>, devic
     }
     Ok(ok.into_iter().map(|b| b != 0).collect())
 }
+
+/// `Groth16::<Bn254>::rerandomize_proof(vk, proof, rng)` for a batch under one key on the GPU
+/// (`g16_proofs_rerandomize`), one lane per proof:
+/// `A' = r1^-1 A`, `B' = r1 B + (r1 r2) delta`, `C' = C + r2 A`.  `scalars`: `None` (the library draws every
+/// `(r1, r2)` from the operating system's CSPRNG and wipes them) or one `(r1, r2)` per proof with `r1 != 0`.
+/// Nothing is verified: the new proof is valid exactly when the old one was.
+pub fn rerandomize_proofs(
+    vk: &VerifyingKey<Bn254>,
+    proofs: &[Proof<Bn254>],
+    scalars: Option<&[(Fr, Fr)]>,
+    device: i32,
+) -> Result<Vec<Proof<Bn254>>, GpuError> {
+    let n = proofs.len();
+    let words: Option<Vec<u64>> = match scalars {
+        Some(s) if s.len() != n => return Err(GpuError::Library(ffi::G16_ERR_INVALID, "one (r1, r2) per proof".into())),
+        Some(s) => Some(s.iter().flat_map(|(r1, r2)| pack::fr_words(r1).into_iter().chain(pack::fr_words(r2))).collect()),
+        None => None,
+    };
+    let mut delta = [0u8; 128];
+    pack::pack_g2(&vk.delta_g2, &mut delta);
+    let mut raw = vec![0u8; ffi::G16_PROOF_BYTES * n];
+    for (p, o) in proofs.iter().zip(raw.chunks_exact_mut(ffi::G16_PROOF_BYTES)) {
+        pack::pack_g1(&p.a, &mut o[0..64]);
+        pack::pack_g2(&p.b, &mut o[64..192]);
+        pack::pack_g1(&p.c, &mut o[192..256]);
+    }
+    let sc_ptr = words.as_ref().map_or(std::ptr::null(), |w| w.as_ptr());
+    // in place: proofs_out == proofs is supported
+    let st = unsafe {
+        ffi::g16_proofs_rerandomize(device, delta.as_ptr(), raw.as_ptr(), n as u32, sc_ptr, raw.as_mut_ptr(), std::ptr::null_mut())
+    };
+    if st != ffi::G16_OK {
+        return Err(GpuError::Library(st, "g16_proofs_rerandomize failed".into()));
+    }
+    Ok(raw
+        .chunks_exact(ffi::G16_PROOF_BYTES)
+        .map(|c| {
+            let rec: &[u8; 256] = c.try_into().expect("256-byte record");
+            pack::unpack_proof(rec)
+        })
+        .collect())
+}
