@@ -42,7 +42,8 @@ __all__ = ["read_zkey", "R1CSFile", "R1CS", "CircomCircuit", "CircomBuilder", "C
            "CircuitBindingReport", "read_ptau", "write_ptau", "check_srs", "SrsReport", "contribute_srs", "new_srs",
            "points_from_ark", "points_to_ark", "read_ark_key", "write_ark_key", "read_ark_vk", "write_ark_vk",
            "proofs_from_ark", "proofs_to_ark", "ark_point_bytes", "rerandomize", "rerandomize_keys",
-           "rerandomize_times"]
+           "rerandomize_times", "PreparedVerifyingKey", "prepare_verifying_key", "verify_prepared", "pairing_check",
+           "verify_prepared_times"]
 
 FR_MODULUS = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 
@@ -1748,6 +1749,101 @@ def rerandomize_times(lib: Optional[B.Library] = None) -> dict:
     return dict(zip(RERANDOMIZE_PHASES, (float(x) for x in ms)))
 
 
+class PreparedVerifyingKey:
+    """Groth16::process_vk's PreparedVerifyingKey, resident on the device (g16_pvk): the tested key, the Miller value
+    of (beta, -alpha) and the line tables of gamma and delta.  prepare_verifying_key makes one; verify_prepared uses
+    it; close() (or the garbage collector) releases it."""
+
+    def __init__(self, lib, ptr, n_public, device):
+        self.lib, self._ptr, self.n_public, self.device = lib, ptr, n_public, device
+
+    def alpha_beta(self) -> bytes:
+        """the stored Miller value of (beta, -alpha): 12 x 32 bytes, coefficient of w^i at 32 i, Montgomery"""
+        out = np.zeros(384, dtype=np.uint8)
+        self.lib.check(self.lib.g16_pvk_alpha_beta(self._handle(), _np_ptr(out)))
+        return out.tobytes()
+
+    def _handle(self):
+        if not self._ptr:
+            raise G16Error(B.G16_ERR_INVALID, "the prepared verifying key is closed")
+        return self._ptr
+
+    def close(self):
+        if self._ptr:
+            self.lib.g16_pvk_destroy(self._ptr)
+        self._ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def prepare_verifying_key(vk: "VerifyingKey", device=0, lib: Optional[B.Library] = None) -> PreparedVerifyingKey:
+    """Groth16::process_vk(&vk) on the GPU (g16_pvk_create).  The key is TESTED (verify_batch does not): a
+    non-canonical coordinate, a point off its curve or a G2 point outside the subgroup raises G16Error
+    (G16_ERR_INVALID) naming the point."""
+    lib = lib or B.load()
+    d, _ic = _vk_desc(vk)
+    h = C.c_void_p()
+    lib.check(lib.g16_pvk_create(device, C.byref(d), C.byref(h)))
+    return PreparedVerifyingKey(lib, h, _ic.shape[0] - 1, device)
+
+
+def verify_prepared(pvk: PreparedVerifyingKey, proofs, public_inputs):
+    """Groth16::verify_with_processed_vk for a batch under a prepared key (g16_verify_prepared): one workgroup per
+    proof, the low-latency form.  Arguments and verdicts are verify_batch's.  Returns a list of bools."""
+    lib = pvk.lib
+    raw = b"".join(p.raw if isinstance(p, Proof) else bytes(p) for p in proofs)
+    n = len(raw) // B.G16_PROOF_BYTES
+    if len(public_inputs) != n:
+        raise G16Error(B.G16_ERR_INVALID, "one public-input vector per proof")
+    flat = []
+    for pi in public_inputs:
+        if len(pi) != pvk.n_public:
+            raise G16Error(B.G16_ERR_INVALID, "MalformedVerifyingKey: wrong number of public inputs")
+        flat.extend(pi)
+    pubs = _as_fr(flat, lib) if (flat and not isinstance(flat[0], np.ndarray)) else \
+        (np.ascontiguousarray(np.stack(flat)) if flat else np.zeros((0, 4), np.uint64))
+    buf = np.frombuffer(raw, dtype=np.uint8)
+    ok = np.zeros(max(n, 1), dtype=np.uint8)
+    st = lib.g16_verify_prepared(pvk._handle(), _np_ptr(buf) if n else None, _np_ptr(pubs) if len(flat) else None, n,
+                                 _np_ptr(ok))
+    if st != B.G16_OK:
+        raise G16Error(st, "g16_verify_prepared failed")
+    return [bool(x) for x in ok[:n]]
+
+
+def pairing_check(g1_points, g2_points, device=0, lib: Optional[B.Library] = None) -> bool:
+    """prod_i e(P_i, Q_i) == 1 for 1 to 16 pairs on the wave-cooperative pairing (g16_pairing_check).  g1_points:
+    64-byte packed G1 points, g2_points: 128-byte packed G2 points (all-zero = infinity: the pair contributes 1).
+    A malformed point (non-canonical word, off its curve, Q outside G2) gives False."""
+    lib = lib or B.load()
+    g1 = np.frombuffer(b"".join(bytes(p) for p in g1_points), dtype=np.uint8)
+    g2 = np.frombuffer(b"".join(bytes(q) for q in g2_points), dtype=np.uint8)
+    n = len(g1_points)
+    if n != len(g2_points) or g1.shape[0] != 64 * n or g2.shape[0] != 128 * n:
+        raise G16Error(B.G16_ERR_INVALID, "one 64-byte G1 point per 128-byte G2 point")
+    ok = np.zeros(1, dtype=np.uint8)
+    st = lib.g16_pairing_check(device, _np_ptr(g1) if n else None, _np_ptr(g2) if n else None, n, _np_ptr(ok))
+    if st != B.G16_OK:
+        raise G16Error(st, "g16_pairing_check failed: 1 to 16 pairs")
+    return bool(ok[0])
+
+
+VERIFY_PREPARED_PHASES = ("upload", "inputs", "g2_tests", "pairing", "download", "prepare")
+
+
+def verify_prepared_times(lib: Optional[B.Library] = None) -> dict:
+    """milliseconds of device time per phase of this thread's last verify_prepared (g16_verify_prepared_times):
+    g2_tests runs beside inputs and pairing on a second stream; prepare is the thread's last prepare_verifying_key"""
+    lib = lib or B.load()
+    ms = (C.c_float * len(VERIFY_PREPARED_PHASES))()
+    lib.check(lib.g16_verify_prepared_times(ms, len(VERIFY_PREPARED_PHASES)))
+    return dict(zip(VERIFY_PREPARED_PHASES, (float(x) for x in ms)))
+
+
 class _Reduction:
     """R1CSToQAP::witness_map_from_matrices on the GPU; the subclass names the QAP."""
     NAME = "circom"
@@ -1804,6 +1900,16 @@ class Groth16:
     def verify(vk: "VerifyingKey", public_inputs, proof, **kw) -> bool:
         """Groth16::verify_with_processed_vk(&process_vk(&vk), inputs, &proof) on the GPU"""
         return verify_batch(vk, [proof], [list(public_inputs)], **kw)[0]
+
+    @staticmethod
+    def process_vk(vk: "VerifyingKey", **kw) -> PreparedVerifyingKey:
+        """Groth16::process_vk(&vk) on the GPU (prepare_verifying_key): the key is tested and its tables built once"""
+        return prepare_verifying_key(vk, **kw)
+
+    @staticmethod
+    def verify_with_processed_vk(pvk: PreparedVerifyingKey, public_inputs, proof) -> bool:
+        """Groth16::verify_with_processed_vk(&pvk, inputs, &proof) on the GPU, one workgroup for the proof"""
+        return verify_prepared(pvk, [proof], [list(public_inputs)])[0]
 
     @staticmethod
     def rerandomize_proof(vk: "VerifyingKey", proof, rng=None, **kw) -> Proof:

@@ -174,6 +174,8 @@ ABI_SYMBOLS = [
     "g16_ark_vk_write", "g16_ark_pk_layout", "g16_ark_vk_layout",
     "g16_verify_aggregate_keys", "g16_verify_batch_keys",
     "g16_proofs_rerandomize", "g16_proofs_rerandomize_keys", "g16_proofs_rerandomize_times",
+    "g16_pvk_create", "g16_pvk_destroy", "g16_pvk_alpha_beta", "g16_verify_prepared", "g16_pairing_check",
+    "g16_verify_prepared_times",
 ]
 
 
@@ -319,6 +321,12 @@ class Library:
             "g16_proofs_rerandomize": (C.c_int, [C.c_int, vp, vp, C.c_uint32, vp, vp, vp]),
             "g16_proofs_rerandomize_keys": (C.c_int, [C.c_int, vp, vp, C.c_uint32, vp, vp, vp, vp]),
             "g16_proofs_rerandomize_times": (C.c_int, [C.POINTER(C.c_float), C.c_uint32]),
+            "g16_pvk_create": (C.c_int, [C.c_int, C.POINTER(VkDesc), C.POINTER(vp)]),
+            "g16_pvk_destroy": (None, [vp]),
+            "g16_pvk_alpha_beta": (C.c_int, [vp, vp]),
+            "g16_verify_prepared": (C.c_int, [vp, vp, vp, C.c_uint32, vp]),
+            "g16_pairing_check": (C.c_int, [C.c_int, vp, vp, C.c_uint32, vp]),
+            "g16_verify_prepared_times": (C.c_int, [C.POINTER(C.c_float), C.c_uint32]),
         }
         # measurement builds only (make EXTRA=-DG16_DEBUG_ABI; include/g16_amd.h): not an ABI symbol, never "missing"
         optional = {"g16_debug_alu_bench": (C.c_int, [C.c_int, C.c_int, C.c_uint32, C.c_uint32,

@@ -22,6 +22,13 @@ std::mutex g_err_mu;
 std::string g_create_error;
 }  // namespace
 
+namespace g16 {
+// for the create calls of other translation units (g16_pvk_create): the message g16_last_error(NULL) returns
+void set_create_error(const std::string& msg) {
+  std::lock_guard<std::mutex> g(g_err_mu);
+  g_create_error = msg;
+}
+}  // namespace g16
 
 namespace {
 

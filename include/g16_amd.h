@@ -885,6 +885,47 @@ g16_status g16_proofs_rerandomize_keys(int device, const uint8_t* delta_g2s /* n
                                        uint8_t* proofs_out, uint8_t* ok_out);
 g16_status g16_proofs_rerandomize_times(float* ms, uint32_t cap);   /* per-phase device ms of the last call on this thread */
 
+/* ---- low-latency verification: a prepared verifying key (not on the proving path) -------------------- */
+/* g16_verify_batch and g16_verify_aggregate check a proof in ONE lane: right for tens of thousands of proofs, some
+ * hundred milliseconds for one.  These calls check a proof in one WORKGROUP, the Fq12 arithmetic spread over its 64
+ * lanes, under a key prepared once.
+ *
+ * g16_pvk_create is Groth16::process_vk: a device-resident handle with -alpha, beta, gamma, delta, the IC row, the
+ *   Frobenius constants, the Miller value of (beta, -alpha) and the line coefficients of gamma and of delta for every
+ *   step of the Miller loop (ark-ec's G2Prepared).  Unlike g16_verify_batch it TESTS the key: every coordinate
+ *   canonical, alpha and the IC points on the curve, beta, gamma and delta on the twist and in G2.  A key that fails:
+ *   G16_ERR_INVALID, and g16_last_error(NULL) names the point (alpha_g1, beta_g2, gamma_g2, delta_g2,
+ *   gamma_abc_g1[j]) and the reason.  A point at infinity is accepted; its pair contributes 1.
+ * g16_pvk_alpha_beta: the stored Miller value of (beta, -alpha), 12 Fq: out[32 i ..] = the coefficient of w^i in
+ *   Fq12 = Fq[w] / (w^12 - 18 w^6 + 82), 8 x u32 Montgomery.  Its final exponentiation is e(-alpha, beta).
+ * g16_verify_prepared is verify_with_processed_vk for n_proofs >= 0 proofs.  proofs, public_inputs and every rule
+ *   are g16_verify_batch's, and ok_out[i] is exactly its verdict under the same key: the structural tests come
+ *   first (canonical words, A and C on the curve, B on the twist and in the subgroup), a malformed proof gets 0 and
+ *   its neighbours are untouched.  n_proofs == 0: G16_OK, nothing is written.  Calls on one handle serialise on a
+ *   mutex in the handle; different handles run side by side.  The call uses the handle's own two streams and
+ *   synchronises THOSE, not the device: a prover on the same card is not stalled.  Per proof: X = IC_0 + sum pub_j
+ *   IC_{j+1} with one lane per term, ONE Miller loop for (A, B), (-X, gamma), (-C, delta) (64 squarings; the lines
+ *   of gamma and delta from the handle's tables, those of B from inversion-free projective steps), the stored
+ *   (beta, -alpha) value, one final exponentiation with one inversion; the subgroup test of B (psi(B) = [6 x^2] B,
+ *   127 bits) runs beside all of that on the second stream.
+ * g16_pairing_check: *ok_out = 1 iff prod_i e(P_i, Q_i) = 1 for 1 <= n_pairs <= 16 pairs, every pair through the
+ *   on-the-fly line path in one workgroup, under the same structural tests (a malformed point: *ok_out = 0); a pair
+ *   with an infinite side contributes 1.  Standalone: no handle.
+ * g16_verify_prepared_times: device milliseconds of the calling thread's last g16_verify_prepared in 0 upload,
+ *   1 prepared inputs, 2 the tests of B (beside 1 and 3), 3 Miller loop + final exponentiation, 4 download; 5 is the
+ *   preparation kernel of the thread's last g16_pvk_create; entries from 6 on are 0.
+ * Not here: fixed-base tables for IC in the handle (they would remove the ladder of X), multi-device forms.
+ * G16_ERR_NO_DEVICE without a device: there is no CPU fallback.                                                  */
+typedef struct g16_pvk g16_pvk;
+g16_status g16_pvk_create(int device, const g16_vk_desc* vk, g16_pvk** out);
+void g16_pvk_destroy(g16_pvk* pvk);
+g16_status g16_pvk_alpha_beta(const g16_pvk* pvk, uint8_t out[384]);
+g16_status g16_verify_prepared(g16_pvk* pvk, const uint8_t* proofs, const uint64_t* public_inputs, uint32_t n_proofs,
+                               uint8_t* ok_out);
+g16_status g16_pairing_check(int device, const uint8_t* g1 /* n x 64 */, const uint8_t* g2 /* n x 128 */,
+                             uint32_t n_pairs, uint8_t* ok_out);
+g16_status g16_verify_prepared_times(float* ms, uint32_t cap);
+
 /* ---- loaders (host side, C++): see g16_loaders.h ---------------------------------------------- */
 
 #ifdef __cplusplus

@@ -76,6 +76,10 @@ pub struct g16_ptau {
 pub struct g16_ark_pk {
     _private: [u8; 0],
 }
+#[repr(C)]
+pub struct g16_pvk {
+    _private: [u8; 0],
+}
 
 // arkworks serialization (include/g16_amd.h): the extra per-point reason bit, the groups, the flags
 pub const G16_KEY_BAD_ENCODING: u32 = 8;
@@ -345,6 +349,12 @@ extern "C" {
     pub fn g16_proofs_rerandomize(device: c_int, delta_g2: *const u8, proofs: *const u8, n_proofs: u32, scalars: *const u64, proofs_out: *mut u8, ok_out: *mut u8) -> g16_status;
     pub fn g16_proofs_rerandomize_keys(device: c_int, delta_g2s: *const u8, counts: *const u32, n_keys: u32, proofs: *const u8, scalars: *const u64, proofs_out: *mut u8, ok_out: *mut u8) -> g16_status;
     pub fn g16_proofs_rerandomize_times(ms: *mut c_float, cap: u32) -> g16_status;
+    pub fn g16_pvk_create(device: c_int, vk: *const g16_vk_desc, out: *mut *mut g16_pvk) -> g16_status;
+    pub fn g16_pvk_destroy(pvk: *mut g16_pvk);
+    pub fn g16_pvk_alpha_beta(pvk: *const g16_pvk, out: *mut u8) -> g16_status;
+    pub fn g16_verify_prepared(pvk: *mut g16_pvk, proofs: *const u8, public_inputs: *const u64, n_proofs: u32, ok_out: *mut u8) -> g16_status;
+    pub fn g16_pairing_check(device: c_int, g1: *const u8, g2: *const u8, n_pairs: u32, ok_out: *mut u8) -> g16_status;
+    pub fn g16_verify_prepared_times(ms: *mut c_float, cap: u32) -> g16_status;
 
     // ---- include/g16_loaders.h -----------------------------------------------------------------
     pub fn g16_loader_last_error() -> *const c_char;

@@ -26,7 +26,7 @@ mod verify;
 pub use ark_circom::{circom, read_zkey, CircomBuilder, CircomCircuit, CircomConfig, CircomReduction, Wasm, WitnessCalculator};
 pub use prover::{GpuError, GpuProver, Reduction, Shard};
 pub use reduction::GpuCircomReduction;
-pub use verify::{rerandomize_proofs, verify_aggregate, verify_aggregate_keys, verify_batch, KeyGroup};
+pub use verify::{process_vk, rerandomize_proofs, verify_aggregate, verify_aggregate_keys, verify_batch, verify_prepared, GpuPreparedVerifyingKey, KeyGroup};
 
 use ark_bn254::{Bn254, Fr};
 use ark_groth16::Proof;

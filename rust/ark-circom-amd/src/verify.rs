@@ -171,3 +171,80 @@ pub fn rerandomize_proofs(
         })
         .collect())
 }
+
+/// `PreparedVerifyingKey<Bn254>` on the device (`g16_pvk`): what `Groth16Gpu::process_vk` returns.  The key has
+/// been tested (canonical coordinates, points on their curves, G2 points in the subgroup); the handle holds the
+/// Miller value of (beta, -alpha) and the line tables of gamma and delta.  Dropping it releases the device memory.
+pub struct GpuPreparedVerifyingKey {
+    ptr: *mut ffi::g16_pvk,
+    n_pub: usize,
+}
+
+// calls on one handle serialise on a mutex inside the library
+unsafe impl Send for GpuPreparedVerifyingKey {}
+unsafe impl Sync for GpuPreparedVerifyingKey {}
+
+impl Drop for GpuPreparedVerifyingKey {
+    fn drop(&mut self) {
+        unsafe { ffi::g16_pvk_destroy(self.ptr) }
+    }
+}
+
+/// `Groth16::<Bn254>::process_vk(vk)` on the GPU (`g16_pvk_create`)
+pub fn process_vk(vk: &VerifyingKey<Bn254>, device: i32) -> Result<GpuPreparedVerifyingKey, GpuError> {
+    let p = pack_batch(vk, &[], &[])?;
+    let mut ptr: *mut ffi::g16_pvk = std::ptr::null_mut();
+    let st = unsafe { ffi::g16_pvk_create(device, &p.desc, &mut ptr) };
+    if st != ffi::G16_OK {
+        let msg = unsafe { std::ffi::CStr::from_ptr(ffi::g16_last_error(std::ptr::null())) }.to_string_lossy().into_owned();
+        return Err(GpuError::Library(st, msg));
+    }
+    Ok(GpuPreparedVerifyingKey { ptr, n_pub: vk.gamma_abc_g1.len() - 1 })
+}
+
+/// `out[i]` = `verify_with_processed_vk(pvk, &public_inputs[i], &proofs[i])` (`g16_verify_prepared`): one
+/// workgroup per proof, the low-latency form; the verdicts are `verify_batch`'s.
+pub fn verify_prepared(
+    pvk: &GpuPreparedVerifyingKey,
+    public_inputs: &[Vec<Fr>],
+    proofs: &[Proof<Bn254>],
+) -> Result<Vec<bool>, GpuError> {
+    let n = proofs.len();
+    if public_inputs.len() != n || public_inputs.iter().any(|p| p.len() != pvk.n_pub) {
+        return Err(GpuError::Synthesis(ark_relations::r1cs::SynthesisError::MalformedVerifyingKey));
+    }
+    let mut raw = vec![0u8; ffi::G16_PROOF_BYTES * n];
+    for (p, o) in proofs.iter().zip(raw.chunks_exact_mut(ffi::G16_PROOF_BYTES)) {
+        pack::pack_g1(&p.a, &mut o[0..64]);
+        pack::pack_g2(&p.b, &mut o[64..192]);
+        pack::pack_g1(&p.c, &mut o[192..256]);
+    }
+    let mut pubs: Vec<u64> = Vec::with_capacity(4 * n * pvk.n_pub);
+    for v in public_inputs {
+        pubs.extend_from_slice(&pack::fr_vec_words(v));
+    }
+    let mut ok = vec![0u8; n];
+    let st = unsafe { ffi::g16_verify_prepared(pvk.ptr, raw.as_ptr(), pubs.as_ptr(), n as u32, ok.as_mut_ptr()) };
+    if st != ffi::G16_OK {
+        return Err(GpuError::Library(st, "g16_verify_prepared failed".into()));
+    }
+    Ok(ok.into_iter().map(|b| b != 0).collect())
+}
+
+impl crate::Groth16Gpu {
+    /// `Groth16::<Bn254>::process_vk(&vk)` on the GPU: the key is tested, its (beta, -alpha) Miller value and
+    /// the line tables of gamma and delta are built once and stay on the device.
+    pub fn process_vk(vk: &VerifyingKey<Bn254>, device: i32) -> Result<GpuPreparedVerifyingKey, GpuError> {
+        process_vk(vk, device)
+    }
+
+    /// `Groth16::<Bn254>::verify_with_processed_vk(&pvk, public_inputs, &proof)` on the GPU: one workgroup
+    /// checks the proof (a few milliseconds, not the some hundred of the one-lane-per-proof verifiers).
+    pub fn verify_with_processed_vk(
+        pvk: &GpuPreparedVerifyingKey,
+        public_inputs: &[Fr],
+        proof: &Proof<Bn254>,
+    ) -> Result<bool, GpuError> {
+        Ok(verify_prepared(pvk, &[public_inputs.to_vec()], std::slice::from_ref(proof))?[0])
+    }
+}
