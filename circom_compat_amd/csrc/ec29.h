@@ -51,19 +51,27 @@ struct XYZZ29 {
     LF X2 = p.x.sqr();               // M
     LF Mm = (X2.dbl() + X2).carry();  // |v| < 6p
     LF X3 = (Mm.sqr() - S.dbl()).carry();            // (-5p, 4p)
-    LF Y3 = LF::mul_sub(Mm, S - X3, W, p.y);         // M (carried for Fq2)
+    // Y3: limbs of Mm in [-8, 2^29 + 8), of S - X3 within +-(2^29 + 8), W and p.y products (p.y possibly negated
+    // and carried); values |Mm| < 6p, S - X3 in (-5p, 7p), |W| < 2p, |p.y| < 2p: 42 + 4 = 46 p^2 in G1, and per
+    // component of Fq2 2 * 42 + 2 * 4 = 92 p^2 < 168.9 p^2 (mul4: 337 p^2)
+    LF Y3 = LF::mul_sub_y3(Mm, S - X3, W, p.y);      // M
     return XYZZ29{X3, Y3, V, W};
   }
   // dbl-2008-s-1
   G16_HD void dbl_in_place() {
     if (is_inf()) return;
     LF U = y.dbl().carry();          // |v| < 6p
-    LF V = U.sqr();
-    LF W = U * V;
-    LF S = x * V;
-    LF X2 = x.sqr();
-    LF Mm = (X2.dbl() + X2).carry();
-    LF X3 = (Mm.sqr() - S.dbl()).carry();
+    LF V = U.sqr();                  // M
+    LF W = U * V;                    // M
+    LF S = x * V;                    // M
+    LF X2 = x.sqr();                 // M
+    LF Mm = (X2.dbl() + X2).carry();  // (-3p, 6p), limbs in [-8, 2^29 + 8)
+    LF X3 = (Mm.sqr() - S.dbl()).carry();            // (-5p, 4p)
+    // Y3: S - X3 in (-5p, 7p) with limbs within +-(2^29 + 8); W a product, y stored (limbs in [-8, 2^29 + 8),
+    // |v| < 3p): 6 * 7 + 2 * 3 = 48 p^2 in G1, per component of Fq2 2 * 42 + 2 * 6 = 96 p^2 < 168.9 p^2
+    // (mul4 allows 337 p^2): mul_sub_y3 would be inside its contract here.  NOT used: with the merged form in add
+    // and dbl_in_place k_bucket_reduce<Fq2>, already at 512 registers, goes from 34 to 59 spilled VGPRs (80 to 156
+    // bytes of scratch, profiles/r09_acc_diet_resource_usage.txt) -- the two keep mul_sub, the split form for Fq2.
     LF Y3 = LF::mul_sub(Mm, S - X3, W, y);
     zz = V * zz;
     zzz = W * zzz;
@@ -107,31 +115,57 @@ struct XYZZ29 {
     LF PPP = Pp * PP;                              // M
     LF Q = x * PP;                                 // M
     LF X3 = (R.sqr() - PPP - Q.dbl()).carry();     // S: (-7p, 5p)
-    LF Y3 = LF::mul_sub(R, Q - X3, y, PPP);        // M (S for Fq2)
+    // Y3: |R| < 10p against Q - X3 in (-6p, 9p), |y| < 3p against |PPP| < 2p: 96 p^2 in G1, per component of Fq2
+    // 2 * 90 + 2 * 6 = 192 p^2 < 337 p^2 (mul4); all limbs within +-(2^29 + 8)
+    LF Y3 = LF::mul_sub_y3(R, Q - X3, y, PPP);     // M (stored-y class for Fq2: (-2p, 3p))
     zz = zz * PP;
     zzz = zzz * PPP;
     x = X3;
     y = Y3;
   }
-  // Branch-free core of madd for software-pipelined callers (two independent additions per lane
+  // The general formula of madd alone: no infinity test, no select, no branch (the accumulation loop of
+  // msm_curve.inc.h keeps the infinity cases out of its per-iteration path).  PRECONDITION for a meaningful result:
+  // neither operand is infinite.  *x_may_coincide reports the 2^-23 filter on Pp (the caller then redoes the
+  // addition exactly, or defers it).  Infinite operands have all-zero coordinates and a dead lane hands in a stale
+  // finite point: every product formed then has a zero or an in-class factor, so the column and value bounds hold
+  // whatever comes in (F29_CHECK sees those calls too); the result is simply not a group element.
+  static G16_HD XYZZ29 madd_core(const XYZZ29& acc, const Aff29<LF>& p, bool* x_may_coincide) {
+    LF U2 = p.x * acc.zz;   // M
+    LF S2 = p.y * acc.zzz;  // M
+    LF Pp = U2 - acc.x;     // limbs within +-(2^29+8); |v| < 10p
+    LF R = S2 - acc.y;      // same
+    *x_may_coincide = Pp.maybe_zero_mod_p();
+    LF PP = Pp.sqr();
+    LF PPP = Pp * PP;
+    LF Q = acc.x * PP;
+    LF X3 = (R.sqr() - PPP - Q.dbl()).carry();       // (-7p, 5p)
+    LF Y3 = LF::mul_sub_y3(R, Q - X3, acc.y, PPP);   // as in madd: 192 p^2 per component of Fq2
+    return XYZZ29{X3, Y3, acc.zz * PP, acc.zzz * PPP};
+  }
+  // The exact answer for an addition that madd_core flagged (same precondition): res = madd_core(acc, p) unless the
+  // x-coordinates really coincide -- then the doubling or the point at infinity, exactly what madd() returns (its
+  // formula is madd_core's).  Forms Pp and R again (two products on a 2^-23 path) and shares madd()'s out-of-line
+  // tail, so the caller's loop holds ONE copy of the general formula: with w.acc.madd(p) in its place the G2
+  // accumulation kernel grew from 7.7 K to 12.1 K instructions and from 90 to 190 AGPRs
+  // (profiles/r09_acc_diet_resource_usage.txt).
+  static G16_HD XYZZ29 madd_resolve(const XYZZ29& acc, const Aff29<LF>& p, const XYZZ29& res) {
+    LF Pp = p.x * acc.zz - acc.x;
+    LF R = p.y * acc.zzz - acc.y;
+    bool handled;
+    XYZZ29 r = madd_rare(p, Pp, R, &handled);
+    return handled ? r : res;
+  }
+  // Branch-free madd for software-pipelined callers (two independent additions per lane
   // in ONE basic block so the scheduler can interleave their dependent multiply chains):
   // returns acc + p by the general formula and reports through *special when the x-coordinates
   // may coincide (~2^-23 of calls: the caller then redoes this addition with madd()).  The
   // infinity cases are resolved by selects, not branches.
   static G16_HD XYZZ29 madd_select(const XYZZ29& acc, const Aff29<LF>& p, bool* special) {
     const bool acc_inf = acc.is_inf();
-    // an infinite accumulator has all-zero coordinates: give the formulas something harmless
-    LF U2 = p.x * acc.zz;
-    LF S2 = p.y * acc.zzz;
-    LF Pp = U2 - acc.x;
-    LF R = S2 - acc.y;
-    *special = !acc_inf && !p.inf && Pp.maybe_zero_mod_p();
-    LF PP = Pp.sqr();
-    LF PPP = Pp * PP;
-    LF Q = acc.x * PP;
-    LF X3 = (R.sqr() - PPP - Q.dbl()).carry();
-    LF Y3 = LF::mul_sub(R, Q - X3, acc.y, PPP);
-    XYZZ29 r{X3, Y3, acc.zz * PP, acc.zzz * PPP};
+    bool x_may_coincide;
+    // an infinite accumulator has all-zero coordinates: harmless to the formulas
+    XYZZ29 r = madd_core(acc, p, &x_may_coincide);
+    *special = !acc_inf && !p.inf && x_may_coincide;
     if (acc_inf) r = XYZZ29{p.x, p.y, LF::one(), LF::one()};
     if (p.inf) r = acc;
     return r;
@@ -161,6 +195,10 @@ struct XYZZ29 {
     LF PPP = Pp * PP;
     LF Q = U1 * PP;
     LF X3 = (R.sqr() - PPP - Q.dbl()).carry();
+    // Y3: Pp, R differences of two products: limbs in (-2^29, 2^29), |v| < 3p; X3 in (-7p, 5p) carried, so Q - X3
+    // in (-6p, 9p) with limbs within +-(2^29 + 8); S1, PPP products: 3 * 9 + 2 * 2 = 31 p^2 in G1, per component
+    // of Fq2 2 * 27 + 2 * 4 = 62 p^2 < 168.9 p^2 (mul4 allows 337 p^2): inside mul_sub_y3's contract, but mul_sub
+    // stays (see dbl_in_place: the registers of k_bucket_reduce<Fq2>)
     LF Y3 = LF::mul_sub(R, Q - X3, S1, PPP);
     zz = (zz * q.zz) * PP;
     zzz = (zzz * q.zzz) * PPP;

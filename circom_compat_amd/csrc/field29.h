@@ -298,6 +298,8 @@ struct F29 {
   static G16_HD F29 mul_sub(const F29& a, const F29& b, const F29& c, const F29& d) {
     return mul2(a, b, c.neg(), d);
   }
+  // the Y3 of the group law (ec29.h): a b - c d under the name both field types share -- here mul_sub itself
+  static G16_HD F29 mul_sub_y3(const F29& a, const F29& b, const F29& c, const F29& d) { return mul_sub(a, b, c, d); }
   // Same value, limbs 0..7 moved to the CENTRED range: one parallel carry step around 2^28 instead of 0.
   //   input  : limbs 0..7 within +-(2^29 + 2^4) (any class of ec29.h)
   //   output : limbs 0..7 in [-2^28 - 1, 2^28], top limb moved by at most 1
@@ -744,6 +746,17 @@ struct F29x2 {
     return mul_sub_merged(a, b, c, d);
 #else
     return mul_sub_split(a, b, c, d);
+#endif
+  }
+  // What ec29.h forms every Y3 with: the merged form, whatever mul_sub is built as.  Its result -- limbs 0..7 in
+  // [0, 2^29), components in (-2p, 3p) -- is inside ec29.h's stored-y class, and the group-level tests
+  // (tests/test_lazy_ec.py) check group elements and classes, not the integer that mul_sub's own test pins.
+  // (F29X2_Y3_SPLIT, variant builds: the A/B partner with two full Fq2 products.)
+  static G16_HD F29x2 mul_sub_y3(const F29x2& a, const F29x2& b, const F29x2& c, const F29x2& d) {
+#ifdef F29X2_Y3_SPLIT
+    return mul_sub_split(a, b, c, d);
+#else
+    return mul_sub_merged(a, b, c, d);
 #endif
   }
   G16_HD bool is_zero_mod_p() const { return c0.is_zero_mod_p() && c1.is_zero_mod_p(); }

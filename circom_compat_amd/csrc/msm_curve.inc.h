@@ -78,6 +78,7 @@ struct AccWay {
   using LF = typename Lazy<F>::type;
   uint32_t seg, pos, end, g, bend, bnext, en_next, en_next2;  // bend = offset[g+1], bnext = offset[g+2]
   bool live;
+  bool empty;  // acc is the point at infinity (all-zero limbs): the next finite point of this lane STARTS a run
   XYZZ29<LF> acc;
   Affine<F> raw_next;
 };
@@ -119,6 +120,7 @@ __device__ __forceinline__ void acc_way_init(AccWay<F>& w, uint32_t seg, uint32_
   w.live = w.pos < M;
   w.end = w.live ? (w.pos + S < M ? w.pos + S : M) : w.pos;
   w.acc = XYZZ29<typename Lazy<F>::type>::infinity();
+  w.empty = true;
   w.raw_next = Affine<F>::infinity();
   w.g = 0;
   w.bend = w.bnext = 0;
@@ -140,9 +142,15 @@ __device__ __forceinline__ void acc_way_init(AccWay<F>& w, uint32_t seg, uint32_
 // only waited for one iteration later (at the next point's unpack), when they have long completed.
 // With the boundary block first, every wave drained its fresh stores + a dependent offset[] load
 // whenever one of its lanes crossed a bucket boundary (~half of the iterations).
+//
+// The infinity cases of the addition live here too, out of the per-iteration arithmetic (XYZZ29::madd_core has
+// none): an EMPTY accumulator -- at the start of a segment and after every boundary reset -- takes its first
+// finite point as (x, y, 1, 1) in a divergent block next to the boundary block (*started: the caller commits no
+// addition for this entry), and a point at infinity (in the key, below idx_min, a dead step) is simply never
+// committed.  A lane whose first points are infinite stays empty.
 template <class F, int PS>
 __device__ __forceinline__ Aff29<typename Lazy<F>::type> acc_way_prepare(
-    AccWay<F>& w, bool* step, const Affine<F>* __restrict__ pts, uint32_t npts, uint32_t idx_min,
+    AccWay<F>& w, bool* step, bool* started, const Affine<F>* __restrict__ pts, uint32_t npts, uint32_t idx_min,
     uint32_t idx_bits, const uint32_t* __restrict__ entries, const uint32_t* __restrict__ offset,
     uint32_t nb, MsmAcc<F>* __restrict__ partial) {
   using LF = typename Lazy<F>::type;
@@ -154,12 +162,18 @@ __device__ __forceinline__ Aff29<typename Lazy<F>::type> acc_way_prepare(
   if (*step && w.pos == w.bend) {  // crossed into the next non-empty bucket: emit, restart
     partial[w.g + w.seg] = w.acc;
     w.acc = XYZZ29<LF>::infinity();
+    w.empty = true;
     ++w.g;
     w.bend = w.bnext;  // fetched during the previous iteration
     while (w.bend == w.pos) {  // runs of empty buckets (rare): chase the array
       ++w.g;
       w.bend = offset[w.g + 1];
     }
+  }
+  *started = w.empty && *step && !p.inf;
+  if (*started) {  // first finite point of a run: 4 field elements of moves under the exec mask
+    w.acc = XYZZ29<LF>{p.x, p.y, LF::one(), LF::one()};
+    w.empty = false;
   }
   // look-ahead for the next crossing, EVERY iteration (a conditional load would need a copy into
   // the loop-carried register at the end of the boundary block, i.e. a wait for it right there)
@@ -174,11 +188,15 @@ __device__ __forceinline__ Aff29<typename Lazy<F>::type> acc_way_prepare(
 // repeated points) is not redone here -- an exact madd() drags an out-of-line call, its scratch frame
 // and ~90 VGPRs into the hot kernel -- but appended to a list: (slot of the partial this accumulator
 // will be stored to, entry).  k_acc_fixup adds the listed points to the stored partials afterwards.
+// res = madd_core(w.acc, p) is an addition only where this lane has a live step, a finite point and an
+// accumulator that did not just start its run with it (started, acc_way_prepare): nothing else is committed.
 template <class F, bool FAST>
-__device__ __forceinline__ void acc_way_commit(AccWay<F>& w, bool step,
-                                               const XYZZ29<typename Lazy<F>::type>& res, bool special,
+__device__ __forceinline__ void acc_way_commit(AccWay<F>& w, bool step, bool started,
+                                               const XYZZ29<typename Lazy<F>::type>& res, bool x_may_coincide,
                                                const Aff29<typename Lazy<F>::type>& p, uint32_t en,
                                                uint32_t half, MsmFixList* fix) {
+  const bool that = step && !started && !p.inf;
+  const bool special = that && x_may_coincide;
   if (FAST) {
     if (special) {
       const uint32_t k = atomicAdd(&fix->count, 1u);
@@ -186,12 +204,16 @@ __device__ __forceinline__ void acc_way_commit(AccWay<F>& w, bool step,
         fix->slot[k] = (w.g + w.seg) | (half << 31);
         fix->entry[k] = en;
       }
-    } else {
+    } else if (that) {
       w.acc = res;
     }
   } else {
-    if (special) w.acc.madd(p);  // x-coordinates may coincide: redo exactly (doubling / cancellation)
-    else w.acc = res;
+    if (special) {  // x-coordinates may coincide: resolve exactly (doubling / cancellation), as madd() would
+      w.acc = XYZZ29<typename Lazy<F>::type>::madd_resolve(w.acc, p, res);
+      w.empty = w.acc.is_inf();  // P + (-P): the next finite point starts the run again
+    } else if (that) {
+      w.acc = res;
+    }
   }
   if (step) ++w.pos;
 }
@@ -199,9 +221,11 @@ __device__ __forceinline__ void acc_way_commit(AccWay<F>& w, bool step,
 // One lane = one equal segment of the sorted entry list (persistent grid: `lanes` segments over
 // gridDim.x * blockDim.x threads, normally one each).  The dependent multiply-add chains of one
 // mixed addition cannot keep the half-rate multiplier busy on their own (~11 cycles of latency per
-// ~8-cycle issue); two or three waves per SIMD do: the exact variant (219 VGPRs) runs two, the
+// ~8-cycle issue); two or three waves per SIMD do.  Until round 9 the exact variant (219 VGPRs) ran two, the
 // optimistic G1 variant (149 VGPRs, FAST below) three -- 3072 x 128 threads = two rounds of resident
-// workgroups (msm.h, MSM_ACC_BLOCKS), the G2 kernel one wave per SIMD over 2048 workgroups.  Interleaving
+// workgroups (msm.h, MSM_ACC_BLOCKS), the G2 kernel one wave per SIMD over 2048 workgroups; with the infinity
+// cases out of the iteration (acc_way_prepare) the optimistic kernels hold 120 / 125 VGPRs, four waves per SIMD,
+// the exact G1 ones 166 / 170 (profiles/r09_acc_diet_resource_usage.txt).  Interleaving
 // two segments per lane in one basic block was measured and lost: ~450 VGPRs (1 wave per SIMD),
 // 21.4 vs 17.5 ms for the four G1 MSMs of a 2^22 proof; capped at 256 VGPRs it spills.
 // PS = record stride in points (2: this query is one half of an interleaved pair,
@@ -248,12 +272,12 @@ __global__ void __launch_bounds__(ACC_THREADS) G16_ACC_ATTR
     acc_way_init<F, PS>(w, t0, S, M, pts, npts, idx_min, idx_bits, entries, offset, nb);
     if (!w.live) break;  // segments are handed out in order: nothing left for later threads either
     for (uint32_t it = 0; it < S; ++it) {
-      bool step, special;
+      bool step, started, x_may_coincide;
       const uint32_t en = w.en_next;  // the entry whose point acc_way_prepare unpacks
       const Aff29<LF> p =
-          acc_way_prepare<F, PS>(w, &step, pts, npts, idx_min, idx_bits, entries, offset, nb, partial);
-      const XYZZ29<LF> r = XYZZ29<LF>::madd_select(w.acc, p, &special);
-      acc_way_commit<F, FAST>(w, step, r, special, p, en, half, fix);
+          acc_way_prepare<F, PS>(w, &step, &started, pts, npts, idx_min, idx_bits, entries, offset, nb, partial);
+      const XYZZ29<LF> r = XYZZ29<LF>::madd_core(w.acc, p, &x_may_coincide);
+      acc_way_commit<F, FAST>(w, step, started, r, x_may_coincide, p, en, half, fix);
     }
     partial[w.g + w.seg] = w.acc;
   }
