@@ -40,6 +40,7 @@ __all__ = ["read_zkey", "R1CSFile", "R1CS", "CircomCircuit", "CircomBuilder", "C
            "verify_batch_fast", "verify_aggregate_keys", "verify_batch_keys", "verify_batch_fast_keys", "check_key", "KeyReport", "contribute_key", "check_contribution",
            "ContributionReport", "Srs", "trapdoor_srs", "setup_from_srs", "check_key_circuit",
            "CircuitBindingReport", "read_ptau", "write_ptau", "check_srs", "SrsReport", "contribute_srs", "new_srs",
+           "LagrangeSrs", "LagrangeReport", "prepare_phase2", "prepare_phase2_times", "check_lagrange",
            "points_from_ark", "points_to_ark", "read_ark_key", "write_ark_key", "read_ark_vk", "write_ark_vk",
            "proofs_from_ark", "proofs_to_ark", "ark_point_bytes", "rerandomize", "rerandomize_keys",
            "rerandomize_times", "PreparedVerifyingKey", "prepare_verifying_key", "verify_prepared", "pairing_check",
@@ -856,30 +857,206 @@ def trapdoor_srs(log2_domain: int, toxic: Sequence[int], device=0, lib: Optional
                view(d.beta_tau_g1, d.n_tau, 64), bytes(d.beta_g2), keepalive=handle)
 
 
+class LagrangeSrs:
+    """The Lagrange sections 12-15 of a prepared .ptau (`snarkjs powersoftau prepare phase2`), the layout of
+    include/g16_amd.h: tau_g1 (2^(power+2) - 1, 64) uint8 in levels 0 .. power + 1; tau_g2 (2^(power+1) - 1, 128),
+    alpha_tau_g1 and beta_tau_g1 (2^(power+1) - 1, 64) in levels 0 .. power.  Level p starts at row 2^p - 1 and holds
+    the 2^p points L_j(tau) G of the domain of size 2^p.  Arrays a caller supplies are taken as they are:
+    check_lagrange tells whether they belong to an Srs."""
+    ARRAYS = B.LAGRANGE_ARRAYS
+
+    def __init__(self, power, tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, keepalive=None):
+        self.power = int(power)
+        if not 0 <= self.power <= 27:
+            raise SynthesisError(B.G16_ERR_DOMAIN_TOO_LARGE, "a Lagrange set has power <= 27")
+        self.tau_g1 = np.ascontiguousarray(tau_g1, dtype=np.uint8).reshape(-1, 64)
+        self.tau_g2 = np.ascontiguousarray(tau_g2, dtype=np.uint8).reshape(-1, 128)
+        self.alpha_tau_g1 = np.ascontiguousarray(alpha_tau_g1, dtype=np.uint8).reshape(-1, 64)
+        self.beta_tau_g1 = np.ascontiguousarray(beta_tau_g1, dtype=np.uint8).reshape(-1, 64)
+        m1, m2 = (4 << self.power) - 1, (2 << self.power) - 1
+        if (self.tau_g1.shape[0], self.tau_g2.shape[0], self.alpha_tau_g1.shape[0],
+                self.beta_tau_g1.shape[0]) != (m1, m2, m2, m2):
+            raise G16Error(B.G16_ERR_INVALID, f"a Lagrange set of power {self.power} has {m1} tau_g1 points and "
+                                              f"{m2} of each other array")
+        self._keepalive = keepalive
+
+    def levels(self, name) -> int:
+        """levels of the array: power + 2 for tau_g1, power + 1 for the others"""
+        if name not in self.ARRAYS:
+            raise G16Error(B.G16_ERR_INVALID, f"no array {name!r}")
+        return self.power + (2 if name == "tau_g1" else 1)
+
+    def level(self, name, p):
+        """view of level p of the array: 2^p rows"""
+        p = int(p)
+        if not 0 <= p < self.levels(name):
+            raise G16Error(B.G16_ERR_INVALID, f"{name} has no level {p}")
+        return getattr(self, name)[(1 << p) - 1:(2 << p) - 1]
+
+    @staticmethod
+    def locate(index):
+        """position in a section -> (level, j)"""
+        p = (int(index) + 1).bit_length() - 1
+        return p, int(index) + 1 - (1 << p)
+
+    def to_c(self) -> B.SrsLagrangeDesc:
+        d = B.SrsLagrangeDesc()
+        d.power = self.power
+        d.tau_g1, d.tau_g2 = self.tau_g1.ctypes.data, self.tau_g2.ctypes.data
+        d.alpha_tau_g1, d.beta_tau_g1 = self.alpha_tau_g1.ctypes.data, self.beta_tau_g1.ctypes.data
+        return d
+
+
+def _srs_power(d: B.SrsDesc) -> int:
+    """the largest power of a .ptau the arrays cover (write_ptau's rule)"""
+    power = 0
+    while power < 28 and d.n_tau >= 2 << power and d.n_tau_g1 >= (4 << power) - 1:
+        power += 1
+    return power
+
+
+def prepare_phase2(srs: Srs, power=None, device=0, lib: Optional[B.Library] = None) -> LagrangeSrs:
+    """`snarkjs powersoftau prepare phase2` on the GPU (g16_srs_prepare): every level of the Lagrange copies of
+    the four arrays, by the group transform of setup_from_srs.  power: None = the largest the arrays cover (at most
+    27); entries of srs beyond 2^(power+1) - 1 / 2^power are dropped.  The same bytes on every run."""
+    lib = lib or B.load()
+    d = srs.to_c()
+    power = min(_srs_power(d), 27) if power is None else int(power)
+    if power < 0:
+        raise G16Error(B.G16_ERR_INVALID, "power >= 0")
+    if power > 27:
+        raise SynthesisError(B.G16_ERR_DOMAIN_TOO_LARGE, "g16_srs_prepare: power > 27")
+    if d.n_tau < 1 << power or d.n_tau_g1 < (2 << power) - 1:
+        raise G16Error(B.G16_ERR_INVALID, "the SRS is shorter than 2^power")
+    m1, m2 = (4 << power) - 1, (2 << power) - 1
+    tau_g1 = np.empty((m1, 64), dtype=np.uint8)
+    tau_g2 = np.empty((m2, 128), dtype=np.uint8)
+    alpha = np.empty((m2, 64), dtype=np.uint8)
+    beta = np.empty((m2, 64), dtype=np.uint8)
+    st = lib.g16_srs_prepare(device, C.byref(d), power, _np_ptr(tau_g1), _np_ptr(tau_g2), _np_ptr(alpha),
+                             _np_ptr(beta))
+    if st != B.G16_OK:
+        raise (SynthesisError if st == B.G16_ERR_DOMAIN_TOO_LARGE else G16Error)(st, "g16_srs_prepare failed")
+    return LagrangeSrs(power, tau_g1, tau_g2, alpha, beta)
+
+
+def prepare_phase2_times(lib: Optional[B.Library] = None) -> dict:
+    """milliseconds per phase of this thread's last prepare_phase2 (g16_srs_prepare_times), the phases of
+    setup_from_srs_times"""
+    lib = lib or B.load()
+    ms = (C.c_float * len(SETUP_SRS_PHASES))()
+    lib.check(lib.g16_srs_prepare_times(ms, len(SETUP_SRS_PHASES)))
+    return dict(zip(SETUP_SRS_PHASES, (float(x) for x in ms)))
+
+
+class LagrangeReport:
+    """g16_srs_lagrange_report + the bad-point list of g16_srs_lagrange_check.  ok: no bad point and no failed
+    relation; relations_checked: False when a structural failure made the relations meaningless;
+    relations_failed: bit (1 << array), failed_arrays the names; n_points / n_bad / n_infinity: dicts by array
+    name; bad_points: [(array_name, level, j, reason_bits)] in ascending (array, position) order, at most
+    max_listed."""
+    REASONS = ((B.KEY_BAD_NONCANONICAL, "non-canonical coordinate"), (B.KEY_BAD_OFF_CURVE, "off the curve"),
+               (B.KEY_BAD_SUBGROUP, "outside the prime-order subgroup"))
+
+    def __init__(self, rep: B.SrsLagrangeReportC, bad):
+        self.ok = bool(rep.ok)
+        self.relations_checked = bool(rep.relations_checked)
+        self.relations_failed = int(rep.relations_failed)
+        self.failed_arrays = [q for i, q in enumerate(B.LAGRANGE_ARRAYS) if self.relations_failed >> i & 1]
+        self.n_points = {q: int(rep.n_points[i]) for i, q in enumerate(B.LAGRANGE_ARRAYS)}
+        self.n_bad = {q: int(rep.n_bad[i]) for i, q in enumerate(B.LAGRANGE_ARRAYS)}
+        self.n_infinity = {q: int(rep.n_infinity[i]) for i, q in enumerate(B.LAGRANGE_ARRAYS)}
+        self.bad_points = [(B.LAGRANGE_ARRAYS[b.query],) + LagrangeSrs.locate(b.index) + (int(b.reason),)
+                           for b in bad]
+
+    def __eq__(self, o):
+        return isinstance(o, LagrangeReport) and vars(o) == vars(self)
+
+    def describe(self) -> str:
+        if self.ok:
+            return "ok"
+        if self.bad_points:
+            q, p, j, why = self.bad_points[0]
+            words = ", ".join(w for bit, w in self.REASONS if why & bit)
+            return (f"{q} level {p} entry {j}: {words} (reason {why}); {sum(self.n_bad.values())} bad point(s) "
+                    "in all")
+        if not self.relations_checked:
+            return f"{sum(self.n_bad.values())} bad point(s)"
+        return "; ".join(f"the Lagrange levels of {q} are not the transforms of its powers"
+                         for q in self.failed_arrays)
+
+    def __repr__(self):
+        return f"LagrangeReport({self.describe()})"
+
+
+def check_lagrange(srs: Srs, lag: LagrangeSrs, rho=None, device=0, max_listed=64,
+                   lib: Optional[B.Library] = None) -> LagrangeReport:
+    """Are the Lagrange sections of a prepared .ptau the transforms of THIS string's powers
+    (g16_srs_lagrange_check, on the GPU): every Lagrange point canonical, on its curve and (G2) in the subgroup;
+    then, per array, one random 128-bit combination over all its levels against one full-width combination over
+    the powers.  srs is expected to have passed check_srs.  A wrong entry passes with probability at most 2^-127.
+    rho: None (drawn by the library from the OS CSPRNG) or (2^(power+2) - 1) + 3 (2^(power+1) - 1) ints in
+    [1, 2^128): tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1 in this order, levels ascending."""
+    lib = lib or B.load()
+    d, dl = srs.to_c(), lag.to_c()
+    rho_arr = None
+    if rho is not None:
+        rho = [int(x) for x in rho]
+        if len(rho) != ((4 << lag.power) - 1) + 3 * ((2 << lag.power) - 1):
+            raise G16Error(B.G16_ERR_INVALID, "one coefficient per Lagrange point")
+        if any(not 0 <= x < 1 << 128 for x in rho):
+            raise G16Error(B.G16_ERR_INVALID, "coefficients are integers in [1, 2^128)")
+        rho_arr = np.array([[x & 0xFFFFFFFFFFFFFFFF, x >> 64] for x in rho], dtype=np.uint64).reshape(-1, 2)
+    max_listed = int(max_listed)
+    bad = (B.KeyBadPoint * max(max_listed, 1))()
+    rep = B.SrsLagrangeReportC()
+    st = lib.g16_srs_lagrange_check(device, C.byref(d), C.byref(dl), _np_ptr(rho_arr) if rho_arr is not None else None,
+                                    bad, max_listed, C.byref(rep))
+    if st != B.G16_OK:
+        raise (SynthesisError if st == B.G16_ERR_DOMAIN_TOO_LARGE else G16Error)(st, "g16_srs_lagrange_check failed")
+    return LagrangeReport(rep, bad[:rep.n_listed])
+
+
 def setup_from_srs(a: Csr, b: Csr, c: Csr, n_vars: int, n_public: int, srs: Srs, device=0,
-                   lib: Optional[B.Library] = None, reduction: str = "circom") -> ProvingKey:
+                   lib: Optional[B.Library] = None, reduction: str = "circom",
+                   lagrange: Optional[LagrangeSrs] = None) -> ProvingKey:
     """The initial key (gamma = delta = 1) of a circuit from a powers-of-tau string, on the GPU
     (g16_setup_from_srs): what `snarkjs zkey new` computes of the points, nobody knowing tau, alpha or beta.
     Matrix arguments and reduction as trapdoor_setup takes them; byte for byte the key trapdoor_setup mints
     for (tau, alpha, beta, 1, 1).  contribute_key then re-randomises delta.  The SRS is NOT verified here:
-    check_srs / read_ptau(validate=True) do that."""
+    check_srs / read_ptau(validate=True) do that.
+    lagrange: the string's LagrangeSrs (prepare_phase2, read_ptau(lagrange=True)): no transform is computed, the
+    bases are read from it (g16_setup_from_prepared).  The same key when the circuit's domain is 2^power; below
+    that every field but the circom h_query is, which is then the one `snarkjs zkey new` writes: it differs from
+    the default's point by point and yields the same proofs (include/g16_amd.h).  NOT verified here either:
+    check_lagrange does that."""
     lib = lib or B.load()
     at, bt, ct = _setup_matrices(a, b, c, n_vars, n_public, lib)
     h = C.c_void_p()
     cat, cbt, cct = at.to_c(), bt.to_c(), ct.to_c()
     d = srs.to_c()
-    st = lib.g16_setup_from_srs(device, C.byref(cat), C.byref(cbt), C.byref(cct), n_vars, n_public, a.num_rows,
-                                C.byref(d), REDUCTIONS[reduction], C.byref(h))
+    if lagrange is not None:
+        dl = lagrange.to_c()
+        st = lib.g16_setup_from_prepared(device, C.byref(cat), C.byref(cbt), C.byref(cct), n_vars, n_public,
+                                         a.num_rows, C.byref(d), C.byref(dl), REDUCTIONS[reduction], C.byref(h))
+        what = "g16_setup_from_prepared failed"
+    else:
+        st = lib.g16_setup_from_srs(device, C.byref(cat), C.byref(cbt), C.byref(cct), n_vars, n_public, a.num_rows,
+                                    C.byref(d), REDUCTIONS[reduction], C.byref(h))
+        what = "g16_setup_from_srs failed"
     if st != B.G16_OK:
-        raise (SynthesisError if st == B.G16_ERR_DOMAIN_TOO_LARGE else G16Error)(st, "g16_setup_from_srs failed")
+        raise (SynthesisError if st == B.G16_ERR_DOMAIN_TOO_LARGE else G16Error)(st, what)
     return _setup_key(lib, h, n_vars, n_public)
 
 
-def read_ptau(src, validate=False, lib: Optional[B.Library] = None) -> Srs:
+def read_ptau(src, validate=False, lagrange=False, lib: Optional[B.Library] = None) -> Srs:
     """snarkjs .ptau (a path, or bytes) -> Srs, with .power and .ceremony_power (g16_ptau_open; the arrays are
     views of the mapped file).  validate=True runs check_srs (on the GPU) and raises G16Error naming the first
     bad point or the failed relation; the default looks at no point.  The contribution transcript of the file
-    is not verified either way."""
+    is not verified either way.
+    lagrange=True: the file must be prepared (sections 12-15, g16_ptau_lagrange); the result has .lagrange, a
+    LagrangeSrs of views, and validate=True runs check_lagrange after check_srs.  The default ignores those
+    sections, whatever they hold."""
     lib = lib or B.load()
     h = C.c_void_p()
     if isinstance(src, (bytes, bytearray, memoryview)):
@@ -899,22 +1076,35 @@ def read_ptau(src, validate=False, lib: Optional[B.Library] = None) -> Srs:
     srs = Srs(view(d.tau_g1, d.n_tau_g1, 64), view(d.tau_g2, d.n_tau, 128), view(d.alpha_tau_g1, d.n_tau, 64),
               view(d.beta_tau_g1, d.n_tau, 64), bytes(d.beta_g2), keepalive=handle)
     srs.power, srs.ceremony_power = int(hdr.power), int(hdr.ceremony_power)
+    if lagrange:
+        dl = B.SrsLagrangeDesc()
+        lib.check(lib.g16_ptau_lagrange(h, C.byref(dl)), loader=True)
+        m1, m2 = (4 << dl.power) - 1, (2 << dl.power) - 1
+        srs.lagrange = LagrangeSrs(dl.power, view(dl.tau_g1, m1, 64), view(dl.tau_g2, m2, 128),
+                                   view(dl.alpha_tau_g1, m2, 64), view(dl.beta_tau_g1, m2, 64), keepalive=handle)
     if validate:
         rep = check_srs(srs, lib=lib)
         if not rep.ok:
             raise G16Error(B.G16_ERR_INVALID, "ptau failed validation: " + rep.describe())
+        if lagrange:
+            lrep = check_lagrange(srs, srs.lagrange, lib=lib)
+            if not lrep.ok:
+                raise G16Error(B.G16_ERR_INVALID, "ptau failed validation: " + lrep.describe())
     return srs
 
 
-def write_ptau(path, srs: Srs, lib: Optional[B.Library] = None):
+def write_ptau(path, srs: Srs, lagrange: Optional[LagrangeSrs] = None, lib: Optional[B.Library] = None):
     """Srs -> snarkjs .ptau (g16_ptau_write) of the largest power the arrays cover: sections 1-6 and an empty
-    contribution list, entries beyond 2^power dropped."""
+    contribution list, entries beyond 2^power dropped.  lagrange: a PREPARED file of lagrange.power
+    (g16_ptau_write_prepared): sections 12-15 as well."""
     lib = lib or B.load()
     d = srs.to_c()
-    power = 0
-    while power < 28 and d.n_tau >= 2 << power and d.n_tau_g1 >= (4 << power) - 1:
-        power += 1
-    lib.check(lib.g16_ptau_write(os.fsencode(path), C.byref(d), power), loader=True)
+    if lagrange is not None:
+        dl = lagrange.to_c()
+        lib.check(lib.g16_ptau_write_prepared(os.fsencode(path), C.byref(d), C.byref(dl), lagrange.power),
+                  loader=True)
+        return
+    lib.check(lib.g16_ptau_write(os.fsencode(path), C.byref(d), _srs_power(d)), loader=True)
 
 
 class SrsReport:
@@ -1076,14 +1266,20 @@ class CircuitBindingReport:
 
 
 def check_key_circuit(pk: "ProvingKey", a: Csr, b: Csr, c: Csr, srs: Srs, rho=None, device=0, max_listed=64,
-                      lib: Optional[B.Library] = None, reduction: str = "circom") -> CircuitBindingReport:
+                      lib: Optional[B.Library] = None, reduction: str = "circom",
+                      lagrange: Optional[LagrangeSrs] = None) -> CircuitBindingReport:
     """Is pk a key of THIS circuit under THIS ceremony -- the binding check_key cannot give.  Recomputes the
     initial key from the SRS and the matrices (setup_from_srs), then requires, in this order, vk.gamma_abc_g1
     and vk.gamma_g2 equal to the fresh key's, and check_contribution(fresh, pk).ok: a_query, b_g1_query,
     b_g2_query, alpha and beta byte for byte, l_query, h_query and delta by pairings.  pk should have passed
-    check_key; rho, max_listed as check_contribution takes them."""
+    check_key; rho, max_listed as check_contribution takes them.
+    lagrange: the string's LagrangeSrs; the initial key is then read from it (setup_from_srs(lagrange=...)), with
+    the H query of `snarkjs zkey new`.  A key snarkjs made for a circuit smaller than the ceremony passes only
+    this way: the default's H query is the reference's, a different set of points for the same proofs, and the
+    pairing comparison of h_query reports "contribution"."""
     lib = lib or B.load()
-    fresh = setup_from_srs(a, b, c, pk.n_vars, pk.n_public, srs, device=device, lib=lib, reduction=reduction)
+    fresh = setup_from_srs(a, b, c, pk.n_vars, pk.n_public, srs, device=device, lib=lib, reduction=reduction,
+                           lagrange=lagrange)
     if fresh.domain_size != pk.domain_size:
         return CircuitBindingReport("shape")
     if not np.array_equal(np.asarray(fresh.vk.gamma_abc_g1), np.asarray(pk.vk.gamma_abc_g1)):

@@ -123,6 +123,21 @@ class SrsReportC(C.Structure):
                 ("n_listed", C.c_uint32)]
 
 
+class SrsLagrangeDesc(C.Structure):
+    _fields_ = [("power", C.c_uint32), ("tau_g1", C.c_void_p), ("tau_g2", C.c_void_p),
+                ("alpha_tau_g1", C.c_void_p), ("beta_tau_g1", C.c_void_p)]
+
+
+# g16_srs_lagrange_check: the arrays are SRS_QUERIES[:4]; relations_failed has bit (1 << array)
+LAGRANGE_ARRAYS = SRS_QUERIES[:4]
+
+
+class SrsLagrangeReportC(C.Structure):
+    _fields_ = [("ok", C.c_uint8), ("relations_checked", C.c_uint8), ("relations_failed", C.c_uint32),
+                ("n_points", C.c_uint64 * 4), ("n_bad", C.c_uint64 * 4), ("n_infinity", C.c_uint64 * 4),
+                ("n_listed", C.c_uint32)]
+
+
 class PtauHeader(C.Structure):
     _fields_ = [("n8q", C.c_uint32), ("q", C.c_uint8 * 32), ("power", C.c_uint32), ("ceremony_power", C.c_uint32)]
 
@@ -169,6 +184,8 @@ ABI_SYMBOLS = [
     "g16_srs_create", "g16_srs_desc_of", "g16_srs_destroy", "g16_setup_from_srs", "g16_setup_from_srs_times",
     "g16_srs_check", "g16_ptau_open", "g16_ptau_open_mem", "g16_ptau_close", "g16_ptau_header_get", "g16_ptau_srs",
     "g16_ptau_write", "g16_srs_contribute", "g16_srs_contribute_times",
+    "g16_srs_prepare", "g16_srs_prepare_times", "g16_srs_lagrange_check", "g16_setup_from_prepared",
+    "g16_ptau_lagrange", "g16_ptau_write_prepared",
     "g16_points_from_ark", "g16_points_to_ark", "g16_ark_proofs_read", "g16_ark_proofs_write", "g16_ark_pk_size",
     "g16_ark_pk_read", "g16_ark_pk_key", "g16_ark_pk_close", "g16_ark_pk_write", "g16_ark_vk_size", "g16_ark_vk_read",
     "g16_ark_vk_write", "g16_ark_pk_layout", "g16_ark_vk_layout",
@@ -301,6 +318,17 @@ class Library:
             "g16_ptau_header_get": (C.c_int, [vp, C.POINTER(PtauHeader)]),
             "g16_ptau_srs": (C.c_int, [vp, C.POINTER(SrsDesc)]),
             "g16_ptau_write": (C.c_int, [C.c_char_p, C.POINTER(SrsDesc), C.c_uint32]),
+            "g16_srs_prepare": (C.c_int, [C.c_int, C.POINTER(SrsDesc), C.c_uint32, vp, vp, vp, vp]),
+            "g16_srs_prepare_times": (C.c_int, [C.POINTER(C.c_float), C.c_uint32]),
+            "g16_srs_lagrange_check": (C.c_int, [C.c_int, C.POINTER(SrsDesc), C.POINTER(SrsLagrangeDesc), vp,
+                                                 C.POINTER(KeyBadPoint), C.c_uint32,
+                                                 C.POINTER(SrsLagrangeReportC)]),
+            "g16_setup_from_prepared": (C.c_int, [C.c_int, C.POINTER(Csr), C.POINTER(Csr), C.POINTER(Csr),
+                                                  C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SrsDesc),
+                                                  C.POINTER(SrsLagrangeDesc), C.c_int, C.POINTER(vp)]),
+            "g16_ptau_lagrange": (C.c_int, [vp, C.POINTER(SrsLagrangeDesc)]),
+            "g16_ptau_write_prepared": (C.c_int, [C.c_char_p, C.POINTER(SrsDesc), C.POINTER(SrsLagrangeDesc),
+                                                  C.c_uint32]),
             "g16_points_from_ark": (C.c_int, [C.c_int, C.c_int, C.c_uint32, vp, C.c_size_t, C.c_uint64, vp, C.c_size_t,
                                               vp, _u64p]),
             "g16_points_to_ark": (C.c_int, [C.c_int, C.c_int, C.c_uint32, vp, C.c_size_t, C.c_uint64, vp, C.c_size_t,

@@ -305,6 +305,9 @@ uint64_t ptau_section_bytes(uint32_t id, uint32_t power) {
     case 2: return (2 * n - 1) * 64;
     case 3: return n * 128;
     case 4: case 5: return n * 64;
+    case 12: return (4 * n - 1) * 64;  // levels 0 .. power + 1
+    case 13: return (2 * n - 1) * 128; // levels 0 .. power
+    case 14: case 15: return (2 * n - 1) * 64;
     default: return 128;  // 6
   }
 }
@@ -676,7 +679,47 @@ g16_status g16_ptau_srs(const g16_ptau* p, g16_srs_desc* out) {
   return G16_OK;
 }
 
+g16_status g16_ptau_lagrange(const g16_ptau* p, g16_srs_lagrange_desc* out) {
+  if (!p || !out) return fail(G16_ERR_INVALID, "null argument");
+  memset(out, 0, sizeof *out);
+  const uint32_t power = p->hdr.power;
+  if (power > 27) return fail(G16_ERR_IO, "ptau: Lagrange sections of power " + std::to_string(power) + " > 27");
+  for (uint32_t id : {12u, 13u, 14u, 15u}) {
+    const auto it = p->sec.find(id);
+    if (it == p->sec.end())
+      return fail(G16_ERR_IO, "ptau: missing section " + std::to_string(id) + ": the file is not prepared");
+    if (it->second.size != ptau_section_bytes(id, power))
+      return fail(G16_ERR_IO, "ptau: section " + std::to_string(id) + " has " + std::to_string(it->second.size) +
+                                  " bytes, power " + std::to_string(power) + " needs " +
+                                  std::to_string(ptau_section_bytes(id, power)));
+  }
+  const uint8_t* d = p->data.data();
+  out->power = power;
+  out->tau_g1 = d + p->sec.at(12).pos;
+  out->tau_g2 = d + p->sec.at(13).pos;
+  out->alpha_tau_g1 = d + p->sec.at(14).pos;
+  out->beta_tau_g1 = d + p->sec.at(15).pos;
+  return G16_OK;
+}
+
+static g16_status ptau_write_impl(const char* path, const g16_srs_desc* srs, const g16_srs_lagrange_desc* lag,
+                                  uint32_t power);
+
 g16_status g16_ptau_write(const char* path, const g16_srs_desc* srs, uint32_t power) {
+  return ptau_write_impl(path, srs, nullptr, power);
+}
+
+g16_status g16_ptau_write_prepared(const char* path, const g16_srs_desc* srs, const g16_srs_lagrange_desc* lag,
+                                   uint32_t power) {
+  if (!lag || !lag->tau_g1 || !lag->tau_g2 || !lag->alpha_tau_g1 || !lag->beta_tau_g1)
+    return fail(G16_ERR_INVALID, "null argument");
+  if (power > 27) return fail(G16_ERR_INVALID, "ptau: Lagrange sections need power <= 27");
+  if (lag->power != power) return fail(G16_ERR_INVALID, "ptau: the Lagrange set is not of this power");
+  return ptau_write_impl(path, srs, lag, power);
+}
+
+static g16_status ptau_write_impl(const char* path, const g16_srs_desc* srs, const g16_srs_lagrange_desc* lag,
+                                  uint32_t power) {
   if (!path || !srs || !srs->tau_g1 || !srs->tau_g2 || !srs->alpha_tau_g1 || !srs->beta_tau_g1)
     return fail(G16_ERR_INVALID, "null argument");
   if (power > kPtauMaxPower) return fail(G16_ERR_INVALID, "ptau: power > 28");
@@ -695,7 +738,7 @@ g16_status g16_ptau_write(const char* path, const g16_srs_desc* srs, uint32_t po
   };
   put("ptau", 4);
   u32(1);
-  u32(7);
+  u32(lag ? 11 : 7);
   const uint64_t len1 = 4 + 32 + 4 + 4, len7 = 4;
   u32(1);
   put(&len1, 8);
@@ -711,6 +754,12 @@ g16_status g16_ptau_write(const char* path, const g16_srs_desc* srs, uint32_t po
   u32(7);
   put(&len7, 8);
   u32(0);  // no contributions recorded
+  if (lag) {
+    sec(12, lag->tau_g1);
+    sec(13, lag->tau_g2);
+    sec(14, lag->alpha_tau_g1);
+    sec(15, lag->beta_tau_g1);
+  }
   ok = (fclose(f) == 0) && ok;
   return ok ? G16_OK : fail(G16_ERR_IO, "short write");
 }

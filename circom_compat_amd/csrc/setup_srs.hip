@@ -9,28 +9,14 @@
 //                           entries of a size-2n DIF are the size-n transform of its first stage's lower half:
 //                           D[j] = omega_2n^-j / (2n) (tau_g1[j] - tau_g1[j+n]) -- one stage and a size-n transform
 //   h_query[i] (libsnark) = tau_g1[i+n] - tau_g1[i], i < n-1; entry n-1 is infinity
-// Everything on the lazy limbs of field29.h / ec29.h.  Kernels (all one wave per block, no atomics: the results
-// are group elements, the bytes do not depend on any order):
-//   k_naf         a scalar (twiddle) -> its non-adjacent form, two 256-bit masks, once per transform size
-//   k_gntt_stage  one DIF butterfly per lane, (P, Q) -> (P + Q, w^j (P - Q)), points resident as XYZZ.  The
-//                 product is a 255-step double-and-add over the NAF (254 doublings, ~85 additions).  Stages
-//                 with >= 64 blocks index j-major: a whole wave shares j, hence the digit schedule.
-//   k_scale       the upper half of the first stage times 1/n (the lower half has it in its twiddle): n/2
-//                 products instead of n; no output of a DIF passes through a twiddle on every path.
+// The transform itself (k_naf, k_gntt_stage, k_scale, k_affine) is gtransform.h; the kernels of this file:
 //   k_h_first     the first stage of the H transform (or the libsnark differences) straight from the affine SRS
-//   k_affine      XYZZ -> canonical affine, one Fermat inversion per SS_RUN points (Montgomery's trick), with the
-//                 bit reversal of the transform's output folded into the store
 //   k_comb_rows / k_comb_chunk / k_comb_fold   sum_j coeff Base[j] per wire: a lane per short row; long rows
 //                 (the constant wire: a term per constraint) in chunks of SS_CHUNK terms, one block each, then
 //                 one block per long row over its partial sums.  Coefficient 1 / r-1 is one mixed addition /
 //                 subtraction, anything else a double-and-add from the top bit of min(c, r - c).
 // g16_srs_create mints an SRS from a known trapdoor with keygen.hip's k_powers / k_fb_mul (tests, synthetic keys).
-#include <chrono>
-
-#include "../../include/g16_amd.h"
-#include "ec29.h"
-#include "keygen.h"
-#include "ntt.h"
+#include "gtransform.h"
 
 struct g16_srs {
   uint32_t n_tau_g1 = 0, n_tau = 0;
@@ -41,107 +27,8 @@ struct g16_srs {
 namespace g16 {
 namespace {
 
-constexpr uint32_t SS_BLOCK = 64;      // lanes per block: one wave
-constexpr uint32_t SS_RUN = 4;         // points per lane of k_affine: one inversion per SS_RUN points
 constexpr uint32_t SS_SHORT_MAX = 32;  // terms a single lane walks; longer rows go through the chunk kernels
 constexpr uint32_t SS_CHUNK = 1024;    // terms per block of k_comb_chunk
-
-// k = sum (pos_i - neg_i) 2^i, non-adjacent.  Digit i is bit i+1 of 3k minus bit i+1 of k; k < r < 2^254, so 3k
-// fits 256 bits and the leading digit is at most bit 254.
-struct Naf {
-  uint32_t pos[8], neg[8];
-};
-
-G16_HD Naf naf_of(const U256& k) {
-  uint32_t p[8], q[8];
-  uint64_t c = 0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    c += 3ull * k.v[i];
-    const uint32_t h = (uint32_t)c;
-    c >>= 32;
-    p[i] = h & ~k.v[i];
-    q[i] = k.v[i] & ~h;
-  }
-  Naf r;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    r.pos[i] = (p[i] >> 1) | (i < 7 ? p[i + 1] << 31 : 0u);
-    r.neg[i] = (q[i] >> 1) | (i < 7 ? q[i + 1] << 31 : 0u);
-  }
-  return r;
-}
-
-__global__ void __launch_bounds__(256) k_naf(const Fr* sc, uint32_t n, Naf* out) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  out[i] = naf_of(sc[i].to_canonical());
-}
-
-template <class LF>
-__device__ __forceinline__ Aff29<LF> aff_neg(const Aff29<LF>& p) {
-  return Aff29<LF>{p.x, p.y.neg().carry(), p.inf};
-}
-
-// s D for a point held as XYZZ: full additions (12M + 2S), D is not affine
-template <class LF>
-__device__ __forceinline__ XYZZ29<LF> mul_naf(const XYZZ29<LF>& D, const Naf* s) {
-  XYZZ29<LF> acc = XYZZ29<LF>::infinity();
-  if (D.is_inf()) return acc;
-  const LF ny = D.y.neg().carry();
-#pragma unroll 1
-  for (int w = 7; w >= 0; --w) {
-    const uint32_t pw = s->pos[w], nw = s->neg[w];
-    if (!(pw | nw) && acc.is_inf()) continue;
-#pragma unroll 1
-    for (int b = 31; b >= 0; --b) {
-      acc.dbl_in_place();
-      const uint32_t m = 1u << b;
-      if ((pw | nw) & m) acc.add(XYZZ29<LF>{D.x, (nw & m) ? ny : D.y, D.zz, D.zzz});
-    }
-  }
-  return acc;
-}
-
-// ---- group transform ---------------------------------------------------------------------------------
-template <class F>
-__global__ void __launch_bounds__(SS_BLOCK) k_load_affine(const Affine<F>* in, uint32_t n,
-                                                          XYZZ29<typename Lazy<F>::type>* out) {
-  const uint32_t i = blockIdx.x * SS_BLOCK + threadIdx.x;
-  if (i >= n) return;
-  out[i] = XYZZ29<typename Lazy<F>::type>::from_affine(affine_from_mont256<F>(in[i]));
-}
-
-// pair t of the stage with half-size 2^hl in a transform of 2 * npairs points; 2^nbl = blocks of the stage =
-// stride of j in the twiddle table tw[e] = NAF(omega^-e), e < npairs
-template <class LF>
-__global__ void __launch_bounds__(SS_BLOCK) k_gntt_stage(XYZZ29<LF>* a, uint32_t npairs, uint32_t hl, uint32_t nbl,
-                                                         uint32_t jmajor, const Naf* tw) {
-  const uint32_t t = blockIdx.x * SS_BLOCK + threadIdx.x;
-  if (t >= npairs) return;
-  uint32_t b, j;
-  if (jmajor) {
-    j = t >> nbl;
-    b = t & ((1u << nbl) - 1u);
-  } else {
-    b = t >> hl;
-    j = t & ((1u << hl) - 1u);
-  }
-  const size_t i0 = ((size_t)b << (hl + 1)) + j, i1 = i0 + ((size_t)1 << hl);
-  const XYZZ29<LF> P = a[i0], Q = a[i1];
-  XYZZ29<LF> S = P, D = P;
-  S.add(Q);
-  D.add(Q.neg());
-  a[i0] = S;
-  a[i1] = mul_naf(D, tw + ((size_t)j << nbl));
-}
-
-template <class LF>
-__global__ void __launch_bounds__(SS_BLOCK) k_scale(XYZZ29<LF>* a, uint32_t n, const Naf* s) {
-  const uint32_t i = blockIdx.x * SS_BLOCK + threadIdx.x;
-  if (i >= n) return;
-  a[i] = mul_naf(a[i], s);
-}
 
 // circom (c != NULL): out[j] = c[j] (tau[j] - tau[j+n]), tau[2n-1] = infinity; libsnark: tau[j+n] - tau[j], j < n-1
 __global__ void __launch_bounds__(SS_BLOCK) k_h_first(const G1Affine* tau, uint32_t n, const Naf* c, G1XYZZ29* out) {
@@ -162,44 +49,12 @@ __global__ void __launch_bounds__(SS_BLOCK) k_h_first(const G1Affine* tau, uint3
   }
 }
 
-// lane t of block g owns the points g * SS_BLOCK * SS_RUN + r * SS_BLOCK + t, r < SS_RUN.  Prefix products of the
-// ZZZ down the run (an infinite point counts as 1), one inversion, then back up: 1/ZZZ_r = inv(prefix_r ZZZ_r)
-// prefix_r, 1/ZZ = (ZZ / ZZZ)^2.  brev_bits >= 0: entry i of work is entry bitrev(i) of the output.
-// PACKED: the internal form load_packed_affine reads (the bases of the combinations); else the zkey encoding.
-template <class F, bool PACKED>
-__global__ void __launch_bounds__(SS_BLOCK) k_affine(const XYZZ29<typename Lazy<F>::type>* work, uint32_t n,
-                                                     int brev_bits, Affine<F>* out) {
-  using LF = typename Lazy<F>::type;
-  const uint32_t first = blockIdx.x * (SS_BLOCK * SS_RUN) + threadIdx.x;
-  LF pre[SS_RUN];
-  LF run = LF::one();
-#pragma unroll
-  for (uint32_t r = 0; r < SS_RUN; ++r) {
-    const uint32_t i = first + r * SS_BLOCK;
-    pre[r] = run;
-    if (i < n && !work[i].is_inf()) run = run * work[i].zzz;
-  }
-  LF inv = f29_inv(run);
-#pragma unroll
-  for (int r = SS_RUN - 1; r >= 0; --r) {
-    const uint32_t i = first + (uint32_t)r * SS_BLOCK;
-    if (i >= n) continue;
-    const uint32_t dst = brev_bits > 0 ? __brev(i) >> (32 - brev_bits) : i;
-    const XYZZ29<LF> P = work[i];
-    if (P.is_inf()) {
-      out[dst] = Affine<F>::infinity();
-      continue;
-    }
-    const LF iz3 = inv * pre[r];
-    inv = inv * P.zzz;
-    const LF iz2 = (iz3 * P.zz).sqr();
-    const LF x = P.x * iz2, y = P.y * iz3;
-    if (PACKED) {
-      out[dst] = store_packed_affine<F>(Aff29<LF>{x, y, false});
-    } else {
-      out[dst] = Affine<F>{x.to_mont256(), y.to_mont256()};
-    }
-  }
+// the zkey encoding (a level of a Lagrange set as it stands) -> the packed internal form the combinations read
+template <class F>
+__global__ void __launch_bounds__(SS_BLOCK) k_pack_affine(const Affine<F>* in, uint32_t n, Affine<F>* out) {
+  const uint32_t i = blockIdx.x * SS_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  out[i] = store_packed_affine<F>(affine_from_mont256<F>(in[i]));
 }
 
 // ---- sparse point combinations ---------------------------------------------------------------------------
@@ -329,50 +184,7 @@ __global__ void __launch_bounds__(SS_BLOCK) k_comb_fold(const CombLong* rows, co
 // ---- host side ---------------------------------------------------------------------------------------
 enum { T_UPLOAD = 0, T_NTT_G1, T_NTT_G2, T_H, T_AFFINE, T_COMB, T_DOWNLOAD, T_COUNT };
 
-struct PhaseClock {
-  float* ms;
-  hipStream_t s;
-  std::chrono::steady_clock::time_point t0;
-  PhaseClock(float* m, hipStream_t st) : ms(m), s(st), t0(std::chrono::steady_clock::now()) {}
-  void lap(int phase) {
-    G16_HIP(hipStreamSynchronize(s));
-    const auto t1 = std::chrono::steady_clock::now();
-    ms[phase] += std::chrono::duration<float, std::milli>(t1 - t0).count();
-    t0 = t1;
-  }
-};
-
 thread_local float t_phase_ms[T_COUNT];
-
-struct Twiddles {  // of one transform size n = 2^k
-  DevBuf<Naf> tw, tw_scaled, top, h;  // omega_n^-e | omega_n^-e / n, e < n/2 | 1/n | omega_2n^-j / (2n), j < n
-};
-
-void naf_table(const Fr& base, const Fr& scale, uint32_t count, Fr* tmp, DevBuf<Naf>& out, hipStream_t s) {
-  out.alloc(count ? count : 1);
-  if (!count) return;
-  fr_powers(base, scale, tmp, count, count, s);
-  G16_LAUNCH(k_naf, ceil_div(count, 256), 256, 0, s, (const Fr*)tmp, count, out.p);
-}
-
-// in place: natural order in, bit-reversed out; scaled: times 1/n
-template <class LF>
-void group_intt(XYZZ29<LF>* a, int k, const Twiddles& T, bool scaled, hipStream_t s) {
-  const uint32_t npairs = k ? 1u << (k - 1) : 0;
-  for (int st = 0; st < k; ++st) {
-    const uint32_t hl = (uint32_t)(k - 1 - st), nbl = (uint32_t)st;
-    const Naf* tw = (st == 0 && scaled) ? T.tw_scaled.p : T.tw.p;
-    G16_LAUNCH((k_gntt_stage<LF>), ceil_div(npairs, SS_BLOCK), SS_BLOCK, 0, s, a, npairs, hl, nbl,
-               (uint32_t)(nbl >= 6 ? 1 : 0), tw);
-    if (st == 0 && scaled)
-      G16_LAUNCH((k_scale<LF>), ceil_div(npairs, SS_BLOCK), SS_BLOCK, 0, s, a, npairs, (const Naf*)T.top.p);
-  }
-}
-
-template <class F, bool PACKED>
-void to_affine(const XYZZ29<typename Lazy<F>::type>* work, uint32_t n, int brev_bits, Affine<F>* out, hipStream_t s) {
-  if (n) G16_LAUNCH((k_affine<F, PACKED>), ceil_div(n, SS_BLOCK * SS_RUN), SS_BLOCK, 0, s, work, n, brev_bits, out);
-}
 
 struct DevCsr {
   DevBuf<uint32_t> rowptr, col;
@@ -438,12 +250,6 @@ void combine(const DevCsr* const* mats, const Affine<F>* const* bases, uint32_t 
   }
 }
 
-template <class T>
-void fetch(std::vector<uint8_t>& dst, const T* dev, size_t count) {
-  dst.resize(count ? count * sizeof(T) : 1);
-  if (count) G16_HIP(hipMemcpy(dst.data(), dev, count * sizeof(T), hipMemcpyDeviceToHost));
-}
-
 Fr fr_of_limbs(const uint64_t* p) {
   Fr a;
   memcpy(a.v, p, 32);
@@ -454,6 +260,11 @@ Fr fr_of_limbs(const uint64_t* p) {
 }  // namespace g16
 
 using namespace g16;
+
+// lag == NULL: the Lagrange bases and the circom H by the group transform; else read from the prepared set
+static g16_status setup_impl(int device, const g16_csr* at, const g16_csr* bt, const g16_csr* ct, uint32_t n_vars,
+                             uint32_t n_public, uint32_t num_constraints, const g16_srs_desc* srs,
+                             const g16_srs_lagrange_desc* lag, int reduction, g16_setup** out);
 
 extern "C" {
 
@@ -527,6 +338,22 @@ void g16_srs_destroy(g16_srs* s) { delete s; }
 g16_status g16_setup_from_srs(int device, const g16_csr* at, const g16_csr* bt, const g16_csr* ct, uint32_t n_vars,
                               uint32_t n_public, uint32_t num_constraints, const g16_srs_desc* srs, int reduction,
                               g16_setup** out) {
+  return setup_impl(device, at, bt, ct, n_vars, n_public, num_constraints, srs, nullptr, reduction, out);
+}
+
+g16_status g16_setup_from_prepared(int device, const g16_csr* at, const g16_csr* bt, const g16_csr* ct,
+                                   uint32_t n_vars, uint32_t n_public, uint32_t num_constraints,
+                                   const g16_srs_desc* srs, const g16_srs_lagrange_desc* lag, int reduction,
+                                   g16_setup** out) {
+  if (!lag) return G16_ERR_INVALID;
+  return setup_impl(device, at, bt, ct, n_vars, n_public, num_constraints, srs, lag, reduction, out);
+}
+
+}  // extern "C"
+
+static g16_status setup_impl(int device, const g16_csr* at, const g16_csr* bt, const g16_csr* ct, uint32_t n_vars,
+                             uint32_t n_public, uint32_t num_constraints, const g16_srs_desc* srs,
+                             const g16_srs_lagrange_desc* lag, int reduction, g16_setup** out) {
   if (!at || !bt || !ct || !srs || !out) return G16_ERR_INVALID;
   if (reduction != G16_REDUCTION_CIRCOM && reduction != G16_REDUCTION_LIBSNARK) return G16_ERR_INVALID;
   *out = nullptr;
@@ -537,6 +364,11 @@ g16_status g16_setup_from_srs(int device, const g16_csr* at, const g16_csr* bt, 
   const uint32_t n = 1u << k;
   if ((uint64_t)srs->n_tau_g1 < 2 * (uint64_t)n - 1 || srs->n_tau < n) return G16_ERR_INVALID;
   if (!srs->tau_g1 || !srs->tau_g2 || !srs->alpha_tau_g1 || !srs->beta_tau_g1) return G16_ERR_INVALID;
+  if (lag) {
+    if (lag->power > 27) return G16_ERR_DOMAIN_TOO_LARGE;
+    if (lag->power < (uint32_t)k) return G16_ERR_INVALID;
+    if (!lag->tau_g1 || !lag->tau_g2 || !lag->alpha_tau_g1 || !lag->beta_tau_g1) return G16_ERR_INVALID;
+  }
   if (N < num_inputs || !at->row_ptr || !bt->row_ptr || !ct->row_ptr) return G16_ERR_INVALID;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return G16_ERR_NO_DEVICE;
@@ -567,29 +399,35 @@ g16_status g16_setup_from_srs(int device, const g16_csr* at, const g16_csr* bt, 
     lag2.alloc(n);
     w1.alloc(maxn);
     w2.alloc(maxn);
-    G16_HIP(hipMemcpy(tau1.p, srs->tau_g1, (size_t)n1 * 64, hipMemcpyHostToDevice));
+    const bool need_tau = !lag || reduction == G16_REDUCTION_LIBSNARK;
+    if (need_tau) G16_HIP(hipMemcpy(tau1.p, srs->tau_g1, (size_t)n1 * 64, hipMemcpyHostToDevice));
     DevCsr dA, dB, dC;
     dA.upload(at, N);
     dB.upload(bt, N);
     dC.upload(ct, N);
     Twiddles T;
-    {
+    if (!lag) {
       DevBuf<Fr> tmp;
       tmp.alloc(n);
-      const Fr winv = fr_root_of_unity(k).inv(), ninv = Fr::from_u32(n).inv();
-      naf_table(winv, Fr::one(), n / 2, tmp.p, T.tw, s);
-      naf_table(winv, ninv, n / 2, tmp.p, T.tw_scaled, s);
-      naf_table(Fr::one(), ninv, 1, tmp.p, T.top, s);
-      if (reduction == G16_REDUCTION_CIRCOM)
-        naf_table(fr_root_of_unity(k + 1).inv(), Fr::from_u32(2 * n).inv(), n, tmp.p, T.h, s);
-      G16_HIP(hipStreamSynchronize(s));
+      build_twiddles(T, k, reduction == G16_REDUCTION_CIRCOM, tmp.p, s);
     }
     clk.lap(T_UPLOAD);
 
     // ---- Lagrange bases: G1 three times, G2 once; natural order, packed internal affine
     const uint8_t* g1_src[3] = {nullptr, srs->alpha_tau_g1, srs->beta_tau_g1};
     G1Affine* g1_dst[3] = {lag1.p, lagA.p, lagB.p};
-    for (int q = 0; q < 3; ++q) {
+    const size_t lvl = (size_t)n - 1;  // level k of a Lagrange array starts at point 2^k - 1
+    if (lag) {  // level k as it stands: no transform, only the packed form
+      const uint8_t* g1_lag[3] = {lag->tau_g1, lag->alpha_tau_g1, lag->beta_tau_g1};
+      for (int q = 0; q < 3; ++q) {
+        G16_HIP(hipMemcpy(o1.p, g1_lag[q] + lvl * 64, (size_t)n * 64, hipMemcpyHostToDevice));
+        G16_LAUNCH((k_pack_affine<Fq>), ceil_div(n, SS_BLOCK), SS_BLOCK, 0, s, (const G1Affine*)o1.p, n, g1_dst[q]);
+      }
+      G16_HIP(hipMemcpy(o2.p, lag->tau_g2 + lvl * 128, (size_t)n * 128, hipMemcpyHostToDevice));
+      G16_LAUNCH((k_pack_affine<Fq2>), ceil_div(n, SS_BLOCK), SS_BLOCK, 0, s, (const G2Affine*)o2.p, n, lag2.p);
+      clk.lap(T_UPLOAD);
+    }
+    for (int q = 0; q < 3 && !lag; ++q) {
       const G1Affine* in = tau1.p;
       if (g1_src[q]) {
         G16_HIP(hipMemcpy(o1.p, g1_src[q], (size_t)n * 64, hipMemcpyHostToDevice));
@@ -601,15 +439,26 @@ g16_status g16_setup_from_srs(int device, const g16_csr* at, const g16_csr* bt, 
       to_affine<Fq, true>(w1.p, n, k, g1_dst[q], s);
       clk.lap(T_AFFINE);
     }
-    G16_HIP(hipMemcpy(o2.p, srs->tau_g2, (size_t)n * 128, hipMemcpyHostToDevice));
-    G16_LAUNCH((k_load_affine<Fq2>), ceil_div(n, SS_BLOCK), SS_BLOCK, 0, s, (const G2Affine*)o2.p, n, w2.p);
-    group_intt<Fq2x29>(w2.p, k, T, true, s);
-    clk.lap(T_NTT_G2);
-    to_affine<Fq2, true>(w2.p, n, k, lag2.p, s);
-    clk.lap(T_AFFINE);
+    if (!lag) {
+      G16_HIP(hipMemcpy(o2.p, srs->tau_g2, (size_t)n * 128, hipMemcpyHostToDevice));
+      G16_LAUNCH((k_load_affine<Fq2>), ceil_div(n, SS_BLOCK), SS_BLOCK, 0, s, (const G2Affine*)o2.p, n, w2.p);
+      group_intt<Fq2x29>(w2.p, k, T, true, s);
+      clk.lap(T_NTT_G2);
+      to_affine<Fq2, true>(w2.p, n, k, lag2.p, s);
+      clk.lap(T_AFFINE);
+    }
 
     // ---- H
-    if (reduction == G16_REDUCTION_CIRCOM) {
+    if (lag && reduction == G16_REDUCTION_CIRCOM) {
+      // the odd entries of level k + 1 of tau_g1 AS IT STANDS.  For k == power that level is the transform of
+      // tau^0 .. tau^(2n-2) | infinity, the h_query of g16_setup_from_srs; below the power it is the transform of
+      // all 2n powers, and the two queries differ point by point by multiples of tau^(2n-1) G -- the same proofs,
+      // since the quotient has no coefficient at x^(2n-1) (include/g16_amd.h).
+      const uint8_t* top = lag->tau_g1 + (2 * (size_t)n - 1) * 64;
+      S->h.resize((size_t)n * 64);
+      for (size_t i = 0; i < n; ++i) memcpy(S->h.data() + i * 64, top + (2 * i + 1) * 64, 64);
+      clk.lap(T_H);
+    } else if (reduction == G16_REDUCTION_CIRCOM) {
       G16_LAUNCH(k_h_first, ceil_div(n, SS_BLOCK), SS_BLOCK, 0, s, (const G1Affine*)tau1.p, n, (const Naf*)T.h.p, w1.p);
       group_intt<Fq29>(w1.p, k, T, false, s);
       clk.lap(T_H);
@@ -619,8 +468,10 @@ g16_status g16_setup_from_srs(int device, const g16_csr* at, const g16_csr* bt, 
       clk.lap(T_H);
       to_affine<Fq, false>(w1.p, n, -1, o1.p, s);
     }
-    clk.lap(T_AFFINE);
-    fetch(S->h, o1.p, n);
+    if (!(lag && reduction == G16_REDUCTION_CIRCOM)) {
+      clk.lap(T_AFFINE);
+      fetch(S->h, o1.p, n);
+    }
     clk.lap(T_DOWNLOAD);
 
     // ---- queries
@@ -684,6 +535,8 @@ g16_status g16_setup_from_srs(int device, const g16_csr* at, const g16_csr* bt, 
     return G16_ERR_INTERNAL;
   }
 }
+
+extern "C" {
 
 g16_status g16_setup_from_srs_times(float* ms, uint32_t cap) {
   if (!ms) return G16_ERR_INVALID;

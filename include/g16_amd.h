@@ -741,6 +741,92 @@ g16_status g16_srs_contribute(int device, const g16_srs_desc* srs,
                               uint8_t* beta_tau_g1_out, uint8_t beta_g2_out[128]);
 g16_status g16_srs_contribute_times(float* ms, uint32_t cap);
 
+/* ---- prepared powers of tau: the Lagrange sections (not on the proving path) ----------------------- */
+/* `snarkjs powersoftau prepare phase2`: a PREPARED .ptau carries, next to the four monomial arrays, their
+ * Lagrange-basis copies for every domain size up to the file's power (sections 12-15); `snarkjs zkey new` builds
+ * keys from those and refuses a file without them.  A LAGRANGE SET of power P is four packed arrays in the usual
+ * point encoding (Montgomery LE, all-zero = infinity):
+ *   tau_g1        (section 12)  levels p = 0 .. P+1   2^(P+2) - 1 points of  64 bytes
+ *   tau_g2        (section 13)  levels p = 0 .. P     2^(P+1) - 1 points of 128 bytes
+ *   alpha_tau_g1  (section 14)  levels p = 0 .. P     2^(P+1) - 1 points of  64 bytes
+ *   beta_tau_g1   (section 15)  levels p = 0 .. P     2^(P+1) - 1 points of  64 bytes
+ * Level p starts at point offset 2^p - 1 and holds 2^p points; entry j of level p is
+ *   (1 / 2^p) sum_{i < 2^p} omega_p^(-i j) M[i]      natural order, omega_p the 2^p-th root g16_fft_in_place uses
+ * with M the array's monomial section (M[i] = tau^i G1 and so on): L_j(tau) G of the domain of size 2^p.  Level
+ * P+1 of tau_g1 reads M[2^(P+1) - 1] as infinity: a file holds only 2^(P+1) - 1 powers (g16_ptau_write), and
+ * entries a longer g16_srs_desc holds beyond that are dropped.
+ * THIS LAYOUT IS WRITTEN FROM KNOWLEDGE OF snarkjs; no snarkjs and no prepared file were on hand to pin it
+ * (g16_loaders.h says the same of sections 1-7).  Supported: P <= 27 (level 28 is the last one Fr has a root
+ * for); above that G16_ERR_DOMAIN_TOO_LARGE.
+ *
+ * g16_srs_prepare computes every level of the four arrays with the group transform of g16_setup_from_srs (one
+ * copy of the kernels, csrc/gtransform.h).  One level is resident on the device at a time and is downloaded as it
+ * finishes: 144 bytes per G1 and 288 per G2 point of the level, 64 per point of the level's input, 2 x 64 bytes
+ * of twiddle schedule per pair.  No atomics: the same bytes on every run.  Standalone: no ctx is needed, a ctx
+ * alive on the device is left untouched.  An SRS with fewer than 2^(P+1) - 1 / 2^P entries, a NULL pointer:
+ * G16_ERR_INVALID, and nothing is written.  g16_srs_prepare_times: milliseconds the calling thread's last
+ * g16_srs_prepare spent in the phases of g16_setup_from_srs_times (0 upload + twiddle schedules, 1 G1
+ * transforms, 2 G2 transforms, 4 affine passes, 6 downloads; the others 0).
+ *
+ * g16_srs_lagrange_check verifies a Lagrange set against the monomial arrays it claims to come from -- what
+ * nothing else does for sections 12-15 of a downloaded file (g16_srs_check looks at the monomial arrays only).
+ * Structural part: every Lagrange point is tested as in g16_srs_check (canonical, on the curve, G2 in the
+ * subgroup; infinity is valid and counted); bad_out receives the first min(bad_cap, 65536) bad points sorted by
+ * (array, index), query = G16_SRS_Q_TAU_G1 .. _BETA_TAU_G1, index = the position in the section (level p,
+ * entry j: 2^p - 1 + j).  Relation part, per array and only when no structural check failed: with a 128-bit
+ * rho for every Lagrange point,
+ *   sum_p sum_j rho^(p)_j Lambda^(p)[j]  ==  sum_i C_i M[i],      C = sum_p iNTT_{2^p}(rho^(p)) zero-extended
+ * -- all levels of an array fold into ONE 128-bit combination over the Lagrange points and ONE full-width
+ * combination over the monomial points; the two sums are compared as group elements on the device, no pairing.
+ * C is computed on the device with the Fr transform of the witness map.  The pad entry of level P+1 of tau_g1
+ * contributes nothing.  relations_failed has bit (1 << array) for an array whose sums differ.
+ * Soundness: every point that reaches the relation is in its prime-order group (G1 has cofactor 1, G2 Lagrange
+ * points are subgroup-tested, the monomial arrays are expected to have passed g16_srs_check), so a wrong entry
+ * differs from the right one by d G for a scalar d and the relation holds iff sum rho d = 0 mod r: with
+ * unpredictable rho a set with a wrong entry passes with probability at most 2^-127 (the small-exponent test of
+ * g16_srs_check).  Whoever knows rho makes two entries cancel (d_j = rho_k, d_k = -rho_j), and the relation holds.
+ * rho: ((2^(P+2) - 1) + 3 (2^(P+1) - 1)) x 2 u64 in array order (tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1),
+ *      levels ascending (little-endian 128-bit integers, NOT Montgomery), every one non-zero (a zero entry:
+ *      G16_ERR_INVALID), or NULL: drawn from the operating system's CSPRNG (a failure to get randomness is
+ *      G16_ERR_INTERNAL, never a fixed fallback).
+ * A monomial point that is malformed (non-canonical or off the curve) is skipped, not dereferenced further.
+ * Memory: the arrays are streamed through two page-locked host slots and two device slots of min(2^18, longest
+ * array) points; besides them 32 + 2 x 36 bytes per point of the top level (C and the transform's planes).
+ * G16_LAGCHECK_CHUNK=<points> overrides the chunk (tests).  No atomics: the same report and list on every run.
+ *
+ * g16_setup_from_prepared is g16_setup_from_srs with every transform skipped: the four Lagrange bases are level
+ * k (domain = 2^k) of the four arrays, the circom H query is the odd entries of level k+1 of tau_g1 AS IT
+ * STANDS, the libsnark H query comes from the monomial tau_g1 as in g16_setup_from_srs, the single points from
+ * srs.  lag->power < k: G16_ERR_INVALID.  For k == power the key is byte for byte g16_setup_from_srs's.  For
+ * k < power every field but the circom h_query is: g16_setup_from_srs follows the reference's witness map
+ * (the transform of tau^0 .. tau^(2n-2) padded with ONE zero), whereas level k+1 below the power is the transform
+ * of all 2n powers, tau^(2n-1) included -- what `snarkjs zkey new` takes.  The two queries differ point by point
+ * by multiples of tau^(2n-1) G and yield the same proofs, since d = A B - C has degree <= 2n-2 and so no
+ * coefficient at x^(2n-1); a pairing comparison of the two H queries (g16_contribution_check against a key
+ * rebuilt the other way) does see the difference.  Its phase timer is g16_setup_from_srs_times.              */
+typedef struct {
+  uint32_t power;
+  const uint8_t *tau_g1, *tau_g2, *alpha_tau_g1, *beta_tau_g1;
+} g16_srs_lagrange_desc;
+enum { G16_LAGRANGE_N_ARRAYS = 4 };  /* indexed by G16_SRS_Q_TAU_G1 .. G16_SRS_Q_BETA_TAU_G1 */
+typedef struct {
+  uint8_t  ok;                 /* 1 iff no bad point and no failed relation */
+  uint8_t  relations_checked;  /* 0 when a structural failure made the relations meaningless */
+  uint32_t relations_failed;   /* bit (1 << array) */
+  uint64_t n_points[G16_LAGRANGE_N_ARRAYS], n_bad[G16_LAGRANGE_N_ARRAYS], n_infinity[G16_LAGRANGE_N_ARRAYS];
+  uint32_t n_listed;           /* entries written to bad_out */
+} g16_srs_lagrange_report;
+g16_status g16_srs_prepare(int device, const g16_srs_desc* srs, uint32_t power, uint8_t* tau_g1_out,
+                           uint8_t* tau_g2_out, uint8_t* alpha_tau_g1_out, uint8_t* beta_tau_g1_out);
+g16_status g16_srs_prepare_times(float* ms, uint32_t cap);
+g16_status g16_srs_lagrange_check(int device, const g16_srs_desc* srs, const g16_srs_lagrange_desc* lag,
+                                  const uint64_t* rho /* NULL = CSPRNG */, g16_key_bad_point* bad_out,
+                                  uint32_t bad_cap, g16_srs_lagrange_report* report);
+g16_status g16_setup_from_prepared(int device, const g16_csr* at, const g16_csr* bt, const g16_csr* ct,
+                                   uint32_t n_vars, uint32_t n_public, uint32_t num_constraints,
+                                   const g16_srs_desc* srs, const g16_srs_lagrange_desc* lag, int reduction,
+                                   g16_setup** out);
+
 /* ---- arkworks serialization (not on the proving path) ---------------------------------------------- */
 /* Every other entry point takes and returns points in the .zkey encoding (32-byte little-endian MONTGOMERY
  * coordinates, affine x|y, all-zero = infinity).  arkworks exchanges keys, verifying keys and proofs in

@@ -67,7 +67,10 @@ g16_status g16_zkey_write(const char* path, const g16_key_desc* key, const uint8
  *   2  tauG1, 2 * 2^power - 1 G1 points      3  tauG2, 2^power G2 points
  *   4  alphaTauG1, 2^power G1 points          5  betaTauG1, 2^power G1 points        6  betaG2, one G2 point
  *   7  contributions: ignored on read, written as a zero count
- *   12..15  the Lagrange-form copies of a "prepared" file: ignored, g16_setup_from_srs computes its own
+ *   12..15  the Lagrange-form copies of a "prepared" file (`powersoftau prepare phase2`): tauG1 in levels
+ *           0 .. power + 1 (4 * 2^power - 1 G1 points), tauG2, alphaTauG1, betaTauG1 in levels 0 .. power
+ *           (2 * 2^power - 1 points each); the layout of a level is g16_amd.h's ("prepared powers of tau").
+ *           g16_ptau_open and g16_ptau_srs ignore them whatever their size; g16_ptau_lagrange hands them out.
  * Points in the encoding of the rest of the ABI: 32-byte little-endian Montgomery coordinates, all-zero =
  * infinity.  THIS DESCRIPTION IS WRITTEN FROM KNOWLEDGE OF snarkjs: no .ptau file and no snarkjs were at hand to
  * pin it to, the reader is tested against this writer and against an independent encoding of the same
@@ -88,6 +91,13 @@ g16_status g16_ptau_srs(const g16_ptau* p, g16_srs_desc* out);
 /* writes sections 1..7 from an SRS with n_tau_g1 >= 2 * 2^power - 1 and n_tau >= 2^power (entries beyond are
  * dropped); ceremony_power = power                                                                       */
 g16_status g16_ptau_write(const char* path, const g16_srs_desc* srs, uint32_t power);
+/* zero-copy views of sections 12..15, owned by the handle.  G16_ERR_IO with a message: one of them is absent (the
+ * file is not prepared), its size does not match the power, or power > 27.  The points are handed out as they
+ * come: run g16_srs_lagrange_check on them.                                                              */
+g16_status g16_ptau_lagrange(const g16_ptau* p, g16_srs_lagrange_desc* out);
+/* g16_ptau_write plus sections 12..15 from a Lagrange set of exactly this power (power <= 27)           */
+g16_status g16_ptau_write_prepared(const char* path, const g16_srs_desc* srs, const g16_srs_lagrange_desc* lag,
+                                   uint32_t power);
 
 /* ------------------------------------------------ arkworks containers: the layout walk -------- */
 /* Where the fields of an ark-serialize'd ProvingKey<Bn254> / VerifyingKey<Bn254> lie (the format: g16_amd.h,

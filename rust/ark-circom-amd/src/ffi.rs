@@ -256,6 +256,31 @@ pub struct g16_srs_report {
     pub n_listed: u32,
 }
 
+/// Sections 12-15 of a prepared .ptau: tau_g1 in levels 0..=power+1, the others in levels 0..=power.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct g16_srs_lagrange_desc {
+    pub power: u32,
+    pub tau_g1: *const u8,
+    pub tau_g2: *const u8,
+    pub alpha_tau_g1: *const u8,
+    pub beta_tau_g1: *const u8,
+}
+
+pub const G16_LAGRANGE_N_ARRAYS: usize = 4;
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct g16_srs_lagrange_report {
+    pub ok: u8,
+    pub relations_checked: u8,
+    pub relations_failed: u32,
+    pub n_points: [u64; G16_LAGRANGE_N_ARRAYS],
+    pub n_bad: [u64; G16_LAGRANGE_N_ARRAYS],
+    pub n_infinity: [u64; G16_LAGRANGE_N_ARRAYS],
+    pub n_listed: u32,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct g16_ptau_header {
@@ -334,6 +359,10 @@ extern "C" {
     pub fn g16_srs_check(device: c_int, srs: *const g16_srs_desc, rho: *const u64, bad_out: *mut g16_key_bad_point, bad_cap: u32, report: *mut g16_srs_report) -> g16_status;
     pub fn g16_srs_contribute(device: c_int, srs: *const g16_srs_desc, secrets: *const u64, tau_g1_out: *mut u8, tau_g2_out: *mut u8, alpha_tau_g1_out: *mut u8, beta_tau_g1_out: *mut u8, beta_g2_out: *mut u8) -> g16_status;
     pub fn g16_srs_contribute_times(ms: *mut c_float, cap: u32) -> g16_status;
+    pub fn g16_srs_prepare(device: c_int, srs: *const g16_srs_desc, power: u32, tau_g1_out: *mut u8, tau_g2_out: *mut u8, alpha_tau_g1_out: *mut u8, beta_tau_g1_out: *mut u8) -> g16_status;
+    pub fn g16_srs_prepare_times(ms: *mut c_float, cap: u32) -> g16_status;
+    pub fn g16_srs_lagrange_check(device: c_int, srs: *const g16_srs_desc, lag: *const g16_srs_lagrange_desc, rho: *const u64, bad_out: *mut g16_key_bad_point, bad_cap: u32, report: *mut g16_srs_lagrange_report) -> g16_status;
+    pub fn g16_setup_from_prepared(device: c_int, at: *const g16_csr, bt: *const g16_csr, ct: *const g16_csr, n_vars: u32, n_public: u32, num_constraints: u32, srs: *const g16_srs_desc, lag: *const g16_srs_lagrange_desc, reduction: c_int, out: *mut *mut g16_setup) -> g16_status;
     pub fn g16_points_from_ark(device: c_int, group: c_int, flags: u32, input: *const u8, in_stride: usize, n: u64, out: *mut u8, out_stride: usize, reason_out: *mut u8, n_bad: *mut u64) -> g16_status;
     pub fn g16_points_to_ark(device: c_int, group: c_int, flags: u32, input: *const u8, in_stride: usize, n: u64, out: *mut u8, out_stride: usize, n_bad: *mut u64) -> g16_status;
     pub fn g16_ark_proofs_read(device: c_int, flags: u32, input: *const u8, n: u64, proofs_out: *mut u8, reason_out: *mut u8, n_bad: *mut u64) -> g16_status;
@@ -366,6 +395,8 @@ extern "C" {
     pub fn g16_ptau_header_get(p: *const g16_ptau, out: *mut g16_ptau_header) -> g16_status;
     pub fn g16_ptau_srs(p: *const g16_ptau, out: *mut g16_srs_desc) -> g16_status;
     pub fn g16_ptau_write(path: *const c_char, srs: *const g16_srs_desc, power: u32) -> g16_status;
+    pub fn g16_ptau_lagrange(p: *const g16_ptau, out: *mut g16_srs_lagrange_desc) -> g16_status;
+    pub fn g16_ptau_write_prepared(path: *const c_char, srs: *const g16_srs_desc, lag: *const g16_srs_lagrange_desc, power: u32) -> g16_status;
     pub fn g16_zkey_open(path: *const c_char, out: *mut *mut g16_zkey) -> g16_status;
     pub fn g16_zkey_open_mem(data: *const u8, len: usize, out: *mut *mut g16_zkey) -> g16_status;
     pub fn g16_zkey_close(z: *mut g16_zkey);
