@@ -18,8 +18,9 @@ Host-side mirror (Python harness flavour) of the reference's surface for the pro
     Groth16::prove(&pk, circuit, rng)  src/zkey.rs:866      Groth16.prove(pk, matrices, circuit, rng)
 
 All arithmetic happens in libg16_amd.so (hand-written HIP for gfx950) behind the C ABI of
-include/g16_amd.h.  Witness generation (circom WASM), Ethereum helpers and the arkworks
-ConstraintSystem layer are out of scope.  There is no CPU fallback.
+include/g16_amd.h.  Witness generation (circom WASM) and the arkworks ConstraintSystem layer are out of
+scope; snarkjs JSON and the Ethereum forms (reference src/ethereum.rs) are in snarkjs.py,
+the command line in __main__.py.  There is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -44,7 +45,9 @@ __all__ = ["read_zkey", "R1CSFile", "R1CS", "CircomCircuit", "CircomBuilder", "C
            "points_from_ark", "points_to_ark", "read_ark_key", "write_ark_key", "read_ark_vk", "write_ark_vk",
            "proofs_from_ark", "proofs_to_ark", "ark_point_bytes", "rerandomize", "rerandomize_keys",
            "rerandomize_times", "PreparedVerifyingKey", "prepare_verifying_key", "verify_prepared", "pairing_check",
-           "verify_prepared_times"]
+           "verify_prepared_times", "Witness", "open_wtns", "write_wtns", "fr_from_canonical", "fr_from_canonical_times", "read_proof_json",
+           "write_proof_json", "read_public_json", "write_public_json", "read_vk_json", "write_vk_json",
+           "inputs_to_eth", "solidity_calldata"]
 
 FR_MODULUS = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 
@@ -153,6 +156,17 @@ class VerifyingKey:
     def __init__(self, alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1):
         self.alpha_g1, self.beta_g2, self.gamma_g2, self.delta_g2 = alpha_g1, beta_g2, gamma_g2, delta_g2
         self.gamma_abc_g1 = gamma_abc_g1  # (p+1, 64) uint8
+
+    def to_eth(self, device=0, lib: Optional[B.Library] = None):
+        """ethereum::VerifyingKey::as_tuple (reference src/ethereum.rs:139-161): (alpha1, beta2, gamma2, delta2, ic) as
+        ints, G2 with c1 first (snarkjs.vk_to_eth)"""
+        from . import snarkjs
+        return snarkjs.vk_to_eth(self, device, lib)
+
+    @staticmethod
+    def from_eth(t, device=0, lib: Optional[B.Library] = None) -> "VerifyingKey":
+        from . import snarkjs
+        return snarkjs.vk_from_eth(t, device, lib)
 
 
 class ProvingKey:
@@ -312,6 +326,107 @@ def read_wtns(src, lib: Optional[B.Library] = None) -> np.ndarray:
     return arr.reshape(-1, 4)
 
 
+class Witness:
+    """A snarkjs / rapidsnark .wtns as it lies in the file (open_wtns): the header is checked, the values stay
+    canonical 32-byte little-endian integers.  Prover.prove_wtns converts and range-tests them on the GPU.
+    n: number of values; canonical: read-only (n, 32) uint8 view of the mapping (valid while this object lives)."""
+
+    def __init__(self, lib, handle, n, canonical):
+        self.lib, self._handle, self.n, self.canonical = lib, handle, n, canonical
+
+    def public_inputs(self, n_public: int) -> List[int]:
+        """w[1 .. n_public] as ints (converted on the host: there are few of them)"""
+        if n_public + 1 > self.n:
+            raise G16Error(B.G16_ERR_INVALID, f"{n_public} public inputs in a witness of {self.n} values")
+        raw = self.canonical[1:1 + n_public].tobytes()
+        return [int.from_bytes(raw[i:i + 32], "little") for i in range(0, len(raw), 32)]
+
+    def to_montgomery(self, device=0) -> np.ndarray:
+        """(n, 4) uint64 Montgomery limbs, what read_wtns returns, converted on the GPU (g16_fr_convert)"""
+        return fr_from_canonical(self.canonical, device=device, lib=self.lib)
+
+
+def open_wtns(src, lib: Optional[B.Library] = None) -> Witness:
+    """snarkjs .wtns (path or bytes) -> Witness: the file is mapped, the header checked by read_wtns' rules (and with
+    its messages), nothing is converted, copied or range-tested here (g16_wtns_open)."""
+    lib = lib or B.load()
+    h = C.c_void_p()
+    if isinstance(src, (bytes, bytearray, memoryview)):
+        buf = np.frombuffer(bytes(src), dtype=np.uint8)
+        lib.check(lib.g16_wtns_open_mem(_np_ptr(buf), buf.shape[0], C.byref(h)), loader=True)
+    else:
+        lib.check(lib.g16_wtns_open(os.fsencode(src), C.byref(h)), loader=True)
+    handle = _Handle(lib, h, lib.g16_wtns_close)
+    n = int(lib.g16_wtns_count(h))
+    if n:
+        vals = np.ctypeslib.as_array(C.cast(lib.g16_wtns_values(h), C.POINTER(C.c_uint8)), shape=(n * 32,)).reshape(n, 32)
+        vals.flags.writeable = False   # the mapping is read-only
+    else:
+        vals = np.zeros((0, 32), dtype=np.uint8)
+    return Witness(lib, handle, n, vals)
+
+
+def _canonical_bytes(values) -> np.ndarray:
+    """(n, 32) uint8 canonical little-endian values from such an array, raw bytes or a sequence of ints"""
+    if isinstance(values, np.ndarray):
+        if values.dtype != np.uint8 or values.size % 32:
+            raise G16Error(B.G16_ERR_INVALID, "canonical values: a uint8 array of 32 bytes per value")
+        return np.ascontiguousarray(values).reshape(-1, 32)
+    if isinstance(values, (bytes, bytearray, memoryview)):
+        if len(values) % 32:
+            raise G16Error(B.G16_ERR_INVALID, "canonical values: 32 bytes per value")
+        return np.frombuffer(bytes(values), dtype=np.uint8).reshape(-1, 32)
+    try:
+        raw = b"".join(int(v).to_bytes(32, "little") for v in values)
+    except OverflowError:
+        raise G16Error(B.G16_ERR_INVALID, "canonical values: an integer outside [0, 2^256)") from None
+    return np.frombuffer(raw, dtype=np.uint8).reshape(-1, 32)
+
+
+def write_wtns(path, values):
+    """snarkjs .wtns, format version 2, sections 1 (n8 = 32, the bn128 prime, the count) and 2 (the values): values =
+    ints, or canonical little-endian bytes as a (n, 32) uint8 array.  Nothing is reduced or range-tested."""
+    v = _canonical_bytes(values)
+    with open(path, "wb") as f:
+        f.write(b"wtns" + (2).to_bytes(4, "little") + (2).to_bytes(4, "little"))
+        f.write((1).to_bytes(4, "little") + (40).to_bytes(8, "little"))
+        f.write((32).to_bytes(4, "little") + FR_MODULUS.to_bytes(32, "little") + v.shape[0].to_bytes(4, "little"))
+        f.write((2).to_bytes(4, "little") + (v.shape[0] * 32).to_bytes(8, "little"))
+        f.write(v.tobytes())
+
+
+def fr_from_canonical(data, device=0, lib: Optional[B.Library] = None) -> np.ndarray:
+    """canonical little-endian values ((n, 32) uint8 array, bytes, or ints) -> (n, 4) uint64 Montgomery limbs, converted
+    on the GPU (g16_fr_convert): the bulk form of fr_from_ints.  A value >= r raises G16Error (status
+    G16_ERR_INVALID) whose first_bad is the index of the first such value."""
+    lib = lib or B.load()
+    src = _canonical_bytes(data)
+    out = np.empty((src.shape[0], 4), dtype=np.uint64)
+    bad = C.c_int64(-1)
+    st = lib.g16_fr_convert(device, _np_ptr(src), _np_ptr(out), src.shape[0], C.byref(bad))
+    _check_canonical(lib, st, None, bad)
+    return out
+
+
+FR_CONVERT_PHASES = ("upload", "convert", "download")
+
+
+def fr_from_canonical_times(lib: Optional[B.Library] = None) -> dict:
+    """device milliseconds of this thread's last fr_from_canonical, by phase (g16_fr_convert_times)"""
+    lib = lib or B.load()
+    ms = (C.c_float * len(FR_CONVERT_PHASES))()
+    lib.check(lib.g16_fr_convert_times(ms, len(FR_CONVERT_PHASES)))
+    return dict(zip(FR_CONVERT_PHASES, [float(x) for x in ms]))
+
+
+def _check_canonical(lib, st, ctx, bad):
+    try:
+        lib.check(st, ctx)
+    except G16Error as e:
+        e.first_bad = int(bad.value)
+        raise
+
+
 class CircomCircuit:
     """CircomCircuit{r1cs, witness} (reference src/circom/circuit.rs:12-26).  The witness comes from
     outside (circom's WASM generator is out of scope): ints or Montgomery limbs."""
@@ -407,6 +522,27 @@ class Proof:
     def from_ark(raw, compressed=True, validate=True, device=0, lib: Optional[B.Library] = None) -> "Proof":
         """Proof::deserialize_compressed / _uncompressed of one proof (g16_ark_proofs_read)."""
         return proofs_from_ark(raw, 1, compressed=compressed, validate=validate, device=device, lib=lib)[0]
+
+    def to_json(self, device=0, lib: Optional[B.Library] = None) -> dict:
+        """snarkjs proof.json as a dict (snarkjs.proof_to_json; write_proof_json writes the file)"""
+        from . import snarkjs
+        return snarkjs.proof_to_json(self, device, lib)
+
+    @staticmethod
+    def from_json(src, device=0, lib: Optional[B.Library] = None) -> "Proof":
+        """a proof.json (dict, JSON text or path); every point goes through the codec's validation"""
+        from . import snarkjs
+        return snarkjs.proof_from_json(src, device, lib)
+
+    def to_eth(self, device=0, lib: Optional[B.Library] = None):
+        """ethereum::Proof::as_tuple (reference src/ethereum.rs:104-118): (a, b, c) as ints, G2 with c1 first"""
+        from . import snarkjs
+        return snarkjs.proof_to_eth(self, device, lib)
+
+    @staticmethod
+    def from_eth(t, device=0, lib: Optional[B.Library] = None) -> "Proof":
+        from . import snarkjs
+        return snarkjs.proof_from_eth(t, device, lib)
 
     def rerandomize(self, vk, r1=None, r2=None, device=0, lib: Optional[B.Library] = None) -> "Proof":
         """Groth16::rerandomize_proof of this proof (rerandomize): r1 in [1, r) and r2 in [0, r) as ints, or both
@@ -654,6 +790,63 @@ class Prover:
         pass to prove_dev()"""
         w = _as_fr(full_assignment, self.lib)
         self.lib.check(self.lib.g16_witness_upload(self.ctx, _np_ptr(w), w.shape[0]), self.ctx)
+        return self.witness_buffer()
+
+    # -- canonical witnesses: a .wtns goes to the device as it lies in the file (g16_*_canonical)
+    def _canonical_witness(self, wtns):
+        """((n_vars, 32) uint8 canonical values, keepalive) of a path, bytes, a Witness or such an array"""
+        if isinstance(wtns, np.ndarray):
+            return _canonical_bytes(wtns), None
+        w = wtns if isinstance(wtns, Witness) else open_wtns(wtns, self.lib)
+        return w.canonical, w
+
+    @staticmethod
+    def _draw_rs(r, s):
+        rng = random.SystemRandom()   # as Groth16.prove draws them
+        return (rng.randrange(FR_MODULUS) if r is None else r), (rng.randrange(FR_MODULUS) if s is None else s)
+
+    def prove_wtns(self, wtns, r=None, s=None) -> Proof:
+        """prove(r, s, read_wtns(wtns)) byte for byte, without the host conversion (g16_prove_canonical): wtns = path,
+        bytes, Witness or a (n_vars, 32) uint8 array of canonical values.  r, s: ints or Montgomery limbs; None =
+        drawn as Groth16.prove draws them.  A value >= r raises G16Error naming the element."""
+        w, _keep = self._canonical_witness(wtns)
+        r, s = self._draw_rs(r, s)
+        rs = _as_fr([r, s], self.lib) if not isinstance(r, np.ndarray) else np.stack([r, s])
+        out = np.empty(B.G16_PROOF_BYTES, dtype=np.uint8)
+        self.lib.check(self.lib.g16_prove_canonical(self.ctx, _np_ptr(rs[0:1]), _np_ptr(rs[1:2]), _np_ptr(w),
+                                                    w.shape[0], _np_ptr(out)), self.ctx)
+        return Proof(out.tobytes())
+
+    def prove_wtns_batch(self, wtns_list, rs=None) -> List[Proof]:
+        """prove_batch for canonical witnesses (g16_prove_batch_canonical): one conversion launch per chunk ahead of
+        the batched prover.  rs: sequence of (r, s), None = drawn.  A value >= r raises G16Error naming the proof and
+        the element, with first_bad = proof * n_vars + element; no proof is returned."""
+        ws = [self._canonical_witness(x) for x in wtns_list]
+        count = len(ws)
+        if rs is None:
+            rs = [self._draw_rs(None, None) for _ in range(count)]
+        r, s = self._batch_rs(rs)
+        if r.shape[0] != count:
+            raise G16Error(B.G16_ERR_INVALID, f"{r.shape[0]} (r, s) pairs for {count} witnesses")
+        if count == 0:
+            return []
+        if any(w.shape[0] != self.n_vars for w, _ in ws):
+            raise G16Error(B.G16_ERR_INVALID, "witness length != n_vars of the key")
+        w = np.ascontiguousarray(np.stack([x for x, _ in ws]))
+        out = np.empty(count * B.G16_PROOF_BYTES, dtype=np.uint8)
+        bad = C.c_int64(-1)
+        st = self.lib.g16_prove_batch_canonical(self.ctx, count, _np_ptr(r), _np_ptr(s), _np_ptr(w), self.n_vars,
+                                                _np_ptr(out), C.byref(bad))
+        _check_canonical(self.lib, st, self.ctx, bad)
+        raw = out.tobytes()
+        return [Proof(raw[i * B.G16_PROOF_BYTES:(i + 1) * B.G16_PROOF_BYTES]) for i in range(count)]
+
+    def upload_witness_canonical(self, wtns) -> int:
+        """upload_witness for canonical values (g16_witness_upload_canonical); returns the pointer for prove_dev()"""
+        w, _keep = self._canonical_witness(wtns)
+        bad = C.c_int64(-1)
+        st = self.lib.g16_witness_upload_canonical(self.ctx, _np_ptr(w), w.shape[0], C.byref(bad))
+        _check_canonical(self.lib, st, self.ctx, bad)
         return self.witness_buffer()
 
     def witness_host_buffer(self) -> np.ndarray:
@@ -2135,3 +2328,7 @@ class Groth16:
         w = circuit.full_assignment()
         return Groth16.create_proof_with_reduction_and_matrices(
             pk, r, s, matrices, matrices.num_instance_variables, matrices.num_constraints, w, **kw)
+
+
+from .snarkjs import (read_proof_json, write_proof_json, read_public_json, write_public_json, read_vk_json,  # noqa: E402
+                      write_vk_json, inputs_to_eth, solidity_calldata)

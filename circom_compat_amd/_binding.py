@@ -193,6 +193,8 @@ ABI_SYMBOLS = [
     "g16_proofs_rerandomize", "g16_proofs_rerandomize_keys", "g16_proofs_rerandomize_times",
     "g16_pvk_create", "g16_pvk_destroy", "g16_pvk_alpha_beta", "g16_verify_prepared", "g16_pairing_check",
     "g16_verify_prepared_times",
+    "g16_fr_convert", "g16_fr_convert_times", "g16_witness_upload_canonical", "g16_prove_canonical", "g16_prove_batch_canonical",
+    "g16_wtns_open", "g16_wtns_open_mem", "g16_wtns_count", "g16_wtns_values", "g16_wtns_close",
 ]
 
 
@@ -355,6 +357,17 @@ class Library:
             "g16_verify_prepared": (C.c_int, [vp, vp, vp, C.c_uint32, vp]),
             "g16_pairing_check": (C.c_int, [C.c_int, vp, vp, C.c_uint32, vp]),
             "g16_verify_prepared_times": (C.c_int, [C.POINTER(C.c_float), C.c_uint32]),
+            "g16_fr_convert": (C.c_int, [C.c_int, vp, vp, C.c_size_t, C.POINTER(C.c_int64)]),
+            "g16_fr_convert_times": (C.c_int, [C.POINTER(C.c_float), C.c_uint32]),
+            "g16_witness_upload_canonical": (C.c_int, [vp, vp, C.c_size_t, C.POINTER(C.c_int64)]),
+            "g16_prove_canonical": (C.c_int, [vp, vp, vp, vp, C.c_size_t, vp]),
+            "g16_prove_batch_canonical": (C.c_int, [vp, C.c_size_t, vp, vp, vp, C.c_size_t, vp,
+                                                    C.POINTER(C.c_int64)]),
+            "g16_wtns_open": (C.c_int, [C.c_char_p, C.POINTER(vp)]),
+            "g16_wtns_open_mem": (C.c_int, [vp, C.c_size_t, C.POINTER(vp)]),
+            "g16_wtns_count": (C.c_uint32, [vp]),
+            "g16_wtns_values": (vp, [vp]),
+            "g16_wtns_close": (None, [vp]),
         }
         # measurement builds only (make EXTRA=-DG16_DEBUG_ABI; include/g16_amd.h): not an ABI symbol, never "missing"
         optional = {"g16_debug_alu_bench": (C.c_int, [C.c_int, C.c_int, C.c_uint32, C.c_uint32,

@@ -468,6 +468,19 @@ namespace g16 {
 
 void rank_collect_times(g16_ctx* c) { collect_times(c); }
 
+void ingest_reserve(g16_ctx* c) {
+  if (!c->ingest_bad.p) c->ingest_bad.alloc(1);
+  if (!c->pin_bad) G16_HIP(hipHostMalloc((void**)&c->pin_bad, 8, 0));
+}
+
+void ingest_enqueue(g16_ctx* c, const uint8_t* w_le, Fr* dst, size_t n) {
+  hipStream_t s = c->stream;
+  G16_HIP(hipMemsetAsync(c->ingest_bad.p, 0xff, 8, s));  // INGEST_NONE
+  G16_HIP(hipMemcpyAsync(dst, w_le, n * 32, hipMemcpyHostToDevice, s));
+  fr_from_canonical_enqueue(dst, dst, n, c->ingest_bad.p, s);
+  G16_HIP(hipMemcpyAsync(c->pin_bad, c->ingest_bad.p, 8, hipMemcpyDeviceToHost, s));
+}
+
 // The buffers of a chunk of table-path proofs: the ctx's own for g16_prove (count = 1), the batch workspace's
 // (g16_ctx::BatchWs) for g16_prove_batch.  Proof z: witness w + z w_stride, (r, s) rs[2 z] (uploaded from
 // rs_host + 64 z), its XYZZ record at proj + z FIN_PROJ_BYTES (copied to proj_host).
@@ -1119,6 +1132,7 @@ void g16_ctx_destroy(g16_ctx* c) {
   if (c->ev_user) (void)hipEventDestroy(c->ev_user);
   if (c->pinned_w) (void)hipHostFree(c->pinned_w);
   if (c->pin_io) (void)hipHostFree(c->pin_io);
+  if (c->pin_bad) (void)hipHostFree(c->pin_bad);
   batch_release(c);
   delete c;
 }
@@ -1605,9 +1619,17 @@ static void batch_reserve_common(g16_ctx* c, uint32_t B) {
   b.cap = B;
 }
 
-// count proofs; w: host (count x N x 4 u64) or device (w_on_device: count x N x 32 bytes) witnesses
+// a canonical witness value >= r: element `bad` of the call's witnesses (proof bad / N, element bad % N)
+static g16_status ingest_fail(g16_ctx* c, unsigned long long bad) {
+  return fail(c, G16_ERR_INVALID, "proof " + std::to_string(bad / c->N) + ", witness element " + std::to_string(bad % c->N) +
+                                      " is >= the field modulus");
+}
+
+// count proofs; w: host (count x N x 4 u64) or device (w_on_device: count x N x 32 bytes) witnesses.  bad != NULL:
+// w holds canonical bytes on the host (g16_prove_batch_canonical): every upload becomes ingest_enqueue, and a
+// value >= r ends the call with its index in *bad.
 static g16_status prove_batch(g16_ctx* c, size_t count, const uint64_t* r, const uint64_t* s_, const void* w,
-                              bool w_on_device, size_t n_vars, uint8_t* proofs_out) {
+                              bool w_on_device, size_t n_vars, uint8_t* proofs_out, unsigned long long* bad = nullptr) {
   if (!c) return fail(c, G16_ERR_INVALID, "null argument");
   if (count == 0) return G16_OK;
   if (!r || !s_ || !w || !proofs_out) return fail(c, G16_ERR_INVALID, "null argument");
@@ -1626,13 +1648,17 @@ static g16_status prove_batch(g16_ctx* c, size_t count, const uint64_t* r, const
   if (c->dist_wm) return fail(c, G16_ERR_INVALID, "dist_wm ctx: use the g16_prove_dist_phase* calls");
   return guarded(c, [&]() -> g16_status {
     hipStream_t s = c->stream;
+    if (bad) ingest_reserve(c);
     // (one bucket-path proof: the single-proof enqueue, without asking the runtime for its free memory)
     const uint32_t B = (!c->tbl.active && count == 1) ? 1u : batch_chunk(c, count, /*prove=*/true);
     if (!c->tbl.active && B == 1) {
       // chunks of one (a large key, little free memory, a single proof): the single-proof enqueue once per proof
       for (size_t i = 0; i < count; ++i) {
         const Fr* wi = (const Fr*)((const uint8_t*)w + i * wb);
-        if (!w_on_device) {
+        if (bad) {
+          ingest_enqueue(c, (const uint8_t*)wi, c->w_dev.p, c->N);
+          wi = c->w_dev.p;
+        } else if (!w_on_device) {
           G16_HIP(hipMemcpyAsync(c->w_dev.p, wi, wb, hipMemcpyHostToDevice, s));
           wi = c->w_dev.p;
         }
@@ -1640,6 +1666,10 @@ static g16_status prove_batch(g16_ctx* c, size_t count, const uint64_t* r, const
         memcpy(c->pin_io + 32, s_ + 4 * i, 32);
         enqueue_prove(c, wi);
         G16_HIP(hipStreamSynchronize(s));
+        if (bad && *c->pin_bad != INGEST_NONE) {
+          collect_times(c);
+          return ingest_fail(c, *bad = i * c->N + *c->pin_bad);
+        }
         proof_from_pin(c, proofs_out + i * G16_PROOF_BYTES);
       }
       collect_times(c);
@@ -1656,10 +1686,19 @@ static g16_status prove_batch(g16_ctx* c, size_t count, const uint64_t* r, const
         memcpy(rs_host + 64 * (size_t)z + 32, s_ + 4 * (done + z), 32);
       }
       const Fr* wz = (const Fr*)((const uint8_t*)w + done * wb);
-      if (!w_on_device) {
+      if (bad) {  // one conversion launch over the chunk, ahead of the witnesses' first consumer
+        ingest_enqueue(c, (const uint8_t*)wz, bw.w.p, (size_t)n * c->N);
+        wz = bw.w.p;
+      } else if (!w_on_device) {
         G16_HIP(hipMemcpyAsync(bw.w.p, wz, (size_t)n * wb, hipMemcpyHostToDevice, s));
         wz = bw.w.p;
       }
+      auto chunk_bad = [&]() -> bool {  // (after the chunk's synchronisation)
+        if (!bad || *c->pin_bad == INGEST_NONE) return false;
+        *bad = done * c->N + *c->pin_bad;
+        collect_times(c);
+        return true;
+      };
       if (!c->tbl.active) {
         auto& k = *bw.bk;
         const BucketChunk ch{n,          wz,          c->N,       bw.abc.p,  bw.spmv.p, bw.h.p,   bw.sums.p,
@@ -1668,6 +1707,7 @@ static g16_status prove_batch(g16_ctx* c, size_t count, const uint64_t* r, const
                              proj_host,  proj_host};
         enqueue_prove_buckets(c, ch);
         G16_HIP(hipStreamSynchronize(s));
+        if (chunk_bad()) return ingest_fail(c, *bad);
         fin_host_affine_c_batch(proj_host, n, proofs_out + done * G16_PROOF_BYTES);
         continue;
       }
@@ -1675,6 +1715,7 @@ static g16_status prove_batch(g16_ctx* c, size_t count, const uint64_t* r, const
                         bw.sums.p, bw.scr.p,  bw.part1.p, bw.partH.p, bw.part2.p, bw.proj.p, proj_host};
       enqueue_prove_tables(c, ch);
       G16_HIP(hipStreamSynchronize(s));
+      if (chunk_bad()) return ingest_fail(c, *bad);
       fin_tab_host_affine_batch(proj_host, n, proofs_out + done * G16_PROOF_BYTES);
     }
     collect_times(c);
@@ -1726,6 +1767,84 @@ g16_status g16_witness_upload(g16_ctx* c, const uint64_t* w, size_t n_vars) {
     G16_HIP(hipStreamSynchronize(c->stream));
     return G16_OK;
   });
+}
+
+// ---- canonical witnesses: the same calls for the 32-byte little-endian integers of a .wtns -----------
+g16_status g16_witness_upload_canonical(g16_ctx* c, const uint8_t* w_le, size_t n_vars, int64_t* first_bad) {
+  if (first_bad) *first_bad = -1;
+  if (!c || !w_le) return fail(c, G16_ERR_INVALID, "null argument");
+  if (check_w(c, n_vars) != G16_OK) return G16_ERR_INVALID;
+  unsigned long long bad = INGEST_NONE;
+  g16_status st;
+  if (c->multi) {
+    st = multi_witness_upload_canonical(c, w_le, &bad);
+  } else {
+    st = guarded(c, [&]() -> g16_status {
+      ingest_reserve(c);
+      ingest_enqueue(c, w_le, c->w_dev.p, c->N);
+      G16_HIP(hipStreamSynchronize(c->stream));
+      bad = *c->pin_bad;
+      return G16_OK;
+    });
+  }
+  if (bad == INGEST_NONE) return st;
+  if (first_bad) *first_bad = (int64_t)bad;
+  return ingest_fail(c, bad);
+}
+
+g16_status g16_prove_canonical(g16_ctx* c, const uint64_t r[4], const uint64_t s_[4], const uint8_t* w_le,
+                               size_t n_vars, uint8_t proof_out[G16_PROOF_BYTES]) {
+  if (!c || !r || !s_ || !w_le || !proof_out) return fail(c, G16_ERR_INVALID, "null argument");
+  if (check_w(c, n_vars) != G16_OK) return G16_ERR_INVALID;
+  if (c->multi) {  // converted on the first device, then the resident-witness path
+    const g16_status st = g16_witness_upload_canonical(c, w_le, n_vars, nullptr);
+    if (st != G16_OK) return st;
+    return multi_prove(c, r, s_, multi_child(c, 0)->w_dev.p, /*w_on_device=*/true, proof_out);
+  }
+  if (!c->has_key) return fail(c, G16_ERR_INVALID, "witness-map-only ctx has no resident key");
+  if (c->world != 1) return fail(c, G16_ERR_INVALID, "g16_prove needs world == 1; use partial/finish");
+  if (c->dist_wm) return fail(c, G16_ERR_INVALID, "dist_wm ctx: use the g16_prove_dist_phase* calls");
+  return guarded(c, [&]() -> g16_status {
+    hipStream_t s = c->stream;
+    ingest_reserve(c);
+    ingest_enqueue(c, w_le, c->w_dev.p, c->N);  // a value >= r is proved as 0 and reported below: no host wait here
+    memcpy(c->pin_io, r, 32);
+    memcpy(c->pin_io + 32, s_, 32);
+    enqueue_prove(c, c->w_dev.p);
+    G16_HIP(hipStreamSynchronize(s));
+    collect_times(c);
+    if (*c->pin_bad != INGEST_NONE) return ingest_fail(c, *c->pin_bad);
+    proof_from_pin(c, proof_out);
+    return G16_OK;
+  });
+}
+
+g16_status g16_prove_batch_canonical(g16_ctx* c, size_t count, const uint64_t* r, const uint64_t* s_,
+                                     const uint8_t* w_le, size_t n_vars, uint8_t* proofs_out, int64_t* first_bad) {
+  if (first_bad) *first_bad = -1;
+  if (!c) return fail(c, G16_ERR_INVALID, "null argument");
+  if (count == 0) return G16_OK;
+  if (!r || !s_ || !w_le || !proofs_out) return fail(c, G16_ERR_INVALID, "null argument");
+  if (check_w(c, n_vars) != G16_OK) return G16_ERR_INVALID;
+  // no proof is written unless every witness of the call is in range: the proofs are collected here first
+  std::vector<uint8_t> proofs(count * G16_PROOF_BYTES);
+  unsigned long long bad = INGEST_NONE;
+  g16_status st = G16_OK;
+  if (c->multi) {  // one sharded proof after the other, as g16_prove_batch
+    for (size_t i = 0; i < count && st == G16_OK; ++i) {
+      unsigned long long b1 = INGEST_NONE;
+      st = multi_witness_upload_canonical(c, w_le + i * (size_t)c->N * 32, &b1);
+      if (b1 != INGEST_NONE) st = ingest_fail(c, bad = i * c->N + b1);
+      if (st == G16_OK)
+        st = multi_prove(c, r + 4 * i, s_ + 4 * i, multi_child(c, 0)->w_dev.p, /*w_on_device=*/true,
+                         proofs.data() + i * G16_PROOF_BYTES);
+    }
+  } else {
+    st = prove_batch(c, count, r, s_, w_le, /*w_on_device=*/false, n_vars, proofs.data(), &bad);
+  }
+  if (bad != INGEST_NONE && first_bad) *first_bad = (int64_t)bad;
+  if (st == G16_OK) memcpy(proofs_out, proofs.data(), proofs.size());
+  return st;
 }
 
 void* g16_witness_host_buffer(g16_ctx* c) {

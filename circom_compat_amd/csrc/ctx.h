@@ -12,6 +12,7 @@
 #include "msm.h"
 #include "witness_map.h"
 #include "wm_dist.h"
+#include "wtns_ingest.h"
 
 namespace g16 {
 struct Multi;  // multi.hip
@@ -90,6 +91,10 @@ struct g16_ctx {
   g16::DevBuf<uint8_t> out_dev;  // proof (256) | this rank's partial (1024) | gathered partials
   void* pinned_w = nullptr;      // g16_witness_host_buffer: page-locked staging for the witness
   uint8_t* pin_io = nullptr;     // page-locked (r, s) [64 B] | proof [256 B] of g16_prove_dev
+  // canonical witnesses (g16_*_canonical): the first-bad-element word of k_fr_from_canonical and the page-locked
+  // word it is copied back to; both allocated at the first such call
+  g16::DevBuf<unsigned long long> ingest_bad;
+  unsigned long long* pin_bad = nullptr;
 
   // g16_prove_batch / g16_witness_map_batch: per-proof copies of everything a proof writes, for up to `cap`
   // proofs in one pass (allocated at the first batch call, grown when a larger chunk is needed)
@@ -151,6 +156,11 @@ void rank_partial_enqueue(g16_ctx* c, const uint64_t r[4], const uint64_t s[4], 
 // gathered: world x G16_PARTIAL_BYTES already in c->gathered_dev() (ordered on the main stream)
 void rank_finish_enqueue(g16_ctx* c, const uint64_t r[4], const uint64_t s[4], int world);
 void rank_collect_times(g16_ctx* c);
+// canonical witness ingestion on c's main stream (api.hip; the kernel: wtns_ingest.hip).  ingest_enqueue: n
+// canonical 32-byte values from the host into dst, converted in place there; the first element >= r (or
+// INGEST_NONE) is in *c->pin_bad once the stream has been synchronised.
+void ingest_reserve(g16_ctx* c);
+void ingest_enqueue(g16_ctx* c, const uint8_t* w_le, Fr* dst, size_t n);
 
 // ---- single-process multi-device prover (multi.hip) -------------------------------------------
 g16_status multi_create(const g16_key_desc* key, const g16_csr* a, const g16_csr* b,
@@ -164,6 +174,9 @@ g16_status multi_prove(g16_ctx* parent, const uint64_t r[4], const uint64_t s[4]
 // host witness -> every device's staging buffer; a later multi_prove(w = children[0]->w_dev.p, on
 // device) then moves nothing
 g16_status multi_witness_upload(g16_ctx* parent, const uint64_t* w);
+// the same for canonical bytes: uploaded to and converted on the first device, peer-copied to the others;
+// *bad = the first element >= r (INGEST_NONE: none; then G16_ERR_INVALID comes back and nothing is resident)
+g16_status multi_witness_upload_canonical(g16_ctx* parent, const uint8_t* w_le, unsigned long long* bad);
 g16_ctx* multi_child(g16_ctx* parent, int index);  // nullptr when out of range / not a parent
 int multi_size(const g16_ctx* parent);
 // create-time link probe of a multi-device parent: [src * G + dst] tables; returns G, -1 if not a parent

@@ -439,7 +439,8 @@ g16_status r1cs_parse(const uint8_t* d, size_t n, g16_r1cs* R) {
   return G16_OK;
 }
 
-g16_status wtns_parse(const uint8_t* d, size_t n, uint64_t** out, uint32_t* cnt) {
+// the container walk and header rules of a .wtns: where the nw canonical values of section 2 start
+g16_status wtns_locate(const uint8_t* d, size_t n, size_t* values_pos, uint32_t* cnt) {
   Cursor c(d, n);
   const uint8_t* magic = c.bytes(4);
   if (!magic || memcmp(magic, "wtns", 4) != 0) return fail(G16_ERR_IO, "wtns: bad magic");
@@ -462,7 +463,17 @@ g16_status wtns_parse(const uint8_t* d, size_t n, uint64_t** out, uint32_t* cnt)
   if (!prime || memcmp(prime, kR1csPrime, 32) != 0) return fail(G16_ERR_IO, "wtns: not bn128");
   const uint32_t nw = h.u32();
   if (!h.ok || sec[2].size < (uint64_t)nw * 32) return fail(G16_ERR_IO, "wtns: truncated values");
-  Cursor v(d, n, sec[2].pos);
+  *values_pos = sec[2].pos;
+  *cnt = nw;
+  return G16_OK;
+}
+
+g16_status wtns_parse(const uint8_t* d, size_t n, uint64_t** out, uint32_t* cnt) {
+  size_t pos = 0;
+  uint32_t nw = 0;
+  const g16_status st = wtns_locate(d, n, &pos, &nw);
+  if (st != G16_OK) return st;
+  Cursor v(d, n, pos);
   uint64_t* buf = (uint64_t*)malloc((size_t)(nw ? nw : 1) * 32);
   if (!buf) return fail(G16_ERR_INTERNAL, "out of memory");
   for (uint32_t i = 0; i < nw; ++i) {
@@ -819,6 +830,50 @@ g16_status g16_wtns_read(const char* path, uint64_t** out, uint32_t* n) {
   if (!read_file(path, buf, err)) return fail(G16_ERR_IO, err);
   return wtns_parse(buf.data(), buf.size(), out, n);
 }
+
+// .wtns as it lies in the file: the header is checked, the values are handed out where they are (the device
+// converts and range-tests them: g16_prove_canonical)
+struct g16_wtns {
+  FileView data;
+  size_t pos = 0;
+  uint32_t n = 0;
+};
+
+static g16_status wtns_open_view(g16_wtns* w, g16_wtns** out) {
+  const g16_status st = wtns_locate(w->data.data(), w->data.size(), &w->pos, &w->n);
+  if (st != G16_OK) {
+    delete w;
+    return st;
+  }
+  *out = w;
+  return G16_OK;
+}
+
+g16_status g16_wtns_open(const char* path, g16_wtns** out) {
+  if (!path || !out) return fail(G16_ERR_INVALID, "null argument");
+  *out = nullptr;
+  g16_wtns* w = new g16_wtns();
+  std::string err;
+  if (!w->data.map_file(path, err)) {
+    delete w;
+    return fail(G16_ERR_IO, err);
+  }
+  return wtns_open_view(w, out);
+}
+
+g16_status g16_wtns_open_mem(const uint8_t* data, size_t len, g16_wtns** out) {
+  if (!data || !out) return fail(G16_ERR_INVALID, "null argument");
+  *out = nullptr;
+  g16_wtns* w = new g16_wtns();
+  w->data.copy_of(data, len);
+  return wtns_open_view(w, out);
+}
+
+uint32_t g16_wtns_count(const g16_wtns* w) { return w ? w->n : 0; }
+
+const uint8_t* g16_wtns_values(const g16_wtns* w) { return w ? w->data.data() + w->pos : nullptr; }
+
+void g16_wtns_close(g16_wtns* w) { delete w; }
 
 void g16_free(void* p) { free(p); }
 

@@ -462,6 +462,38 @@ g16_status multi_witness_upload(g16_ctx* parent, const uint64_t* w) {
   return code;
 }
 
+g16_status multi_witness_upload_canonical(g16_ctx* parent, const uint8_t* w_le, unsigned long long* bad) {
+  Multi& M = *parent->multi;
+  const size_t wbytes = (size_t)parent->N * 32;
+  M.witness_resident = false;
+  *bad = INGEST_NONE;
+  g16_ctx* c0 = M.ch[0];
+  std::vector<std::function<void(int)>> st;
+  st.push_back([&](int g) {  // the first device converts
+    if (g != 0) return;
+    G16_HIP(hipSetDevice(c0->device));
+    ingest_reserve(c0);
+    ingest_enqueue(c0, w_le, c0->w_dev.p, parent->N);
+    G16_HIP(hipStreamSynchronize(c0->stream));
+    *bad = *c0->pin_bad;
+  });
+  st.push_back([&](int g) {  // the broadcast multi_prove gives a device-resident witness
+    if (g == 0 || *bad != INGEST_NONE) return;
+    g16_ctx* c = M.ch[g];
+    G16_HIP(hipSetDevice(c->device));
+    G16_HIP(hipMemcpyPeerAsync(c->w_dev.p, c->device, c0->w_dev.p, c0->device, wbytes, c->stream));
+    G16_HIP(hipStreamSynchronize(c->stream));
+  });
+  const int code = M.pool.run(st);
+  if (code != G16_OK) {
+    parent->err = M.pool.first_error;
+    return (g16_status)code;
+  }
+  if (*bad != INGEST_NONE) return G16_ERR_INVALID;  // (the caller words the message)
+  M.witness_resident = true;
+  return G16_OK;
+}
+
 g16_ctx* multi_child(g16_ctx* parent, int index) {
   if (!parent || !parent->multi || index < 0 || index >= parent->multi->G) return nullptr;
   return parent->multi->ch[index];

@@ -1,0 +1,125 @@
+// wtns_ingest.hip -- canonical witness ingestion: the 32-byte little-endian integers of a snarkjs .wtns
+// (rapidsnark, circom's C++ calculator) become the 4 x u64 Montgomery form of the ctx's witness buffer on the
+// device, range test included.  32 bytes in, 32 bytes out, one Montgomery product per element: the host loop
+// this replaces (loaders.cpp, wtns_parse) does the same product one element after the other.
+#include "wtns_ingest.h"
+
+#include "../../include/g16_amd.h"
+
+namespace g16 {
+void set_create_error(const std::string& msg);  // api.hip: what g16_last_error(NULL) returns
+
+namespace {
+
+constexpr int INGEST_BLOCK = 256;
+
+// g16_fr_convert_times: device milliseconds of the calling thread's last g16_fr_convert
+enum { T_UPLOAD = 0, T_CONVERT, T_DOWNLOAD, T_COUNT };
+thread_local float t_phase_ms[T_COUNT] = {0.f, 0.f, 0.f};
+
+struct Events {  // the four marks around the three phases, on the null stream
+  hipEvent_t e[T_COUNT + 1] = {};
+  Events() {
+    for (auto& x : e) G16_HIP(hipEventCreate(&x));
+  }
+  ~Events() {
+    for (auto x : e)
+      if (x) (void)hipEventDestroy(x);
+  }
+  void mark(int i) { G16_HIP(hipEventRecord(e[i], nullptr)); }
+  void collect() {
+    G16_HIP(hipEventSynchronize(e[T_COUNT]));
+    for (int i = 0; i < T_COUNT; ++i)
+      if (hipEventElapsedTime(&t_phase_ms[i], e[i], e[i + 1]) != hipSuccess) t_phase_ms[i] = 0.f;
+  }
+};
+
+// One lane per element, consecutive lanes read consecutive elements (U256 is 16-byte aligned: two 128-bit
+// loads, two 128-bit stores).  No LDS.  in and out may be the same buffer.
+__global__ void __launch_bounds__(INGEST_BLOCK) k_fr_from_canonical(const U256* in, Fr* out, uint64_t n,
+                                                                   unsigned long long* first_bad) {
+  const uint64_t i = (uint64_t)blockIdx.x * INGEST_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const U256 u = in[i];
+  // v < r  <=>  v - r borrows
+  uint64_t br = 0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) br = (((uint64_t)u.v[j] - FrParams::MOD[j] - br) >> 32) & 1;
+  Fr m = Fr::from_canonical(u);
+  if (!br) {  // nothing unreduced leaves this kernel; the smallest failing index wins whatever the schedule
+    m = Fr::zero();
+    atomicMin(first_bad, (unsigned long long)i);
+  }
+  out[i] = m;
+}
+
+}  // namespace
+
+void fr_from_canonical_enqueue(const void* in_le, Fr* out, size_t n, unsigned long long* first_bad, hipStream_t s) {
+  if (!n) return;
+  G16_LAUNCH(k_fr_from_canonical, ceil_div(n, INGEST_BLOCK), INGEST_BLOCK, 0, s, (const U256*)in_le, out,
+             (uint64_t)n, first_bad);
+  G16_HIP(hipGetLastError());
+}
+
+}  // namespace g16
+
+using namespace g16;
+
+extern "C" g16_status g16_fr_convert(int device, const uint8_t* in_le, uint64_t* out_mont, size_t n,
+                                     int64_t* first_bad) {
+  if (first_bad) *first_bad = -1;
+  if (n == 0) return G16_OK;
+  if (!in_le || !out_mont) {
+    set_create_error("g16_fr_convert: null argument");
+    return G16_ERR_INVALID;
+  }
+  if (n >= ((size_t)1 << 31) * INGEST_BLOCK) {  // one launch: the grid holds fewer than 2^31 blocks
+    set_create_error("g16_fr_convert: 2^39 elements or more");
+    return G16_ERR_INVALID;
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return G16_ERR_NO_DEVICE;
+  if (device < 0 || device >= ndev) {
+    set_create_error("g16_fr_convert: device out of range");
+    return G16_ERR_INVALID;
+  }
+  try {
+    G16_HIP(hipSetDevice(device));
+    DevBuf<Fr> buf;
+    DevBuf<unsigned long long> bad;
+    buf.alloc(n);
+    bad.alloc(1);
+    unsigned long long bad_host = INGEST_NONE;
+    Events ev;
+    for (float& t : t_phase_ms) t = 0.f;
+    ev.mark(T_UPLOAD);
+    G16_HIP(hipMemcpy(buf.p, in_le, n * 32, hipMemcpyHostToDevice));
+    G16_HIP(hipMemcpy(bad.p, &bad_host, 8, hipMemcpyHostToDevice));
+    ev.mark(T_CONVERT);
+    fr_from_canonical_enqueue(buf.p, buf.p, n, bad.p, nullptr);
+    ev.mark(T_DOWNLOAD);
+    G16_HIP(hipMemcpy(&bad_host, bad.p, 8, hipMemcpyDeviceToHost));
+    if (bad_host == INGEST_NONE) G16_HIP(hipMemcpy(out_mont, buf.p, n * 32, hipMemcpyDeviceToHost));
+    ev.mark(T_COUNT);
+    ev.collect();
+    if (bad_host != INGEST_NONE) {
+      if (first_bad) *first_bad = (int64_t)bad_host;
+      set_create_error("g16_fr_convert: element " + std::to_string(bad_host) + " is >= the field modulus");
+      return G16_ERR_INVALID;
+    }
+    return G16_OK;
+  } catch (const HipError& e) {
+    set_create_error(e.what());
+    return G16_ERR_HIP;
+  } catch (const std::exception& e) {
+    set_create_error(e.what());
+    return G16_ERR_INTERNAL;
+  }
+}
+
+extern "C" g16_status g16_fr_convert_times(float* ms, uint32_t cap) {
+  if (!ms) return G16_ERR_INVALID;
+  for (uint32_t i = 0; i < cap; ++i) ms[i] = i < (uint32_t)T_COUNT ? t_phase_ms[i] : 0.f;
+  return G16_OK;
+}

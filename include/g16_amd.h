@@ -298,6 +298,30 @@ void* g16_witness_buffer(g16_ctx* ctx);
  * (the multi-device ctx otherwise peer-broadcasts a device-resident witness from the first device
  * inside every call).                                                                             */
 g16_status g16_witness_upload(g16_ctx* ctx, const uint64_t* w, size_t n_vars);
+/* ---- canonical witnesses ----------------------------------------------------------------------------
+ * The witness as snarkjs, rapidsnark and circom's C++ calculator write it (.wtns section 2; g16_wtns_values in
+ * g16_loaders.h): n_vars x 32 bytes, each a little-endian integer below r.  The calls below take those bytes
+ * where their namesakes take Montgomery limbs: the bytes are copied into the same device staging buffer on the
+ * same stream and converted there in place by one kernel launch (one lane per element) ahead of the witness's
+ * first consumer, so the proof is byte for byte that of g16_prove on the converted witness.
+ * A value >= r: G16_ERR_INVALID, g16_last_error names the proof and the element, *first_bad (may be NULL) holds
+ * the index of the first such element -- proof * n_vars + element in the batch call -- and -1 otherwise, and no
+ * proof is written.  (The element itself reaches the device as 0, never unreduced.)
+ * g16_fr_convert: host in, host out through `device`, the bulk form of g16_fr_from_canonical (witness lists, the
+ * public inputs of large verification batches); n == 0: G16_OK; out_mont is written only when every value is
+ * in range; its message is in g16_last_error(NULL).
+ * g16_witness_upload_canonical: g16_witness_upload; a multi-device ctx converts on its first device and
+ * peer-copies the result to the others.  g16_prove_batch_canonical: the witnesses go into the batch workspace's
+ * witness staging, one conversion launch per chunk, then g16_prove_batch_dev's path.                           */
+g16_status g16_fr_convert(int device, const uint8_t* in_le, uint64_t* out_mont, size_t n, int64_t* first_bad);
+/* device milliseconds the calling thread's last g16_fr_convert spent in 0 upload, 1 the conversion kernel,
+ * 2 download (HIP events); entries from 3 on are 0                                                            */
+g16_status g16_fr_convert_times(float* ms, uint32_t cap);
+g16_status g16_witness_upload_canonical(g16_ctx* ctx, const uint8_t* w_le, size_t n_vars, int64_t* first_bad);
+g16_status g16_prove_canonical(g16_ctx* ctx, const uint64_t r[4], const uint64_t s[4], const uint8_t* w_le,
+                               size_t n_vars, uint8_t proof_out[G16_PROOF_BYTES]);
+g16_status g16_prove_batch_canonical(g16_ctx* ctx, size_t count, const uint64_t* r, const uint64_t* s,
+                                     const uint8_t* w_le, size_t n_vars, uint8_t* proofs_out, int64_t* first_bad);
 /* page-locked HOST staging buffer (n_vars x 32 bytes, owned by the ctx): a caller that writes the
  * full assignment here (instead of into a Vec) gets the H2D copy of g16_prove at PCIe line rate   */
 void* g16_witness_host_buffer(g16_ctx* ctx);

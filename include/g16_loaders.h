@@ -148,6 +148,20 @@ g16_status g16_wtns_read(const char* path, uint64_t** out, uint32_t* n);
 g16_status g16_wtns_read_mem(const uint8_t* data, size_t len, uint64_t** out, uint32_t* n);
 void g16_free(void* p);
 
+/* The same file left as it is: the header is checked by the rules and with the messages of g16_wtns_read (magic,
+ * 32-byte fields, the bn128 prime, a section 2 of at least n x 32 bytes), and the n canonical little-endian values
+ * are handed out where they lie -- no conversion, no copy and NO RANGE TEST here: g16_prove_canonical /
+ * g16_witness_upload_canonical / g16_fr_convert (g16_amd.h) convert them on the device and reject a value >= r
+ * there.  g16_wtns_open maps the file read-only under the rules of g16_zkey_open (it must stay unchanged until
+ * g16_wtns_close; G16_ZKEY_COPY=1 reads it into owned memory); g16_wtns_open_mem copies the caller's buffer.
+ * g16_wtns_values: n x 32 bytes owned by the handle; the pointer is only 4-byte aligned in the file.             */
+typedef struct g16_wtns g16_wtns;
+g16_status g16_wtns_open(const char* path, g16_wtns** out);
+g16_status g16_wtns_open_mem(const uint8_t* data, size_t len, g16_wtns** out);
+uint32_t g16_wtns_count(const g16_wtns* w);
+const uint8_t* g16_wtns_values(const g16_wtns* w);
+void g16_wtns_close(g16_wtns* w);
+
 /* canonical little-endian 32-byte integers <-> Montgomery Fr (host helpers for callers that hold
  * decimal / canonical witnesses, e.g. snarkjs JSON)                                               */
 g16_status g16_fr_from_canonical(const uint8_t* in, uint64_t* out, size_t n);

@@ -73,6 +73,10 @@ pub struct g16_ptau {
     _private: [u8; 0],
 }
 #[repr(C)]
+pub struct g16_wtns {
+    _private: [u8; 0],
+}
+#[repr(C)]
 pub struct g16_ark_pk {
     _private: [u8; 0],
 }
@@ -334,6 +338,11 @@ extern "C" {
     pub fn g16_multi_links(ctx: *const g16_ctx, gbps: *mut f32, echo_us: *mut f32, cap: c_int, probe_bytes: *mut u64) -> g16_status;
     pub fn g16_witness_buffer(ctx: *mut g16_ctx) -> *mut c_void;
     pub fn g16_witness_upload(ctx: *mut g16_ctx, w: *const u64, n_vars: usize) -> g16_status;
+    pub fn g16_fr_convert(device: c_int, in_le: *const u8, out_mont: *mut u64, n: usize, first_bad: *mut i64) -> g16_status;
+    pub fn g16_fr_convert_times(ms: *mut c_float, cap: u32) -> g16_status;
+    pub fn g16_witness_upload_canonical(ctx: *mut g16_ctx, w_le: *const u8, n_vars: usize, first_bad: *mut i64) -> g16_status;
+    pub fn g16_prove_canonical(ctx: *mut g16_ctx, r: *const u64, s: *const u64, w_le: *const u8, n_vars: usize, proof_out: *mut u8) -> g16_status;
+    pub fn g16_prove_batch_canonical(ctx: *mut g16_ctx, count: usize, r: *const u64, s: *const u64, w_le: *const u8, n_vars: usize, proofs_out: *mut u8, first_bad: *mut i64) -> g16_status;
     pub fn g16_witness_host_buffer(ctx: *mut g16_ctx) -> *mut c_void;
     pub fn g16_check_satisfied(device: c_int, a: *const g16_csr, b: *const g16_csr, c: *const g16_csr, num_constraints: u32, w: *const u64, n_vars: usize, first_unsatisfied: *mut i64) -> g16_status;
     pub fn g16_verify_batch(device: c_int, vk: *const g16_vk_desc, proofs: *const u8, public_inputs: *const u64, n_proofs: u32, ok_out: *mut u8) -> g16_status;
@@ -414,6 +423,11 @@ extern "C" {
     pub fn g16_wtns_read(path: *const c_char, out: *mut *mut u64, n: *mut u32) -> g16_status;
     pub fn g16_wtns_read_mem(data: *const u8, len: usize, out: *mut *mut u64, n: *mut u32) -> g16_status;
     pub fn g16_free(p: *mut c_void);
+    pub fn g16_wtns_open(path: *const c_char, out: *mut *mut g16_wtns) -> g16_status;
+    pub fn g16_wtns_open_mem(data: *const u8, len: usize, out: *mut *mut g16_wtns) -> g16_status;
+    pub fn g16_wtns_count(w: *const g16_wtns) -> u32;
+    pub fn g16_wtns_values(w: *const g16_wtns) -> *const u8;
+    pub fn g16_wtns_close(w: *mut g16_wtns);
     pub fn g16_fr_from_canonical(input: *const u8, out: *mut u64, n: usize) -> g16_status;
     pub fn g16_fr_to_canonical(input: *const u64, out: *mut u8, n: usize) -> g16_status;
 }
