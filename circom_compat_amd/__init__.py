@@ -56,6 +56,27 @@ def _np_ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _view(ptr, count, width):
+    """count x width bytes of library-owned memory as a (count, width) uint8 array, without a copy"""
+    if count == 0:
+        return np.zeros((0, width), dtype=np.uint8)
+    return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(count * width,)).reshape(count, width)
+
+
+def _rho_array(rho, n, what):
+    """the coefficients of a small-exponent test for the C ABI: None (the library draws them) or n ints in
+    [0, 2^128) -> None or an (n, 2) uint64 array, low word first; `what`: the message when the count is wrong.
+    Zero is refused by the library."""
+    if rho is None:
+        return None
+    rho = [int(x) for x in rho]
+    if len(rho) != n:
+        raise G16Error(B.G16_ERR_INVALID, what)
+    if any(not 0 <= x < 1 << 128 for x in rho):
+        raise G16Error(B.G16_ERR_INVALID, "coefficients are integers in [1, 2^128)")
+    return np.array([[x & 0xFFFFFFFFFFFFFFFF, x >> 64] for x in rho], dtype=np.uint64).reshape(-1, 2)
+
+
 def fr_from_ints(values: Sequence[int], lib: Optional[B.Library] = None) -> np.ndarray:
     """canonical ints -> (n, 4) uint64 Montgomery limbs (the in-memory form of ark_bn254::Fr)."""
     lib = lib or B.load()
@@ -226,20 +247,14 @@ def read_zkey(src, lib: Optional[B.Library] = None, validate=False) -> Tuple[Pro
     lib.check(lib.g16_zkey_key(h, C.byref(kd)), loader=True)
     N, p, n = hdr.n_vars, hdr.n_public, hdr.domain_size
 
-    def view(ptr, count, width):
-        if count == 0:
-            return np.zeros((0, width), dtype=np.uint8)
-        arr = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(count * width,))
-        return arr.reshape(count, width)
-
     cnt = C.c_uint32()
     icp = lib.g16_zkey_ic(h, C.byref(cnt))
     vk = VerifyingKey(bytes(hdr.alpha_g1), bytes(hdr.beta_g2), bytes(hdr.gamma_g2),
-                      bytes(hdr.delta_g2), view(icp, cnt.value, 64).copy())
+                      bytes(hdr.delta_g2), _view(icp, cnt.value, 64).copy())
     pk = ProvingKey(N, p, n, vk, bytes(hdr.beta_g1), bytes(hdr.delta_g1),
-                    view(kd.a_query, N, 64), view(kd.b_g1_query, N, 64),
-                    view(kd.b_g2_query, N, 128), view(kd.l_query, N - p - 1, 64),
-                    view(kd.h_query, n, 64), keepalive=handle)
+                    _view(kd.a_query, N, 64), _view(kd.b_g1_query, N, 64),
+                    _view(kd.b_g2_query, N, 128), _view(kd.l_query, N - p - 1, 64),
+                    _view(kd.h_query, n, 64), keepalive=handle)
     m = B.Matrices()
     lib.check(lib.g16_zkey_matrices(h, C.byref(m)), loader=True)
     mats = ConstraintMatrices(m.num_instance_variables, m.num_witness_variables, m.num_constraints,
@@ -968,17 +983,12 @@ def _setup_key(lib, h, n_vars: int, n_public: int) -> ProvingKey:
     gamma = (C.c_uint8 * 128)()
     lib.check(lib.g16_setup_key(h, C.byref(kd), C.byref(icp), C.byref(cnt), gamma))
 
-    def view(ptr, count, width):
-        if count == 0:
-            return np.zeros((0, width), dtype=np.uint8)
-        return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(count * width,)).reshape(count, width)
-
     vk = VerifyingKey(bytes(kd.alpha_g1), bytes(kd.beta_g2), bytes(gamma), bytes(kd.delta_g2),
-                      view(icp, cnt.value, 64).copy())
+                      _view(icp, cnt.value, 64).copy())
     return ProvingKey(kd.n_vars, kd.n_public, kd.domain_size, vk, bytes(kd.beta_g1), bytes(kd.delta_g1),
-                      view(kd.a_query, n_vars, 64), view(kd.b_g1_query, n_vars, 64),
-                      view(kd.b_g2_query, n_vars, 128), view(kd.l_query, n_vars - n_public - 1, 64),
-                      view(kd.h_query, kd.domain_size, 64), keepalive=handle)
+                      _view(kd.a_query, n_vars, 64), _view(kd.b_g1_query, n_vars, 64),
+                      _view(kd.b_g2_query, n_vars, 128), _view(kd.l_query, n_vars - n_public - 1, 64),
+                      _view(kd.h_query, kd.domain_size, 64), keepalive=handle)
 
 
 def trapdoor_setup(a: Csr, b: Csr, c: Csr, n_vars: int, n_public: int, toxic: Sequence[int],
@@ -1043,11 +1053,8 @@ def trapdoor_srs(log2_domain: int, toxic: Sequence[int], device=0, lib: Optional
     d = B.SrsDesc()
     lib.check(lib.g16_srs_desc_of(h, C.byref(d)))
 
-    def view(ptr, count, width):
-        return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(count * width,)).reshape(count, width)
-
-    return Srs(view(d.tau_g1, d.n_tau_g1, 64), view(d.tau_g2, d.n_tau, 128), view(d.alpha_tau_g1, d.n_tau, 64),
-               view(d.beta_tau_g1, d.n_tau, 64), bytes(d.beta_g2), keepalive=handle)
+    return Srs(_view(d.tau_g1, d.n_tau_g1, 64), _view(d.tau_g2, d.n_tau, 128), _view(d.alpha_tau_g1, d.n_tau, 64),
+               _view(d.beta_tau_g1, d.n_tau, 64), bytes(d.beta_g2), keepalive=handle)
 
 
 class LagrangeSrs:
@@ -1142,44 +1149,78 @@ def prepare_phase2_times(lib: Optional[B.Library] = None) -> dict:
     return dict(zip(SETUP_SRS_PHASES, (float(x) for x in ms)))
 
 
-class LagrangeReport:
+class _CheckReport:
+    """What the reports of check_key, check_contribution, check_srs and check_lagrange share: the verdict fields,
+    the per-query count dicts, equality (same class, same fields) and the skeleton of describe().  A report class
+    gives its RELATIONS (bit, words), the attribute that holds its bad-point list (LIST; an entry ends with its
+    reason bits) and how it names an entry (_where)."""
+    REASONS = ((B.KEY_BAD_NONCANONICAL, "non-canonical coordinate"), (B.KEY_BAD_OFF_CURVE, "off the curve"),
+               (B.KEY_BAD_SUBGROUP, "outside the prime-order subgroup"))
+    RELATIONS = ()
+    SINGLES = ()
+    LIST = "bad"
+
+    def _fill(self, rep, names=()):
+        self.ok = bool(rep.ok)
+        self.relations_checked = bool(rep.relations_checked)
+        self.relations_failed = int(rep.relations_failed)
+        if names:
+            self.n_points = {q: int(rep.n_points[i]) for i, q in enumerate(names)}
+            self.n_bad = {q: int(rep.n_bad[i]) for i, q in enumerate(names)}
+            self.n_infinity = {q: int(rep.n_infinity[i]) for i, q in enumerate(names)}
+
+    def __eq__(self, o):
+        return isinstance(o, type(self)) and vars(o) == vars(self)
+
+    def __repr__(self):
+        return f"{type(self).__name__}({self.describe()})"
+
+    def _where(self, entry):
+        q, i = entry[0], entry[1]
+        return f"{self.SINGLES[i]}" if q == "singles" else f"{q}[{i}]"
+
+    def _bad_words(self):
+        return f"{sum(self.n_bad.values())} bad point(s) in all"
+
+    def _relation_words(self):
+        return "; ".join(w for bit, w in self.RELATIONS if self.relations_failed & bit)
+
+    def _unlisted_words(self):
+        if not self.relations_checked:
+            return f"{sum(self.n_bad.values())} bad point(s)"
+        return self._relation_words()
+
+    def describe(self) -> str:
+        if self.ok:
+            return "ok"
+        bad = getattr(self, self.LIST)
+        if bad:
+            why = bad[0][-1]
+            words = ", ".join(w for bit, w in self.REASONS if why & bit)
+            return f"{self._where(bad[0])}: {words} (reason {why}); {self._bad_words()}"
+        return self._unlisted_words()
+
+
+class LagrangeReport(_CheckReport):
     """g16_srs_lagrange_report + the bad-point list of g16_srs_lagrange_check.  ok: no bad point and no failed
     relation; relations_checked: False when a structural failure made the relations meaningless;
     relations_failed: bit (1 << array), failed_arrays the names; n_points / n_bad / n_infinity: dicts by array
     name; bad_points: [(array_name, level, j, reason_bits)] in ascending (array, position) order, at most
     max_listed."""
-    REASONS = ((B.KEY_BAD_NONCANONICAL, "non-canonical coordinate"), (B.KEY_BAD_OFF_CURVE, "off the curve"),
-               (B.KEY_BAD_SUBGROUP, "outside the prime-order subgroup"))
+    LIST = "bad_points"
 
     def __init__(self, rep: B.SrsLagrangeReportC, bad):
-        self.ok = bool(rep.ok)
-        self.relations_checked = bool(rep.relations_checked)
-        self.relations_failed = int(rep.relations_failed)
+        self._fill(rep, B.LAGRANGE_ARRAYS)
         self.failed_arrays = [q for i, q in enumerate(B.LAGRANGE_ARRAYS) if self.relations_failed >> i & 1]
-        self.n_points = {q: int(rep.n_points[i]) for i, q in enumerate(B.LAGRANGE_ARRAYS)}
-        self.n_bad = {q: int(rep.n_bad[i]) for i, q in enumerate(B.LAGRANGE_ARRAYS)}
-        self.n_infinity = {q: int(rep.n_infinity[i]) for i, q in enumerate(B.LAGRANGE_ARRAYS)}
         self.bad_points = [(B.LAGRANGE_ARRAYS[b.query],) + LagrangeSrs.locate(b.index) + (int(b.reason),)
                            for b in bad]
 
-    def __eq__(self, o):
-        return isinstance(o, LagrangeReport) and vars(o) == vars(self)
+    def _where(self, entry):
+        return f"{entry[0]} level {entry[1]} entry {entry[2]}"
 
-    def describe(self) -> str:
-        if self.ok:
-            return "ok"
-        if self.bad_points:
-            q, p, j, why = self.bad_points[0]
-            words = ", ".join(w for bit, w in self.REASONS if why & bit)
-            return (f"{q} level {p} entry {j}: {words} (reason {why}); {sum(self.n_bad.values())} bad point(s) "
-                    "in all")
-        if not self.relations_checked:
-            return f"{sum(self.n_bad.values())} bad point(s)"
+    def _relation_words(self):
         return "; ".join(f"the Lagrange levels of {q} are not the transforms of its powers"
                          for q in self.failed_arrays)
-
-    def __repr__(self):
-        return f"LagrangeReport({self.describe()})"
 
 
 def check_lagrange(srs: Srs, lag: LagrangeSrs, rho=None, device=0, max_listed=64,
@@ -1192,14 +1233,8 @@ def check_lagrange(srs: Srs, lag: LagrangeSrs, rho=None, device=0, max_listed=64
     [1, 2^128): tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1 in this order, levels ascending."""
     lib = lib or B.load()
     d, dl = srs.to_c(), lag.to_c()
-    rho_arr = None
-    if rho is not None:
-        rho = [int(x) for x in rho]
-        if len(rho) != ((4 << lag.power) - 1) + 3 * ((2 << lag.power) - 1):
-            raise G16Error(B.G16_ERR_INVALID, "one coefficient per Lagrange point")
-        if any(not 0 <= x < 1 << 128 for x in rho):
-            raise G16Error(B.G16_ERR_INVALID, "coefficients are integers in [1, 2^128)")
-        rho_arr = np.array([[x & 0xFFFFFFFFFFFFFFFF, x >> 64] for x in rho], dtype=np.uint64).reshape(-1, 2)
+    rho_arr = _rho_array(rho, ((4 << lag.power) - 1) + 3 * ((2 << lag.power) - 1),
+                         "one coefficient per Lagrange point")
     max_listed = int(max_listed)
     bad = (B.KeyBadPoint * max(max_listed, 1))()
     rep = B.SrsLagrangeReportC()
@@ -1263,18 +1298,15 @@ def read_ptau(src, validate=False, lagrange=False, lib: Optional[B.Library] = No
     d = B.SrsDesc()
     lib.check(lib.g16_ptau_srs(h, C.byref(d)), loader=True)
 
-    def view(ptr, count, width):
-        return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(count * width,)).reshape(count, width)
-
-    srs = Srs(view(d.tau_g1, d.n_tau_g1, 64), view(d.tau_g2, d.n_tau, 128), view(d.alpha_tau_g1, d.n_tau, 64),
-              view(d.beta_tau_g1, d.n_tau, 64), bytes(d.beta_g2), keepalive=handle)
+    srs = Srs(_view(d.tau_g1, d.n_tau_g1, 64), _view(d.tau_g2, d.n_tau, 128), _view(d.alpha_tau_g1, d.n_tau, 64),
+              _view(d.beta_tau_g1, d.n_tau, 64), bytes(d.beta_g2), keepalive=handle)
     srs.power, srs.ceremony_power = int(hdr.power), int(hdr.ceremony_power)
     if lagrange:
         dl = B.SrsLagrangeDesc()
         lib.check(lib.g16_ptau_lagrange(h, C.byref(dl)), loader=True)
         m1, m2 = (4 << dl.power) - 1, (2 << dl.power) - 1
-        srs.lagrange = LagrangeSrs(dl.power, view(dl.tau_g1, m1, 64), view(dl.tau_g2, m2, 128),
-                                   view(dl.alpha_tau_g1, m2, 64), view(dl.beta_tau_g1, m2, 64), keepalive=handle)
+        srs.lagrange = LagrangeSrs(dl.power, _view(dl.tau_g1, m1, 64), _view(dl.tau_g2, m2, 128),
+                                   _view(dl.alpha_tau_g1, m2, 64), _view(dl.beta_tau_g1, m2, 64), keepalive=handle)
     if validate:
         rep = check_srs(srs, lib=lib)
         if not rep.ok:
@@ -1300,7 +1332,7 @@ def write_ptau(path, srs: Srs, lagrange: Optional[LagrangeSrs] = None, lib: Opti
     lib.check(lib.g16_ptau_write(os.fsencode(path), C.byref(d), _srs_power(d)), loader=True)
 
 
-class SrsReport:
+class SrsReport(_CheckReport):
     """g16_srs_report + the bad-point list of g16_srs_check.  ok: no bad point and no failed relation;
     relations_checked: False when a structural failure made the pairing relations meaningless;
     relations_failed: SRS_* bits (_binding); n_points / n_bad / n_infinity: dicts by array name
@@ -1314,35 +1346,12 @@ class SrsReport:
                  (B.SRS_PAIR_ALPHA, "alpha_tau_g1 is not a sequence of powers of tau"),
                  (B.SRS_PAIR_BETA, "beta_tau_g1 is not a sequence of powers of tau"),
                  (B.SRS_PAIR_BETA_G2, "e(beta_tau_g1[0], g2) != e(g1, beta_g2)"))
-    REASONS = ((B.KEY_BAD_NONCANONICAL, "non-canonical coordinate"), (B.KEY_BAD_OFF_CURVE, "off the curve"),
-               (B.KEY_BAD_SUBGROUP, "outside the prime-order subgroup"))
+    SINGLES = B.SRS_SINGLES
+    LIST = "bad_points"
 
     def __init__(self, rep: B.SrsReportC, bad):
-        self.ok = bool(rep.ok)
-        self.relations_checked = bool(rep.relations_checked)
-        self.relations_failed = int(rep.relations_failed)
-        self.n_points = {q: int(rep.n_points[i]) for i, q in enumerate(B.SRS_QUERIES)}
-        self.n_bad = {q: int(rep.n_bad[i]) for i, q in enumerate(B.SRS_QUERIES)}
-        self.n_infinity = {q: int(rep.n_infinity[i]) for i, q in enumerate(B.SRS_QUERIES)}
+        self._fill(rep, B.SRS_QUERIES)
         self.bad_points = [(B.SRS_QUERIES[b.query], int(b.index), int(b.reason)) for b in bad]
-
-    def __eq__(self, o):
-        return isinstance(o, SrsReport) and vars(o) == vars(self)
-
-    def describe(self) -> str:
-        if self.ok:
-            return "ok"
-        if self.bad_points:
-            q, i, why = self.bad_points[0]
-            words = ", ".join(w for bit, w in self.REASONS if why & bit)
-            name = f"{B.SRS_SINGLES[i]}" if q == "singles" else f"{q}[{i}]"
-            return f"{name}: {words} (reason {why}); {sum(self.n_bad.values())} bad point(s) in all"
-        if not self.relations_checked:
-            return f"{sum(self.n_bad.values())} bad point(s)"
-        return "; ".join(w for bit, w in self.RELATIONS if self.relations_failed & bit)
-
-    def __repr__(self):
-        return f"SrsReport({self.describe()})"
 
 
 def check_srs(srs: Srs, rho=None, device=0, max_listed=64, lib: Optional[B.Library] = None) -> SrsReport:
@@ -1356,14 +1365,7 @@ def check_srs(srs: Srs, rho=None, device=0, max_listed=64, lib: Optional[B.Libra
     [1, 2^128), the coefficients of tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1 in this order."""
     lib = lib or B.load()
     d = srs.to_c()
-    rho_arr = None
-    if rho is not None:
-        rho = [int(x) for x in rho]
-        if len(rho) != (d.n_tau_g1 - 1) + 3 * (d.n_tau - 1):
-            raise G16Error(B.G16_ERR_INVALID, "one coefficient per pair of neighbours")
-        if any(not 0 <= x < 1 << 128 for x in rho):
-            raise G16Error(B.G16_ERR_INVALID, "coefficients are integers in [1, 2^128)")
-        rho_arr = np.array([[x & 0xFFFFFFFFFFFFFFFF, x >> 64] for x in rho], dtype=np.uint64).reshape(-1, 2)
+    rho_arr = _rho_array(rho, (d.n_tau_g1 - 1) + 3 * (d.n_tau - 1), "one coefficient per pair of neighbours")
     max_listed = int(max_listed)
     bad = (B.KeyBadPoint * max(max_listed, 1))()
     rep = B.SrsReportC()
@@ -1601,16 +1603,11 @@ def read_ark_key(src, compressed=True, validate=True, device=0, lib: Optional[B.
     lib.check(lib.g16_ark_pk_key(h, C.byref(kd), C.byref(vd)), loader=True)
     N, p, n = kd.n_vars, kd.n_public, kd.domain_size
 
-    def view(ptr, count, width):
-        if count == 0:
-            return np.zeros((0, width), dtype=np.uint8)
-        return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(count * width,)).reshape(count, width)
-
     vk = VerifyingKey(bytes(vd.alpha_g1), bytes(vd.beta_g2), bytes(vd.gamma_g2), bytes(vd.delta_g2),
-                      view(vd.ic, vd.ic_count, 64).copy())
-    return ProvingKey(N, p, n, vk, bytes(kd.beta_g1), bytes(kd.delta_g1), view(kd.a_query, N, 64),
-                      view(kd.b_g1_query, N, 64), view(kd.b_g2_query, N, 128), view(kd.l_query, N - p - 1, 64),
-                      view(kd.h_query, n, 64), keepalive=handle)
+                      _view(vd.ic, vd.ic_count, 64).copy())
+    return ProvingKey(N, p, n, vk, bytes(kd.beta_g1), bytes(kd.delta_g1), _view(kd.a_query, N, 64),
+                      _view(kd.b_g1_query, N, 64), _view(kd.b_g2_query, N, 128), _view(kd.l_query, N - p - 1, 64),
+                      _view(kd.h_query, n, 64), keepalive=handle)
 
 
 def write_ark_key(pk: ProvingKey, compressed=True, h_len=None, device=0, lib: Optional[B.Library] = None) -> bytes:
@@ -1705,7 +1702,7 @@ def _verify_args(vk, proofs, public_inputs, lib):
     return d, buf, pubs, n, ic
 
 
-class KeyReport:
+class KeyReport(_CheckReport):
     """g16_key_report + the bad-point list of g16_key_check.  ok: no bad point and no failed relation;
     relations_checked: False when a structural failure made the pairing relations meaningless;
     relations_failed: KEY_PAIR_BETA | KEY_PAIR_DELTA | KEY_PAIR_B | KEY_VK_MISMATCH bits (_binding);
@@ -1715,35 +1712,11 @@ class KeyReport:
                  (B.KEY_PAIR_DELTA, "e(delta_g1, g2) != e(g1, delta_g2)"),
                  (B.KEY_PAIR_B, "b_g1_query and b_g2_query do not hold the same scalars"),
                  (B.KEY_VK_MISMATCH, "the verifying key differs from the proving key"))
-    REASONS = ((B.KEY_BAD_NONCANONICAL, "non-canonical coordinate"), (B.KEY_BAD_OFF_CURVE, "off the curve"),
-               (B.KEY_BAD_SUBGROUP, "outside the prime-order subgroup"))
+    SINGLES = B.KEY_SINGLES
 
     def __init__(self, rep: B.KeyReportC, bad):
-        self.ok = bool(rep.ok)
-        self.relations_checked = bool(rep.relations_checked)
-        self.relations_failed = int(rep.relations_failed)
-        self.n_points = {q: int(rep.n_points[i]) for i, q in enumerate(B.KEY_QUERIES)}
-        self.n_bad = {q: int(rep.n_bad[i]) for i, q in enumerate(B.KEY_QUERIES)}
-        self.n_infinity = {q: int(rep.n_infinity[i]) for i, q in enumerate(B.KEY_QUERIES)}
+        self._fill(rep, B.KEY_QUERIES)
         self.bad = [(B.KEY_QUERIES[b.query], int(b.index), int(b.reason)) for b in bad]
-
-    def __eq__(self, o):
-        return isinstance(o, KeyReport) and vars(o) == vars(self)
-
-    def describe(self) -> str:
-        if self.ok:
-            return "ok"
-        if self.bad:
-            q, i, why = self.bad[0]
-            words = ", ".join(w for bit, w in self.REASONS if why & bit)
-            name = f"{B.KEY_SINGLES[i]}" if q == "singles" else f"{q}[{i}]"
-            return f"{name}: {words} (reason {why}); {sum(self.n_bad.values())} bad point(s) in all"
-        if not self.relations_checked:
-            return f"{sum(self.n_bad.values())} bad point(s)"
-        return "; ".join(w for bit, w in self.RELATIONS if self.relations_failed & bit)
-
-    def __repr__(self):
-        return f"KeyReport({self.describe()})"
 
 
 def check_key(pk: "ProvingKey", vk=None, rho=None, device=0, max_listed=64,
@@ -1768,14 +1741,7 @@ def check_key(pk: "ProvingKey", vk=None, rho=None, device=0, max_listed=64,
         C.memmove(d.gamma_g2, bytes(vk.gamma_g2), 128)
         C.memmove(d.delta_g2, bytes(vk.delta_g2), 128)
         d.ic, d.ic_count = ic.ctypes.data, ic.shape[0]
-    rho_arr = None
-    if rho is not None:
-        rho = [int(x) for x in rho]
-        if len(rho) != pk.n_vars:
-            raise G16Error(B.G16_ERR_INVALID, "one coefficient per wire")
-        if any(not 0 <= x < 1 << 128 for x in rho):
-            raise G16Error(B.G16_ERR_INVALID, "coefficients are integers in [1, 2^128)")
-        rho_arr = np.array([[x & 0xFFFFFFFFFFFFFFFF, x >> 64] for x in rho], dtype=np.uint64).reshape(-1, 2)
+    rho_arr = _rho_array(rho, pk.n_vars, "one coefficient per wire")
     max_listed = int(max_listed)
     bad = (B.KeyBadPoint * max(max_listed, 1))()
     rep = B.KeyReportC()
@@ -1813,7 +1779,7 @@ def contribute_key(pk: "ProvingKey", d=None, device=0, lib: Optional[B.Library] 
                       pk.b_g1_query, pk.b_g2_query, l_out, h_out, keepalive=pk)
 
 
-class ContributionReport:
+class ContributionReport(_CheckReport):
     """g16_contribution_report + the bad-point list of g16_key_contribution_check.  ok: nothing but delta
     changed, no bad point, no failed relation; relations_checked: False when a structural failure (or keys of
     different sizes) made the pairing relations meaningless; relations_failed: CONTRIB_* bits (_binding);
@@ -1825,30 +1791,20 @@ class ContributionReport:
                  (B.CONTRIB_PAIR_L, "l_query was not scaled by the inverse of delta's factor"),
                  (B.CONTRIB_PAIR_H, "h_query was not scaled by the inverse of delta's factor"))
 
+    SINGLES = B.KEY_SINGLES
+
     def __init__(self, rep: B.ContributionReportC, bad):
-        self.ok = bool(rep.ok)
-        self.relations_checked = bool(rep.relations_checked)
-        self.relations_failed = int(rep.relations_failed)
+        self._fill(rep)
         self.n_bad = {"l_query": int(rep.n_bad_l), "h_query": int(rep.n_bad_h)}
         self.bad = [(B.KEY_QUERIES[b.query], int(b.index), int(b.reason)) for b in bad]
 
-    def __eq__(self, o):
-        return isinstance(o, ContributionReport) and vars(o) == vars(self)
+    def _bad_words(self):
+        return f"{len(self.bad)} bad point(s) listed"
 
-    def describe(self) -> str:
-        if self.ok:
-            return "ok"
-        if self.bad:
-            q, i, why = self.bad[0]
-            words = ", ".join(w for bit, w in KeyReport.REASONS if why & bit)
-            name = f"{B.KEY_SINGLES[i]}" if q == "singles" else f"{q}[{i}]"
-            return f"{name}: {words} (reason {why}); {len(self.bad)} bad point(s) listed"
+    def _unlisted_words(self):
         if self.relations_failed:
-            return "; ".join(w for bit, w in self.RELATIONS if self.relations_failed & bit)
+            return self._relation_words()
         return f"{sum(self.n_bad.values())} bad point(s)"
-
-    def __repr__(self):
-        return f"ContributionReport({self.describe()})"
 
 
 def check_contribution(before: "ProvingKey", after: "ProvingKey", rho=None, device=0, max_listed=64,
@@ -1861,14 +1817,8 @@ def check_contribution(before: "ProvingKey", after: "ProvingKey", rho=None, devi
     len(l_query) + len(h_query) ints in [1, 2^128), L's first.  The contribution transcript is NOT checked."""
     lib = lib or B.load()
     kb, ka = before.to_c(), after.to_c()
-    rho_arr = None
-    if rho is not None:
-        rho = [int(x) for x in rho]
-        if len(rho) != before.n_vars - before.n_public - 1 + before.domain_size:
-            raise G16Error(B.G16_ERR_INVALID, "one coefficient per point of l_query and h_query")
-        if any(not 0 <= x < 1 << 128 for x in rho):
-            raise G16Error(B.G16_ERR_INVALID, "coefficients are integers in [1, 2^128)")
-        rho_arr = np.array([[x & 0xFFFFFFFFFFFFFFFF, x >> 64] for x in rho], dtype=np.uint64).reshape(-1, 2)
+    rho_arr = _rho_array(rho, before.n_vars - before.n_public - 1 + before.domain_size,
+                         "one coefficient per point of l_query and h_query")
     max_listed = int(max_listed)
     bad = (B.KeyBadPoint * max(max_listed, 1))()
     rep = B.ContributionReportC()
@@ -1910,14 +1860,7 @@ def verify_aggregate(vk: "VerifyingKey", proofs, public_inputs, rho=None, device
     return_structural=True returns (verdict, [proof i is well formed])."""
     lib = lib or B.load()
     d, buf, pubs, n, _ic = _verify_args(vk, proofs, public_inputs, lib)
-    rho_arr = None
-    if rho is not None:
-        rho = [int(x) for x in rho]
-        if len(rho) != n:
-            raise G16Error(B.G16_ERR_INVALID, "one coefficient per proof")
-        if any(not 0 <= x < 1 << 128 for x in rho):
-            raise G16Error(B.G16_ERR_INVALID, "coefficients are integers in [1, 2^128)")
-        rho_arr = np.array([[x & 0xFFFFFFFFFFFFFFFF, x >> 64] for x in rho], dtype=np.uint64).reshape(n, 2)
+    rho_arr = _rho_array(rho, n, "one coefficient per proof")
     ok = np.zeros(1, dtype=np.uint8)
     structural = np.zeros(max(n, 1), dtype=np.uint8)
     st = lib.g16_verify_aggregate(device, C.byref(d), _np_ptr(buf), _np_ptr(pubs), n,

@@ -113,7 +113,7 @@ __global__ void __launch_bounds__(KC_BLOCK) k_ak_decode(const uint32_t* in, uint
 
 // G2 with G16_ARK_VALIDATE, behind k_ak_decode<Fq2>: a point that decoded and is not in the r-torsion becomes
 // G16_KEY_BAD_SUBGROUP and an all-zero record.  A kernel of its own: the 254-bit double-and-add needs the registers
-// of k_kc_g2, the square roots of the decode far fewer.
+// of k_chk_flags_g2, the square roots of the decode far fewer.
 __global__ void __launch_bounds__(KC_BLOCK) k_ak_subgroup(G2Affine* pts, uint32_t n, uint8_t* reason) {
   const uint32_t i = blockIdx.x * KC_BLOCK + threadIdx.x;
   if (i >= n || reason[i]) return;

@@ -18,13 +18,10 @@
 //
 // g16_key_contribution_check: keycheck.hip's structure on the points a contribution changes.  Per chunk of a
 // query (L or H), the AFTER points, the BEFORE points and rho side by side in one slot:
-//   k_cc_g1      reason byte per AFTER point       k_cc_rho / k_cc_fold   sum rho_i P_i over both sides
-//   k_cc_collect counts / lists the bad points by a scan (no atomics)
-//   k_cc_final   six Miller loops, three final exponentiations, the report and the list.
-#include <stdlib.h>
-
-#include <memory>
-
+//   k_chk_flags_g1  reason byte per AFTER point    k_cc_rho / k_chk_fold  sum rho_i P_i over both sides
+//   k_chk_collect   counts / lists the bad points by a scan (no atomics)
+//   k_cc_final      six Miller loops, three final exponentiations, the report and the list.
+// The flag, fold and collect kernels, the halves of the final kernel and the staging are those of keycheck.h.
 #include "keycheck.h"
 
 namespace g16 {
@@ -141,23 +138,10 @@ struct CcKey {
 };
 
 struct CcState {  // device-resident for the whole call
-  uint64_t n_bad[CC_N];
-  uint32_t n_list[CC_N];
+  CheckTally tally;  // slots CC_L, CC_H, CC_SINGLES
   G1XYZZ sum[2][2];  // [L, H][before, after]: sum rho_i P_i so far
   g16_contribution_report report;
 };
-
-__global__ void __launch_bounds__(KC_BLOCK) k_cc_g1(const G1Affine* pts, uint32_t n, uint8_t* flags) {
-  const uint32_t i = blockIdx.x * KC_BLOCK + threadIdx.x;
-  if (i >= n) return;
-  flags[i] = g1_flag(pts[i]);
-}
-
-__global__ void __launch_bounds__(KC_BLOCK) k_cc_g2(const VkDev* vk, const G2Affine* pts, uint32_t n, uint8_t* flags) {
-  const uint32_t i = blockIdx.x * KC_BLOCK + threadIdx.x;
-  if (i >= n) return;
-  flags[i] = g2_flag(pts[i], vk);
-}
 
 // blockIdx.y = 0: part[block] = sum over the block of rho_i BEFORE_i; 1: part[nb + block] = the same over AFTER.
 // Entry i is left out on both sides when AFTER_i is malformed: the relations are not reported then anyway.
@@ -172,66 +156,6 @@ __global__ void __launch_bounds__(KC_BLOCK) k_cc_rho(const G1Affine* before, con
   if (t == 0) part[blockIdx.y * gridDim.x + blockIdx.x] = sh[0];
 }
 
-// one block: the chunk's 2 x nb block sums into the two running sums of query q
-__global__ void __launch_bounds__(KC_BLOCK) k_cc_fold(const G1XYZZ* part, uint32_t nb, uint32_t q, CcState* st) {
-  __shared__ G1XYZZ sh[KC_BLOCK];
-  const uint32_t t = threadIdx.x;
-#pragma unroll 1
-  for (uint32_t side = 0; side < 2; ++side) {
-    G1XYZZ a = G1XYZZ::infinity();
-#pragma unroll 1
-    for (uint32_t k = t; k < nb; k += KC_BLOCK) a.add(part[side * nb + k]);
-    kc_block_sum(sh, a);
-    if (t == 0) {
-      G1XYZZ s = st->sum[q][side];
-      s.add(sh[0]);
-      st->sum[q][side] = s;
-    }
-    __syncthreads();
-  }
-}
-
-// k_kc_collect of keycheck.hip on this call's state: lane t owns a contiguous run of the chunk's flags; counts,
-// an exclusive scan, then every lane appends its bad points behind those of the lanes before it
-__global__ void __launch_bounds__(KC_SCAN) k_cc_collect(const uint8_t* flags, uint32_t n, uint32_t q, uint32_t base,
-                                                        CcState* st, g16_key_bad_point* lists, uint32_t cap) {
-  __shared__ uint32_t sh_bad[KC_SCAN];
-  __shared__ uint32_t sh_start;
-  const uint32_t t = threadIdx.x;
-  const uint32_t seg = (n + KC_SCAN - 1) / KC_SCAN;
-  const uint32_t lo = t * seg < n ? t * seg : n, hi = lo + seg < n ? lo + seg : n;
-  uint32_t bad = 0;
-#pragma unroll 1
-  for (uint32_t i = lo; i < hi; ++i) bad += (flags[i] & ~KC_INF) ? 1 : 0;
-  sh_bad[t] = bad;
-  __syncthreads();
-  if (t == 0) {
-    uint32_t run = 0;
-#pragma unroll 1
-    for (uint32_t k = 0; k < KC_SCAN; ++k) {
-      const uint32_t c = sh_bad[k];
-      sh_bad[k] = run;
-      run += c;
-    }
-    const uint32_t start = st->n_list[q];
-    sh_start = start;
-    st->n_bad[q] += run;
-    st->n_list[q] = (uint64_t)start + run < cap ? start + run : cap;
-  }
-  __syncthreads();
-  uint64_t at = (uint64_t)sh_start + sh_bad[t];
-  g16_key_bad_point* list = lists + (size_t)q * cap;
-#pragma unroll 1
-  for (uint32_t i = lo; i < hi && bad && at < cap; ++i) {
-    const uint8_t f = flags[i] & ~KC_INF;
-    if (!f) continue;
-    list[at].query = CC_QUERY_ID[q];
-    list[at].index = base + i;
-    list[at].reason = f;
-    ++at;
-  }
-}
-
 // lanes 0..5: ML(g2, delta1') ML(delta2', -g1) | ML(delta2, S_L) ML(delta2', -S_L') | the same for H;
 // lanes 0..2: product and final exponentiation of one pair each; then the report and the list.
 // Nothing is paired when a structural check failed.
@@ -240,22 +164,9 @@ __global__ void __launch_bounds__(KC_BLOCK) k_cc_final(const VkDev* vk, const Cc
                                                        g16_key_bad_point* out_list) {
   __shared__ F12 sh[6];
   __shared__ uint32_t sh_fail[3];
-  __shared__ uint32_t sh_any, sh_off[CC_N + 1];
+  __shared__ uint32_t sh_off[CC_N + 2];
   const uint32_t t = threadIdx.x;
-  if (t == 0) {
-    uint64_t bad = 0;
-    uint32_t off = 0;
-    for (int q = 0; q < CC_N; ++q) {
-      bad += st->n_bad[q];
-      sh_off[q] = off;
-      const uint32_t room = cap - off;
-      off += st->n_list[q] < room ? st->n_list[q] : room;
-    }
-    sh_off[CC_N] = off;
-    sh_any = bad ? 1 : 0;
-  }
-  __syncthreads();
-  const bool pair = !sh_any;
+  const bool pair = !chk_offsets(&st->tally, CC_N, cap, sh_off);
   G2Affine Q = G2Affine::infinity();
   G1Affine P = G1Affine::infinity();
   if (pair && t < 6) {
@@ -272,54 +183,26 @@ __global__ void __launch_bounds__(KC_BLOCK) k_cc_final(const VkDev* vk, const Cc
       if (side) P = P.neg();
     }
   }
-  F12 f = f12_one();
-  miller_mul(&f, &Q, &P, vk);  // one call site: infinity on either side (every idle lane) returns at once
-  if (t < 6) sh[t] = f;
-  __syncthreads();
-  if (t < 3) {
-    bool one = true;
-    if (pair) {
-      F12 g;
-      f12_mul(&g, &sh[2 * t], &sh[2 * t + 1]);
-      one = final_exp_is_one(&g, vk);
-    }
-    sh_fail[t] = one ? 0 : (2u << t);  // G16_CONTRIB_PAIR_DELTA, _L, _H
-  }
-  __syncthreads();
+  const uint32_t failed = chk_pairs(Q, P, 3, pair, vk, sh, sh_fail);
   if (t == 0) {
     g16_contribution_report r;
     memset(&r, 0, sizeof r);
     r.relations_checked = pair ? 1 : 0;
     r.relations_failed = mismatch ? G16_CONTRIB_UNCHANGED_MISMATCH : 0;
     if (pair) {
-      r.relations_failed |= sh_fail[0] | sh_fail[1] | sh_fail[2];
+      r.relations_failed |= failed * G16_CONTRIB_PAIR_DELTA;  // pairs 0, 1, 2: G16_CONTRIB_PAIR_DELTA, _L, _H
       if (key->delta_g1_after.is_inf() || key->delta_g2_after.is_inf()) r.relations_failed |= G16_CONTRIB_DELTA_INFINITE;
     }
     r.ok = (pair && !r.relations_failed) ? 1 : 0;
-    r.n_bad_l = st->n_bad[CC_L];
-    r.n_bad_h = st->n_bad[CC_H];
+    r.n_bad_l = st->tally.n_bad[CC_L];
+    r.n_bad_h = st->tally.n_bad[CC_H];
     r.n_listed = sh_off[CC_N];
     st->report = r;
   }
-#pragma unroll 1
-  for (int q = 0; q < CC_N; ++q) {
-    const uint32_t cnt = sh_off[q + 1] - sh_off[q];
-#pragma unroll 1
-    for (uint32_t k = t; k < cnt; k += KC_BLOCK) out_list[sh_off[q] + k] = lists[(size_t)q * cap + k];
-  }
+  chk_emit_lists(sh_off, CC_N, lists, cap, out_list);
 }
 
 // ---- host side -------------------------------------------------------------------------------------
-uint32_t chunk_from_env(uint64_t longest) {
-  uint32_t chunk = CT_DEFAULT_CHUNK;
-  if (const char* e = getenv("G16_CONTRIB_CHUNK")) {  // tests: points per staged chunk
-    const unsigned long long v = strtoull(e, nullptr, 0);
-    if (v >= 1 && v <= (1ull << 24)) chunk = (uint32_t)v;
-  }
-  if (longest < 1) longest = 1;
-  return chunk > longest ? (uint32_t)longest : chunk;
-}
-
 bool key_shape_ok(const g16_key_desc* k) {
   if (!k || k->n_vars < 1 || (uint64_t)k->n_public + 1 > k->n_vars) return false;
   const uint64_t n_l = (uint64_t)k->n_vars - k->n_public - 1;
@@ -351,9 +234,7 @@ extern "C" g16_status g16_key_contribute(int device, const g16_key_desc* key, co
   if (!key_shape_ok(key) || !delta_g1_out || !delta_g2_out) return G16_ERR_INVALID;
   const uint64_t n_l = (uint64_t)key->n_vars - key->n_public - 1, dom = key->domain_size;
   if ((n_l && !l_out) || (dom && !h_out)) return G16_ERR_INVALID;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return G16_ERR_NO_DEVICE;
-  if (device < 0 || device >= ndev) return G16_ERR_INVALID;
+  if (const g16_status ds = device_ok(device)) return ds;
 
   // every copy of d and of what is derived from it lives in this struct and is wiped on every way out
   struct Secret {
@@ -390,7 +271,7 @@ extern "C" g16_status g16_key_contribute(int device, const g16_key_desc* key, co
     const G1Affine nd1 = G1XYZZ::from_affine(d1).mul(sec.dc).to_affine();
     const G2Affine nd2 = G2XYZZ::from_affine(d2).mul(sec.dc).to_affine();
 
-    const uint32_t chunk = chunk_from_env(n_l > dom ? n_l : dom);
+    const uint32_t chunk = chunk_from_env("G16_CONTRIB_CHUNK", CT_DEFAULT_CHUNK, n_l > dom ? n_l : dom);
     std::vector<CtItem> items;
     for (uint64_t at = 0; at < n_l; at += chunk)
       items.push_back(CtItem{key->l_query + at * 64, l_out + at * 64, (uint32_t)(n_l - at < chunk ? n_l - at : chunk)});
@@ -465,9 +346,7 @@ extern "C" g16_status g16_key_contribution_check(int device, const g16_key_desc*
   if (!before->a_query || !before->b_g1_query || !before->b_g2_query || !after->a_query || !after->b_g1_query ||
       !after->b_g2_query)
     return G16_ERR_INVALID;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return G16_ERR_NO_DEVICE;
-  if (device < 0 || device >= ndev) return G16_ERR_INVALID;
+  if (const g16_status ds = device_ok(device)) return ds;
   memset(report, 0, sizeof *report);
   // 1. what a contribution must leave alone: compared as bytes on the host
   if (before->n_vars != after->n_vars || before->n_public != after->n_public ||
@@ -476,9 +355,7 @@ extern "C" g16_status g16_key_contribution_check(int device, const g16_key_desc*
     return G16_OK;
   }
   const uint64_t N = before->n_vars, n_l = N - before->n_public - 1, dom = before->domain_size;
-  if (rho)
-    for (uint64_t i = 0; i < n_l + dom; ++i)
-      if (!(rho[2 * i] | rho[2 * i + 1])) return G16_ERR_INVALID;
+  if (!rho_all_nonzero(rho, n_l + dom)) return G16_ERR_INVALID;
   const uint32_t mismatch =
       (memcmp(before->alpha_g1, after->alpha_g1, 64) || memcmp(before->beta_g1, after->beta_g1, 64) ||
        memcmp(before->beta_g2, after->beta_g2, 128) || memcmp(before->a_query, after->a_query, N * 64) ||
@@ -486,9 +363,8 @@ extern "C" g16_status g16_key_contribution_check(int device, const g16_key_desc*
           ? 1
           : 0;
   try {
-    const uint32_t chunk = chunk_from_env(n_l > dom ? n_l : dom);
+    const uint32_t chunk = chunk_from_env("G16_CONTRIB_CHUNK", CT_DEFAULT_CHUNK, n_l > dom ? n_l : dom);
     const uint32_t nb_max = ceil_div(chunk, KC_BLOCK);
-    const uint32_t cap = bad_cap < KC_MAX_LISTED ? bad_cap : KC_MAX_LISTED;
 
     std::vector<CcItem> items;
     auto add_pairs = [&](uint32_t q, const uint8_t* a, const uint8_t* b, uint64_t count, const uint64_t* r) {
@@ -503,15 +379,6 @@ extern "C" g16_status g16_key_contribution_check(int device, const g16_key_desc*
     items.push_back(CcItem{CCK_G2, CC_SINGLES, 4, 1, after->delta_g2, nullptr, nullptr});
 
     G16_HIP(hipSetDevice(device));
-    std::unique_ptr<VkDev> hv(new VkDev());
-    {
-      const HostConsts& H = host_consts();
-      memset(hv.get(), 0, sizeof(VkDev));
-      hv->frob_x = H.frob_x;
-      hv->frob_y = H.frob_y;
-      hv->b_twist = H.b_twist;
-      memcpy(hv->frob, H.frob, sizeof H.frob);
-    }
     CcKey hk;
     memcpy(&hk.delta_g1_after, after->delta_g1, 64);
     memcpy(&hk.delta_g2_before, before->delta_g2, 128);
@@ -521,44 +388,23 @@ extern "C" g16_status g16_key_contribution_check(int device, const g16_key_desc*
     std::unique_ptr<CcState> hs(new CcState());
     memset(hs.get(), 0, sizeof(CcState));
 
-    // every allocation of the call: nothing is allocated inside the chunk loop
     size_t slot_bytes = (size_t)chunk * CC_SLOT_BYTES_PER_POINT;
     if (slot_bytes < 128) slot_bytes = 128;  // delta_g2 alone
-    PinnedBuf pin[2];
-    DevBuf<uint8_t> dslot[2], dflags;
-    DevBuf<VkDev> dvk;
+    CheckStage stage(slot_bytes, chunk, CC_N, bad_cap);
     DevBuf<CcKey> dkey;
     DevBuf<CcState> dst;
     DevBuf<G1XYZZ> dpart;
-    DevBuf<g16_key_bad_point> dlists, dout;
-    StreamBox copy, comp;
-    EventBox copied[2], done[2];
-    for (int s = 0; s < 2; ++s) {
-      pin[s].alloc(slot_bytes);
-      dslot[s].alloc(slot_bytes);
-      copied[s].create();
-      done[s].create();
-    }
-    dflags.alloc(chunk);
-    dvk.alloc(1);
     dkey.alloc(1);
     dst.alloc(1);
     dpart.alloc(2 * (size_t)nb_max);
-    dlists.alloc((size_t)CC_N * (cap ? cap : 1));
-    dout.alloc(cap ? cap : 1);
-    copy.create();
-    comp.create();
-    G16_HIP(hipMemcpy(dvk.p, hv.get(), sizeof(VkDev), hipMemcpyHostToDevice));
     G16_HIP(hipMemcpy(dkey.p, &hk, sizeof hk, hipMemcpyHostToDevice));
     G16_HIP(hipMemcpy(dst.p, hs.get(), sizeof(CcState), hipMemcpyHostToDevice));
+    const hipStream_t copy = stage.copy.s, comp = stage.comp.s;
+    uint8_t* flags = stage.dflags.p;
 
     const size_t off_before = (size_t)chunk * 64, off_rho = (size_t)chunk * 128;
-    for (size_t k = 0; k < items.size(); ++k) {
-      const CcItem& it = items[k];
-      const int s = (int)(k & 1);
-      if (k >= 2) G16_HIP(hipEventSynchronize(done[s].e));  // the kernels that read this slot two chunks ago
-      uint8_t* h = pin[s].p;
-      uint8_t* dv = dslot[s].p;
+    for (const CcItem& it : items) {
+      const auto [h, dv] = stage.begin();
       const uint32_t n = it.count;
       const uint32_t nb = ceil_div(n, KC_BLOCK);
       if (it.kind == CCK_PAIR) {
@@ -567,48 +413,35 @@ extern "C" g16_status g16_key_contribution_check(int device, const g16_key_desc*
         uint64_t* hr = (uint64_t*)(h + off_rho);
         if (it.rho) {
           memcpy(hr, it.rho, (size_t)n * 16);
-        } else {  // drawn chunk by chunk, straight into the staging slot
-          bool drawn = os_random(hr, (size_t)n * 16);
-          for (uint32_t i = 0; drawn && i < n; ++i)
-            while (drawn && !(hr[2 * (size_t)i] | hr[2 * (size_t)i + 1]))  // probability 2^-128 per entry
-              drawn = os_random(&hr[2 * (size_t)i], 16);
-          if (!drawn) {  // never a fixed fallback; the chunks in flight still read the slots
-            (void)hipStreamSynchronize(copy.s);
-            (void)hipStreamSynchronize(comp.s);
-            return G16_ERR_INTERNAL;
-          }
+        } else if (!draw_rho(hr, n)) {  // drawn chunk by chunk, straight into the staging slot
+          stage.drain();
+          return G16_ERR_INTERNAL;
         }
-        G16_HIP(hipMemcpyAsync(dv, h, (size_t)n * 64, hipMemcpyHostToDevice, copy.s));
-        G16_HIP(hipMemcpyAsync(dv + off_before, h + off_before, (size_t)n * 64, hipMemcpyHostToDevice, copy.s));
-        G16_HIP(hipMemcpyAsync(dv + off_rho, h + off_rho, (size_t)n * 16, hipMemcpyHostToDevice, copy.s));
+        G16_HIP(hipMemcpyAsync(dv, h, (size_t)n * 64, hipMemcpyHostToDevice, copy));
+        G16_HIP(hipMemcpyAsync(dv + off_before, h + off_before, (size_t)n * 64, hipMemcpyHostToDevice, copy));
+        G16_HIP(hipMemcpyAsync(dv + off_rho, h + off_rho, (size_t)n * 16, hipMemcpyHostToDevice, copy));
       } else {
         const size_t bytes = (size_t)n * (it.kind == CCK_G2 ? 128 : 64);
         memcpy(h, it.after, bytes);
-        G16_HIP(hipMemcpyAsync(dv, h, bytes, hipMemcpyHostToDevice, copy.s));
+        G16_HIP(hipMemcpyAsync(dv, h, bytes, hipMemcpyHostToDevice, copy));
       }
-      G16_HIP(hipEventRecord(copied[s].e, copy.s));
-      G16_HIP(hipStreamWaitEvent(comp.s, copied[s].e, 0));
+      stage.staged();
       if (it.kind == CCK_G2) {
-        G16_LAUNCH(k_cc_g2, nb, KC_BLOCK, 0, comp.s, (const VkDev*)dvk.p, (const G2Affine*)dv, n, dflags.p);
+        G16_LAUNCH(k_chk_flags_g2, nb, KC_BLOCK, 0, comp, (const VkDev*)stage.dvk.p, (const G2Affine*)dv, n, 1u, flags);
       } else {
-        G16_LAUNCH(k_cc_g1, nb, KC_BLOCK, 0, comp.s, (const G1Affine*)dv, n, dflags.p);
+        G16_LAUNCH(k_chk_flags_g1, nb, KC_BLOCK, 0, comp, (const G1Affine*)dv, n, flags);
       }
       if (it.kind == CCK_PAIR) {
-        G16_LAUNCH(k_cc_rho, dim3(nb, 2), KC_BLOCK, 0, comp.s, (const G1Affine*)(dv + off_before), (const G1Affine*)dv,
-                   (const uint64_t*)(dv + off_rho), (const uint8_t*)dflags.p, n, dpart.p);
-        G16_LAUNCH(k_cc_fold, 1, KC_BLOCK, 0, comp.s, (const G1XYZZ*)dpart.p, nb, it.q, dst.p);
+        G16_LAUNCH(k_cc_rho, dim3(nb, 2), KC_BLOCK, 0, comp, (const G1Affine*)(dv + off_before), (const G1Affine*)dv,
+                   (const uint64_t*)(dv + off_rho), (const uint8_t*)flags, n, dpart.p);
+        G16_LAUNCH(k_chk_fold<G1XYZZ>, 1, KC_BLOCK, 0, comp, (const G1XYZZ*)dpart.p, nb, 2u, dst.p->sum[it.q]);
       }
-      G16_LAUNCH(k_cc_collect, 1, KC_SCAN, 0, comp.s, (const uint8_t*)dflags.p, n, it.q, it.base, dst.p, dlists.p, cap);
-      G16_HIP(hipEventRecord(done[s].e, comp.s));
+      stage.collect(flags, n, it.q, CC_QUERY_ID[it.q], it.base, &dst.p->tally);
+      stage.end();
     }
-    G16_LAUNCH(k_cc_final, 1, KC_BLOCK, 0, comp.s, (const VkDev*)dvk.p, (const CcKey*)dkey.p, dst.p,
-               (const g16_key_bad_point*)dlists.p, cap, mismatch, dout.p);
-    G16_HIP(hipGetLastError());
-    G16_HIP(hipStreamSynchronize(comp.s));  // the one synchronisation before the download
-    G16_HIP(hipMemcpy(hs.get(), dst.p, sizeof(CcState), hipMemcpyDeviceToHost));
-    *report = hs->report;
-    if (report->n_listed)
-      G16_HIP(hipMemcpy(bad_out, dout.p, (size_t)report->n_listed * sizeof(g16_key_bad_point), hipMemcpyDeviceToHost));
+    G16_LAUNCH(k_cc_final, 1, KC_BLOCK, 0, comp, (const VkDev*)stage.dvk.p, (const CcKey*)dkey.p, dst.p,
+               (const g16_key_bad_point*)stage.dlists.p, stage.cap, mismatch, stage.dout.p);
+    stage.finish(hs.get(), dst.p, report, bad_out);
     return G16_OK;
   } catch (const HipError&) {
     return G16_ERR_HIP;

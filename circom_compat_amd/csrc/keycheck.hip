@@ -14,22 +14,18 @@
 //                hold the same scalars (the small-exponent test g16_verify_aggregate uses for proofs).
 //                Miller loop and final exponentiation are those of pairing.h.
 //
-// The queries are STREAMED: two page-locked host slots and two device slots of `chunk` points; the host
-// fills slot k + 1 and its copy runs while the kernels of slot k do.  Device memory is fixed by the chunk,
-// not by the key.  Per chunk:
-//   k_kc_g1 / k_kc_g2   one reason byte per point
-//   k_kc_rho            (B chunks) rho_i B1_i and rho_i B2_i per lane, per-block sums through LDS trees
-//   k_kc_fold           one block: the chunk's block sums into the running sums of the call
-//   k_kc_collect        one block: counts the flags and appends the bad points, in index order, to the
-//                       query's list (a scan, no atomics: the list does not depend on scheduling)
+// The queries are STREAMED through the CheckStage of keycheck.h: two page-locked host slots and two device slots
+// of `chunk` points; the host fills slot k + 1 and its copy runs while the kernels of slot k do.  Device memory
+// is fixed by the chunk, not by the key.  Per chunk:
+//   k_chk_flags_g1 / _g2  one reason byte per point
+//   k_kc_rho              (B chunks) rho_i B1_i and rho_i B2_i per lane, per-block sums through LDS trees
+//   k_kc_fold             one block: the chunk's block sums into the running sums of the call
+//   k_chk_collect         one block: counts the flags and appends the bad points, in index order, to the
+//                         query's list
 // and once at the end
-//   k_kc_final          six Miller loops in six lanes, three final exponentiations in three, then the report
-//                       and the bad-point list, concatenated in (query, index) order, assembled on the device.
+//   k_kc_final            six Miller loops in six lanes, three final exponentiations in three, then the report
+//                         and the bad-point list, concatenated in (query, index) order, assembled on the device.
 // One synchronisation precedes the download of the report and the list.
-#include <stdlib.h>
-
-#include <memory>
-
 #include "keycheck.h"
 
 namespace g16 {
@@ -44,24 +40,11 @@ struct KcKey {  // the six pairs of the three relations
 };
 
 struct KcState {  // device-resident for the whole call
-  uint64_t n_points[G16_KEY_N_QUERIES], n_bad[G16_KEY_N_QUERIES], n_infinity[G16_KEY_N_QUERIES];
-  uint32_t n_list[G16_KEY_N_QUERIES];  // entries in the query's list (<= cap)
-  G1XYZZ sum_b1;                       // sum rho_i B1_i so far
-  G2XYZZ sum_b2;                       // sum rho_i B2_i so far
+  CheckTally tally;
+  G1XYZZ sum_b1;  // sum rho_i B1_i so far
+  G2XYZZ sum_b2;  // sum rho_i B2_i so far
   g16_key_report report;
 };
-
-__global__ void __launch_bounds__(KC_BLOCK) k_kc_g1(const G1Affine* pts, uint32_t n, uint8_t* flags) {
-  const uint32_t i = blockIdx.x * KC_BLOCK + threadIdx.x;
-  if (i >= n) return;
-  flags[i] = g1_flag(pts[i]);
-}
-
-__global__ void __launch_bounds__(KC_BLOCK) k_kc_g2(const VkDev* vk, const G2Affine* pts, uint32_t n, uint8_t* flags) {
-  const uint32_t i = blockIdx.x * KC_BLOCK + threadIdx.x;
-  if (i >= n) return;
-  flags[i] = g2_flag(pts[i], vk);
-}
 
 // blockIdx.y = 0: part1[block] = sum over the block of rho_i B1_i; 1: part2[block] = the same over B2.
 // A malformed point is left out: the relations are not reported then anyway.
@@ -90,98 +73,21 @@ __global__ void __launch_bounds__(KC_BLOCK) k_kc_rho(const G1Affine* b1, const G
 __global__ void __launch_bounds__(KC_BLOCK) k_kc_fold(const G1XYZZ* part1, const G2XYZZ* part2, uint32_t nb, KcState* st) {
   __shared__ G1XYZZ sh1[KC_BLOCK];
   __shared__ G2XYZZ sh2[KC_BLOCK];
-  const uint32_t t = threadIdx.x;
-  G1XYZZ a1 = G1XYZZ::infinity();
-  G2XYZZ a2 = G2XYZZ::infinity();
-#pragma unroll 1
-  for (uint32_t k = t; k < nb; k += KC_BLOCK) {
-    a1.add(part1[k]);
-    a2.add(part2[k]);
-  }
-  kc_block_sum(sh1, a1);
-  kc_block_sum(sh2, a2);
-  if (t == 0) {
-    G1XYZZ s1 = st->sum_b1;
-    s1.add(sh1[0]);
-    st->sum_b1 = s1;
-    G2XYZZ s2 = st->sum_b2;
-    s2.add(sh2[0]);
-    st->sum_b2 = s2;
-  }
-}
-
-// one block: lane t owns the contiguous run [t * seg, (t + 1) * seg) of the chunk's flags; counts, an exclusive
-// scan of the counts, then every lane appends its bad points behind those of the lanes before it
-__global__ void __launch_bounds__(KC_SCAN) k_kc_collect(const uint8_t* flags, uint32_t n, uint32_t query, uint32_t base,
-                                                        KcState* st, g16_key_bad_point* lists, uint32_t cap) {
-  __shared__ uint32_t sh_bad[KC_SCAN], sh_inf[KC_SCAN];
-  __shared__ uint32_t sh_start;
-  const uint32_t t = threadIdx.x;
-  const uint32_t seg = (n + KC_SCAN - 1) / KC_SCAN;
-  const uint32_t lo = t * seg < n ? t * seg : n, hi = lo + seg < n ? lo + seg : n;
-  uint32_t bad = 0, inf = 0;
-#pragma unroll 1
-  for (uint32_t i = lo; i < hi; ++i) {
-    const uint8_t f = flags[i];
-    bad += (f & ~KC_INF) ? 1 : 0;
-    inf += (f == KC_INF) ? 1 : 0;
-  }
-  sh_bad[t] = bad;
-  sh_inf[t] = inf;
-  __syncthreads();
-  if (t == 0) {
-    uint32_t run = 0, infs = 0;
-#pragma unroll 1
-    for (uint32_t k = 0; k < KC_SCAN; ++k) {
-      const uint32_t c = sh_bad[k];
-      sh_bad[k] = run;
-      run += c;
-      infs += sh_inf[k];
-    }
-    const uint32_t start = st->n_list[query];
-    sh_start = start;
-    st->n_bad[query] += run;
-    st->n_infinity[query] += infs;
-    st->n_list[query] = (uint64_t)start + run < cap ? start + run : cap;
-  }
-  __syncthreads();
-  uint64_t at = (uint64_t)sh_start + sh_bad[t];
-  g16_key_bad_point* list = lists + (size_t)query * cap;
-#pragma unroll 1
-  for (uint32_t i = lo; i < hi && bad && at < cap; ++i) {
-    const uint8_t f = flags[i] & ~KC_INF;
-    if (!f) continue;
-    list[at].query = query;
-    list[at].index = base + i;
-    list[at].reason = f;
-    ++at;
-  }
+  chk_fold(part1, nb, &st->sum_b1, sh1);
+  chk_fold(part2, nb, &st->sum_b2, sh2);
 }
 
 // lanes 0..5: the Miller loops  ML(g2, beta_g1) ML(beta_g2, -g1) | ML(g2, delta_g1) ML(delta_g2, -g1) |
 // ML(g2, sum rho B1) ML(sum rho B2, -g1); lanes 0..2: product and final exponentiation of one pair each;
 // then the report and the list.  Nothing is paired when a structural check failed.
 __global__ void __launch_bounds__(KC_BLOCK) k_kc_final(const VkDev* vk, const KcKey* key, KcState* st,
-                                                       const g16_key_bad_point* lists, uint32_t cap, uint32_t bad_cap,
+                                                       const g16_key_bad_point* lists, uint32_t cap,
                                                        uint32_t vk_mismatch, g16_key_bad_point* out_list) {
   __shared__ F12 sh[6];
   __shared__ uint32_t sh_fail[3];
-  __shared__ uint32_t sh_any, sh_off[G16_KEY_N_QUERIES + 1];
+  __shared__ uint32_t sh_off[G16_KEY_N_QUERIES + 2];
   const uint32_t t = threadIdx.x;
-  if (t == 0) {
-    uint64_t bad = 0;
-    uint32_t off = 0;
-    for (int q = 0; q < G16_KEY_N_QUERIES; ++q) {
-      bad += st->n_bad[q];
-      sh_off[q] = off;
-      const uint32_t room = bad_cap - off;
-      off += st->n_list[q] < room ? st->n_list[q] : room;
-    }
-    sh_off[G16_KEY_N_QUERIES] = off;
-    sh_any = bad ? 1 : 0;
-  }
-  __syncthreads();
-  const bool pair = !sh_any;
+  const bool pair = !chk_offsets(&st->tally, G16_KEY_N_QUERIES, cap, sh_off);
   G2Affine Q = G2Affine::infinity();
   G1Affine P = G1Affine::infinity();
   if (pair && t < 6) {
@@ -193,40 +99,18 @@ __global__ void __launch_bounds__(KC_BLOCK) k_kc_final(const VkDev* vk, const Kc
       P = t == 0 ? key->beta_g1 : t == 2 ? key->delta_g1 : st->sum_b1.to_affine();
     }
   }
-  F12 f = f12_one();
-  miller_mul(&f, &Q, &P, vk);  // one call site: infinity on either side (every idle lane) returns at once
-  if (t < 6) sh[t] = f;
-  __syncthreads();
-  if (t < 3) {
-    bool one = true;
-    if (pair) {
-      F12 g;
-      f12_mul(&g, &sh[2 * t], &sh[2 * t + 1]);
-      one = final_exp_is_one(&g, vk);
-    }
-    sh_fail[t] = one ? 0 : (1u << t);  // G16_KEY_PAIR_BETA, _DELTA, _B
-  }
-  __syncthreads();
+  const uint32_t failed = chk_pairs(Q, P, 3, pair, vk, sh, sh_fail);  // bits G16_KEY_PAIR_BETA, _DELTA, _B
   if (t == 0) {
     g16_key_report r;
     memset(&r, 0, sizeof r);
     r.relations_checked = pair ? 1 : 0;
-    r.relations_failed = pair ? (sh_fail[0] | sh_fail[1] | sh_fail[2] | (vk_mismatch ? G16_KEY_VK_MISMATCH : 0)) : 0;
+    r.relations_failed = pair ? (failed | (vk_mismatch ? G16_KEY_VK_MISMATCH : 0)) : 0;
     r.ok = (pair && !r.relations_failed) ? 1 : 0;
-    for (int q = 0; q < G16_KEY_N_QUERIES; ++q) {
-      r.n_points[q] = st->n_points[q];
-      r.n_bad[q] = st->n_bad[q];
-      r.n_infinity[q] = st->n_infinity[q];
-    }
+    chk_counts(&r, &st->tally, G16_KEY_N_QUERIES);
     r.n_listed = sh_off[G16_KEY_N_QUERIES];
     st->report = r;
   }
-#pragma unroll 1
-  for (int q = 0; q < G16_KEY_N_QUERIES; ++q) {
-    const uint32_t cnt = sh_off[q + 1] - sh_off[q];
-#pragma unroll 1
-    for (uint32_t k = t; k < cnt; k += KC_BLOCK) out_list[sh_off[q] + k] = lists[(size_t)q * cap + k];
-  }
+  chk_emit_lists(sh_off, G16_KEY_N_QUERIES, lists, cap, out_list);
 }
 
 // ---- host side -------------------------------------------------------------------------------------
@@ -262,25 +146,14 @@ extern "C" g16_status g16_key_check(int device, const g16_key_desc* key, const g
   if (!key->a_query || !key->b_g1_query || !key->b_g2_query || (n_l && !key->l_query) || (dom && !key->h_query))
     return G16_ERR_INVALID;
   if (vk && (!vk->ic || vk->ic_count < 1)) return G16_ERR_INVALID;
-  if (rho)
-    for (uint64_t i = 0; i < N; ++i)
-      if (!(rho[2 * i] | rho[2 * i + 1])) return G16_ERR_INVALID;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return G16_ERR_NO_DEVICE;
-  if (device < 0 || device >= ndev) return G16_ERR_INVALID;
+  if (!rho_all_nonzero(rho, N)) return G16_ERR_INVALID;
+  if (const g16_status ds = device_ok(device)) return ds;
   try {
-    // G16_KEYCHECK_CHUNK=<points> (tests): points per staged chunk; never more than the longest query needs
     uint64_t longest = N > dom ? N : dom;
     if (vk && vk->ic_count > longest) longest = vk->ic_count;
     if (longest < 3) longest = 3;  // the single points
-    uint32_t chunk = KC_DEFAULT_CHUNK;
-    if (const char* e = getenv("G16_KEYCHECK_CHUNK")) {
-      const unsigned long long v = strtoull(e, nullptr, 0);
-      if (v >= 1 && v <= (1ull << 24)) chunk = (uint32_t)v;
-    }
-    if (chunk > longest) chunk = (uint32_t)longest;
+    const uint32_t chunk = chunk_from_env("G16_KEYCHECK_CHUNK", KC_DEFAULT_CHUNK, longest);
     const uint32_t nb_max = ceil_div(chunk, KC_BLOCK);
-    const uint32_t cap = bad_cap < KC_MAX_LISTED ? bad_cap : KC_MAX_LISTED;
 
     // what the key and the verifying key must agree on: compared as bytes
     uint32_t vk_mismatch = 0;
@@ -307,13 +180,6 @@ extern "C" g16_status g16_key_check(int device, const g16_key_desc* key, const g
     add_items(items, KC_G2, G16_KEY_Q_SINGLES, singles_g2, nullptr, vk ? 3 : 2, chunk, 3);
 
     G16_HIP(hipSetDevice(device));
-    const HostConsts& H = host_consts();
-    std::unique_ptr<VkDev> hv(new VkDev());
-    memset(hv.get(), 0, sizeof(VkDev));
-    hv->frob_x = H.frob_x;
-    hv->frob_y = H.frob_y;
-    hv->b_twist = H.b_twist;
-    memcpy(hv->frob, H.frob, sizeof H.frob);
     KcKey hk;
     memcpy(&hk.beta_g1, key->beta_g1, 64);
     memcpy(&hk.delta_g1, key->delta_g1, 64);
@@ -323,51 +189,31 @@ extern "C" g16_status g16_key_check(int device, const g16_key_desc* key, const g
     memcpy(&hk.g2, G2_GEN_WORDS, 128);
     std::unique_ptr<KcState> hs(new KcState());
     memset(hs.get(), 0, sizeof(KcState));
-    hs->n_points[G16_KEY_Q_A] = hs->n_points[G16_KEY_Q_B1] = hs->n_points[G16_KEY_Q_B2] = N;
-    hs->n_points[G16_KEY_Q_L] = n_l;
-    hs->n_points[G16_KEY_Q_H] = dom;
-    hs->n_points[G16_KEY_Q_IC] = vk ? vk->ic_count : 0;
-    hs->n_points[G16_KEY_Q_SINGLES] = vk ? 6 : 5;
+    uint64_t* n_points = hs->tally.n_points;
+    n_points[G16_KEY_Q_A] = n_points[G16_KEY_Q_B1] = n_points[G16_KEY_Q_B2] = N;
+    n_points[G16_KEY_Q_L] = n_l;
+    n_points[G16_KEY_Q_H] = dom;
+    n_points[G16_KEY_Q_IC] = vk ? vk->ic_count : 0;
+    n_points[G16_KEY_Q_SINGLES] = vk ? 6 : 5;
 
-    // every allocation of the call: nothing is allocated inside the chunk loop
-    const size_t slot_bytes = (size_t)chunk * KC_SLOT_BYTES_PER_POINT;
-    PinnedBuf pin[2];
-    DevBuf<uint8_t> dslot[2], dflags;
-    DevBuf<VkDev> dvk;
+    CheckStage stage((size_t)chunk * KC_SLOT_BYTES_PER_POINT, 2 * (size_t)chunk, G16_KEY_N_QUERIES, bad_cap);
     DevBuf<KcKey> dkey;
     DevBuf<KcState> dst;
     DevBuf<G1XYZZ> dpart1;
     DevBuf<G2XYZZ> dpart2;
-    DevBuf<g16_key_bad_point> dlists, dout;
-    StreamBox copy, comp;
-    EventBox copied[2], done[2];
-    for (int s = 0; s < 2; ++s) {
-      pin[s].alloc(slot_bytes);
-      dslot[s].alloc(slot_bytes);
-      copied[s].create();
-      done[s].create();
-    }
-    dflags.alloc(2 * (size_t)chunk);
-    dvk.alloc(1);
     dkey.alloc(1);
     dst.alloc(1);
     dpart1.alloc(nb_max);
     dpart2.alloc(nb_max);
-    dlists.alloc((size_t)G16_KEY_N_QUERIES * (cap ? cap : 1));
-    dout.alloc(cap ? cap : 1);
-    copy.create();
-    comp.create();
-    G16_HIP(hipMemcpy(dvk.p, hv.get(), sizeof(VkDev), hipMemcpyHostToDevice));
     G16_HIP(hipMemcpy(dkey.p, &hk, sizeof hk, hipMemcpyHostToDevice));
     G16_HIP(hipMemcpy(dst.p, hs.get(), sizeof(KcState), hipMemcpyHostToDevice));
+    const hipStream_t copy = stage.copy.s, comp = stage.comp.s;
+    const VkDev* dvk = stage.dvk.p;
+    CheckTally* tally = &dst.p->tally;
 
     const size_t off_b1 = (size_t)chunk * 128, off_rho = (size_t)chunk * 192;
-    for (size_t k = 0; k < items.size(); ++k) {
-      const Item& it = items[k];
-      const int s = (int)(k & 1);
-      if (k >= 2) G16_HIP(hipEventSynchronize(done[s].e));  // the kernels that read this slot two chunks ago
-      uint8_t* h = pin[s].p;
-      uint8_t* d = dslot[s].p;
+    for (const Item& it : items) {
+      const auto [h, d] = stage.begin();
       const uint32_t n = it.count;
       if (it.kind == KC_B) {
         memcpy(h, it.src2, (size_t)n * 128);
@@ -375,59 +221,42 @@ extern "C" g16_status g16_key_check(int device, const g16_key_desc* key, const g
         uint64_t* hr = (uint64_t*)(h + off_rho);
         if (rho) {
           memcpy(hr, rho + 2 * (size_t)it.base, (size_t)n * 16);
-        } else {  // drawn chunk by chunk, straight into the staging slot
-          bool drawn = os_random(hr, (size_t)n * 16);
-          for (uint32_t i = 0; drawn && i < n; ++i)
-            while (drawn && !(hr[2 * (size_t)i] | hr[2 * (size_t)i + 1]))  // probability 2^-128 per entry
-              drawn = os_random(&hr[2 * (size_t)i], 16);
-          if (!drawn) {  // never a fixed fallback; the chunks in flight still read the slots
-            (void)hipStreamSynchronize(copy.s);
-            (void)hipStreamSynchronize(comp.s);
-            return G16_ERR_INTERNAL;
-          }
+        } else if (!draw_rho(hr, n)) {  // drawn chunk by chunk, straight into the staging slot
+          stage.drain();
+          return G16_ERR_INTERNAL;
         }
-        G16_HIP(hipMemcpyAsync(d, h, (size_t)n * 128, hipMemcpyHostToDevice, copy.s));
-        G16_HIP(hipMemcpyAsync(d + off_b1, h + off_b1, (size_t)n * 64, hipMemcpyHostToDevice, copy.s));
-        G16_HIP(hipMemcpyAsync(d + off_rho, h + off_rho, (size_t)n * 16, hipMemcpyHostToDevice, copy.s));
+        G16_HIP(hipMemcpyAsync(d, h, (size_t)n * 128, hipMemcpyHostToDevice, copy));
+        G16_HIP(hipMemcpyAsync(d + off_b1, h + off_b1, (size_t)n * 64, hipMemcpyHostToDevice, copy));
+        G16_HIP(hipMemcpyAsync(d + off_rho, h + off_rho, (size_t)n * 16, hipMemcpyHostToDevice, copy));
       } else {
         const size_t bytes = (size_t)n * (it.kind == KC_G2 ? 128 : 64);
         memcpy(h, it.src, bytes);
-        G16_HIP(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, copy.s));
+        G16_HIP(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, copy));
       }
-      G16_HIP(hipEventRecord(copied[s].e, copy.s));
-      G16_HIP(hipStreamWaitEvent(comp.s, copied[s].e, 0));
+      stage.staged();
       const uint32_t nb = ceil_div(n, KC_BLOCK);
-      if (it.kind == KC_G1) {
-        G16_LAUNCH(k_kc_g1, nb, KC_BLOCK, 0, comp.s, (const G1Affine*)d, n, dflags.p);
-        G16_LAUNCH(k_kc_collect, 1, KC_SCAN, 0, comp.s, (const uint8_t*)dflags.p, n, it.query, it.base, dst.p,
-                   dlists.p, cap);
-      } else if (it.kind == KC_G2) {
-        G16_LAUNCH(k_kc_g2, nb, KC_BLOCK, 0, comp.s, (const VkDev*)dvk.p, (const G2Affine*)d, n, dflags.p);
-        G16_LAUNCH(k_kc_collect, 1, KC_SCAN, 0, comp.s, (const uint8_t*)dflags.p, n, it.query, it.base, dst.p,
-                   dlists.p, cap);
-      } else {
-        uint8_t* f1 = dflags.p;
-        uint8_t* f2 = dflags.p + chunk;
-        G16_LAUNCH(k_kc_g1, nb, KC_BLOCK, 0, comp.s, (const G1Affine*)(d + off_b1), n, f1);
-        G16_LAUNCH(k_kc_g2, nb, KC_BLOCK, 0, comp.s, (const VkDev*)dvk.p, (const G2Affine*)d, n, f2);
-        G16_LAUNCH(k_kc_rho, dim3(nb, 2), KC_BLOCK, 0, comp.s, (const G1Affine*)(d + off_b1), (const G2Affine*)d,
+      uint8_t* f1 = stage.dflags.p;
+      uint8_t* f2 = f1 + chunk;
+      if (it.kind == KC_B) {
+        G16_LAUNCH(k_chk_flags_g1, nb, KC_BLOCK, 0, comp, (const G1Affine*)(d + off_b1), n, f1);
+        G16_LAUNCH(k_chk_flags_g2, nb, KC_BLOCK, 0, comp, dvk, (const G2Affine*)d, n, 1u, f2);
+        G16_LAUNCH(k_kc_rho, dim3(nb, 2), KC_BLOCK, 0, comp, (const G1Affine*)(d + off_b1), (const G2Affine*)d,
                    (const uint64_t*)(d + off_rho), (const uint8_t*)f1, (const uint8_t*)f2, n, dpart1.p, dpart2.p);
-        G16_LAUNCH(k_kc_fold, 1, KC_BLOCK, 0, comp.s, (const G1XYZZ*)dpart1.p, (const G2XYZZ*)dpart2.p, nb, dst.p);
-        G16_LAUNCH(k_kc_collect, 1, KC_SCAN, 0, comp.s, (const uint8_t*)f1, n, (uint32_t)G16_KEY_Q_B1, it.base,
-                   dst.p, dlists.p, cap);
-        G16_LAUNCH(k_kc_collect, 1, KC_SCAN, 0, comp.s, (const uint8_t*)f2, n, (uint32_t)G16_KEY_Q_B2, it.base,
-                   dst.p, dlists.p, cap);
+        G16_LAUNCH(k_kc_fold, 1, KC_BLOCK, 0, comp, (const G1XYZZ*)dpart1.p, (const G2XYZZ*)dpart2.p, nb, dst.p);
+        stage.collect(f1, n, G16_KEY_Q_B1, G16_KEY_Q_B1, it.base, tally);
+        stage.collect(f2, n, G16_KEY_Q_B2, G16_KEY_Q_B2, it.base, tally);
+      } else {
+        if (it.kind == KC_G2)
+          G16_LAUNCH(k_chk_flags_g2, nb, KC_BLOCK, 0, comp, dvk, (const G2Affine*)d, n, 1u, f1);
+        else
+          G16_LAUNCH(k_chk_flags_g1, nb, KC_BLOCK, 0, comp, (const G1Affine*)d, n, f1);
+        stage.collect(f1, n, it.query, it.query, it.base, tally);
       }
-      G16_HIP(hipEventRecord(done[s].e, comp.s));
+      stage.end();
     }
-    G16_LAUNCH(k_kc_final, 1, KC_BLOCK, 0, comp.s, (const VkDev*)dvk.p, (const KcKey*)dkey.p, dst.p,
-               (const g16_key_bad_point*)dlists.p, cap, cap, vk_mismatch, dout.p);
-    G16_HIP(hipGetLastError());
-    G16_HIP(hipStreamSynchronize(comp.s));  // the one synchronisation before the download
-    G16_HIP(hipMemcpy(hs.get(), dst.p, sizeof(KcState), hipMemcpyDeviceToHost));
-    *report = hs->report;
-    if (report->n_listed)
-      G16_HIP(hipMemcpy(bad_out, dout.p, (size_t)report->n_listed * sizeof(g16_key_bad_point), hipMemcpyDeviceToHost));
+    G16_LAUNCH(k_kc_final, 1, KC_BLOCK, 0, comp, dvk, (const KcKey*)dkey.p, dst.p,
+               (const g16_key_bad_point*)stage.dlists.p, stage.cap, vk_mismatch, stage.dout.p);
+    stage.finish(hs.get(), dst.p, report, bad_out);
     return G16_OK;
   } catch (const HipError&) {
     return G16_ERR_HIP;

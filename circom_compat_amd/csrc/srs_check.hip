@@ -11,9 +11,9 @@
 //                e(Hi(P), g2) = e(Lo(P), tau_g2[1]) for the three G1 arrays and e(tau_g1[1], Lo(P)) = e(g1, Hi(P))
 //                for tau_g2; the two bases and beta_g2 are tied by three single pairings.
 //
-// The arrays are STREAMED exactly as in keycheck.hip: two page-locked host slots and two device slots of `chunk`
-// points, the copy of chunk k + 1 under the kernels of chunk k.  Per chunk:
-//   k_sc_g1 / k_sc_g2            one reason byte per point
+// The arrays are STREAMED through the CheckStage of keycheck.h: two page-locked host slots and two device slots of
+// `chunk` points, the copy of chunk k + 1 under the kernels of chunk k.  Per chunk:
+//   k_chk_flags_g1 / _g2         one reason byte per point
 //   k_sc_pair_g1 / k_sc_pair_g2  the shifted sums.  Point P[j] enters Lo with rho_j and Hi with rho_{j-1}: one
 //                                lane per point, the point fetched ONCE, both products from one LSB-first chain
 //                                (the running double 2^b P is added into either accumulator: 128 doublings and
@@ -23,16 +23,12 @@
 //                                rho_{base - 1 + k}, so a chunk seam needs nothing but the overlap of one
 //                                coefficient, and the zero entries in front of the first and behind the last point
 //                                of an array keep those two points out of Hi / Lo.
-//   k_sc_fold_g1 / k_sc_fold_g2  one block: the chunk's block sums into the running sums of the call
-//   k_sc_collect                 one block: counts the flags and appends the bad points in index order (a scan)
+//   k_chk_fold                   one block: the chunk's block sums into the running sums of the call
+//   k_chk_collect                one block: counts the flags and appends the bad points in index order (a scan)
 // and once at the end
 //   k_sc_final                   twelve Miller loops in twelve lanes, six final exponentiations in six, then the
 //                                report and the bad-point list assembled on the device.
 // One synchronisation precedes the download of the report and the list.  No atomics anywhere.
-#include <stdlib.h>
-
-#include <memory>
-
 #include "keycheck.h"
 
 namespace g16 {
@@ -47,24 +43,11 @@ struct ScKey {  // the fixed points of the six pairs
 };
 
 struct ScState {  // device-resident for the whole call
-  uint64_t n_points[G16_SRS_N_QUERIES], n_bad[G16_SRS_N_QUERIES], n_infinity[G16_SRS_N_QUERIES];
-  uint32_t n_list[G16_SRS_N_QUERIES];  // entries in the query's list (<= cap)
-  G1XYZZ sum1[SC_N_G1][2];             // [tau_g1, alpha_tau_g1, beta_tau_g1][Lo, Hi] so far
-  G2XYZZ sum2[2];                      // tau_g2: Lo, Hi so far
+  CheckTally tally;
+  G1XYZZ sum1[SC_N_G1][2];  // [tau_g1, alpha_tau_g1, beta_tau_g1][Lo, Hi] so far
+  G2XYZZ sum2[2];           // tau_g2: Lo, Hi so far
   g16_srs_report report;
 };
-
-__global__ void __launch_bounds__(KC_BLOCK) k_sc_g1(const G1Affine* pts, uint32_t n, uint8_t* flags) {
-  const uint32_t i = blockIdx.x * KC_BLOCK + threadIdx.x;
-  if (i >= n) return;
-  flags[i] = g1_flag(pts[i]);
-}
-
-__global__ void __launch_bounds__(KC_BLOCK) k_sc_g2(const VkDev* vk, const G2Affine* pts, uint32_t n, uint8_t* flags) {
-  const uint32_t i = blockIdx.x * KC_BLOCK + threadIdx.x;
-  if (i >= n) return;
-  flags[i] = g2_flag(pts[i], vk);
-}
 
 // part[block] = sum over the block of rho[i + 1] P_i (the chunk's share of Lo), part[nb + block] = the same with
 // rho[i] (of Hi); rho has n + 1 entries of 2 x u64, a zero entry contributes nothing.  D runs through P, 2P, 4P,
@@ -138,83 +121,6 @@ __global__ void __launch_bounds__(KC_BLOCK) k_sc_pair_g2_sliced(const G2Affine* 
   sc_pair_sliced<Fq2>(pts, rho, flags, n, part, sh);
 }
 
-// one block: the chunk's 2 x nb block sums into the two running sums `sum` points at
-template <class F>
-__device__ __forceinline__ void sc_fold(const XYZZ<F>* part, uint32_t nb, XYZZ<F>* sum, XYZZ<F>* sh) {
-  const uint32_t t = threadIdx.x;
-#pragma unroll 1
-  for (uint32_t side = 0; side < 2; ++side) {
-    XYZZ<F> a = XYZZ<F>::infinity();
-#pragma unroll 1
-    for (uint32_t k = t; k < nb; k += KC_BLOCK) a.add(part[side * nb + k]);
-    kc_block_sum(sh, a);
-    if (t == 0) {
-      XYZZ<F> s = sum[side];
-      s.add(sh[0]);
-      sum[side] = s;
-    }
-    __syncthreads();
-  }
-}
-
-__global__ void __launch_bounds__(KC_BLOCK) k_sc_fold_g1(const G1XYZZ* part, uint32_t nb, uint32_t which, ScState* st) {
-  __shared__ G1XYZZ sh[KC_BLOCK];
-  sc_fold<Fq>(part, nb, st->sum1[which], sh);
-}
-
-__global__ void __launch_bounds__(KC_BLOCK) k_sc_fold_g2(const G2XYZZ* part, uint32_t nb, ScState* st) {
-  __shared__ G2XYZZ sh[KC_BLOCK];
-  sc_fold<Fq2>(part, nb, st->sum2, sh);
-}
-
-// k_kc_collect of keycheck.hip on this call's state: lane t owns a contiguous run of the chunk's flags; counts,
-// an exclusive scan, then every lane appends its bad points behind those of the lanes before it
-__global__ void __launch_bounds__(KC_SCAN) k_sc_collect(const uint8_t* flags, uint32_t n, uint32_t query, uint32_t base,
-                                                        ScState* st, g16_key_bad_point* lists, uint32_t cap) {
-  __shared__ uint32_t sh_bad[KC_SCAN], sh_inf[KC_SCAN];
-  __shared__ uint32_t sh_start;
-  const uint32_t t = threadIdx.x;
-  const uint32_t seg = (n + KC_SCAN - 1) / KC_SCAN;
-  const uint32_t lo = t * seg < n ? t * seg : n, hi = lo + seg < n ? lo + seg : n;
-  uint32_t bad = 0, inf = 0;
-#pragma unroll 1
-  for (uint32_t i = lo; i < hi; ++i) {
-    const uint8_t f = flags[i];
-    bad += (f & ~KC_INF) ? 1 : 0;
-    inf += (f == KC_INF) ? 1 : 0;
-  }
-  sh_bad[t] = bad;
-  sh_inf[t] = inf;
-  __syncthreads();
-  if (t == 0) {
-    uint32_t run = 0, infs = 0;
-#pragma unroll 1
-    for (uint32_t k = 0; k < KC_SCAN; ++k) {
-      const uint32_t c = sh_bad[k];
-      sh_bad[k] = run;
-      run += c;
-      infs += sh_inf[k];
-    }
-    const uint32_t start = st->n_list[query];
-    sh_start = start;
-    st->n_bad[query] += run;
-    st->n_infinity[query] += infs;
-    st->n_list[query] = (uint64_t)start + run < cap ? start + run : cap;
-  }
-  __syncthreads();
-  uint64_t at = (uint64_t)sh_start + sh_bad[t];
-  g16_key_bad_point* list = lists + (size_t)query * cap;
-#pragma unroll 1
-  for (uint32_t i = lo; i < hi && bad && at < cap; ++i) {
-    const uint8_t f = flags[i] & ~KC_INF;
-    if (!f) continue;
-    list[at].query = query;
-    list[at].index = base + i;
-    list[at].reason = f;
-    ++at;
-  }
-}
-
 // lanes 2k, 2k + 1: the two Miller loops of pair k; lanes 0..5: product and final exponentiation of pair k
 //   0 PAIR_TAU      ML(g2, tau_g1[1])        ML(tau_g2[1], -g1)
 //   1 PAIR_TAU_G1   ML(g2, Hi(tau_g1))       ML(tau_g2[1], -Lo(tau_g1))
@@ -228,22 +134,9 @@ __global__ void __launch_bounds__(KC_BLOCK) k_sc_final(const VkDev* vk, const Sc
                                                        g16_key_bad_point* out_list) {
   __shared__ F12 sh[12];
   __shared__ uint32_t sh_fail[6];
-  __shared__ uint32_t sh_any, sh_off[G16_SRS_N_QUERIES + 1];
+  __shared__ uint32_t sh_off[G16_SRS_N_QUERIES + 2];
   const uint32_t t = threadIdx.x;
-  if (t == 0) {
-    uint64_t bad = 0;
-    uint32_t off = 0;
-    for (int q = 0; q < G16_SRS_N_QUERIES; ++q) {
-      bad += st->n_bad[q];
-      sh_off[q] = off;
-      const uint32_t room = cap - off;
-      off += st->n_list[q] < room ? st->n_list[q] : room;
-    }
-    sh_off[G16_SRS_N_QUERIES] = off;
-    sh_any = bad ? 1 : 0;
-  }
-  __syncthreads();
-  const bool pair = !sh_any;
+  const bool pair = !chk_offsets(&st->tally, G16_SRS_N_QUERIES, cap, sh_off);
   G2Affine Q = G2Affine::infinity();
   G1Affine P = G1Affine::infinity();
   if (pair && t < 12) {
@@ -264,43 +157,19 @@ __global__ void __launch_bounds__(KC_BLOCK) k_sc_final(const VkDev* vk, const Sc
       if (second) P = P.neg();
     }
   }
-  F12 f = f12_one();
-  miller_mul(&f, &Q, &P, vk);  // one call site: infinity on either side (every idle lane) returns at once
-  if (t < 12) sh[t] = f;
-  __syncthreads();
-  if (t < 6) {
-    bool one = true;
-    if (pair) {
-      F12 g;
-      f12_mul(&g, &sh[2 * t], &sh[2 * t + 1]);
-      one = final_exp_is_one(&g, vk);
-    }
-    sh_fail[t] = one ? 0 : ((uint32_t)G16_SRS_PAIR_TAU << t);  // _TAU, _TAU_G1, _TAU_G2, _ALPHA, _BETA, _BETA_G2
-  }
-  __syncthreads();
+  const uint32_t failed = chk_pairs(Q, P, 6, pair, vk, sh, sh_fail);
   if (t == 0) {
     g16_srs_report r;
     memset(&r, 0, sizeof r);
     r.relations_checked = pair ? 1 : 0;
-    if (pair) {
-      r.relations_failed = host_bits;
-      for (int k = 0; k < 6; ++k) r.relations_failed |= sh_fail[k];
-    }
+    // pairs 0 .. 5: G16_SRS_PAIR_TAU, _TAU_G1, _TAU_G2, _ALPHA, _BETA, _BETA_G2
+    if (pair) r.relations_failed = host_bits | failed * G16_SRS_PAIR_TAU;
     r.ok = (pair && !r.relations_failed) ? 1 : 0;
-    for (int q = 0; q < G16_SRS_N_QUERIES; ++q) {
-      r.n_points[q] = st->n_points[q];
-      r.n_bad[q] = st->n_bad[q];
-      r.n_infinity[q] = st->n_infinity[q];
-    }
+    chk_counts(&r, &st->tally, G16_SRS_N_QUERIES);
     r.n_listed = sh_off[G16_SRS_N_QUERIES];
     st->report = r;
   }
-#pragma unroll 1
-  for (int q = 0; q < G16_SRS_N_QUERIES; ++q) {
-    const uint32_t cnt = sh_off[q + 1] - sh_off[q];
-#pragma unroll 1
-    for (uint32_t k = t; k < cnt; k += KC_BLOCK) out_list[sh_off[q] + k] = lists[(size_t)q * cap + k];
-  }
+  chk_emit_lists(sh_off, G16_SRS_N_QUERIES, lists, cap, out_list);
 }
 
 // ---- host side -------------------------------------------------------------------------------------
@@ -341,26 +210,14 @@ extern "C" g16_status g16_srs_check(int device, const g16_srs_desc* srs, const u
   const uint64_t n1 = srs->n_tau_g1, n2 = srs->n_tau;
   if (n1 < 2 || n2 < 2) return G16_ERR_INVALID;
   const uint64_t n_rho = (n1 - 1) + 3 * (n2 - 1);
-  if (rho)
-    for (uint64_t i = 0; i < n_rho; ++i)
-      if (!(rho[2 * i] | rho[2 * i + 1])) return G16_ERR_INVALID;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return G16_ERR_NO_DEVICE;
-  if (device < 0 || device >= ndev) return G16_ERR_INVALID;
+  if (!rho_all_nonzero(rho, n_rho)) return G16_ERR_INVALID;
+  if (const g16_status ds = device_ok(device)) return ds;
   try {
-    // G16_SRSCHECK_CHUNK=<points> (tests): points per staged chunk; never more than the longest array needs
-    const uint64_t longest = n1 > n2 ? n1 : n2;
-    uint32_t chunk = SC_DEFAULT_CHUNK;
-    if (const char* e = getenv("G16_SRSCHECK_CHUNK")) {
-      const unsigned long long v = strtoull(e, nullptr, 0);
-      if (v >= 1 && v <= (1ull << 24)) chunk = (uint32_t)v;
-    }
-    if (chunk > longest) chunk = (uint32_t)longest;
+    const uint32_t chunk = chunk_from_env("G16_SRSCHECK_CHUNK", SC_DEFAULT_CHUNK, n1 > n2 ? n1 : n2);
     // G16_SRSCHECK_SLICED=1 (measurements): the shifted sums as two ladders in two blockIdx.y slices
     const char* sl = getenv("G16_SRSCHECK_SLICED");
     const bool sliced = sl && sl[0] == '1';
     const uint32_t nb_max = ceil_div(chunk, KC_BLOCK);
-    const uint32_t cap = bad_cap < KC_MAX_LISTED ? bad_cap : KC_MAX_LISTED;
 
     // what needs no arithmetic: compared as bytes on the host, reported with the relations
     const G1Affine g1{Fq::one(), Fq::from_u32(2)};
@@ -383,13 +240,6 @@ extern "C" g16_status g16_srs_check(int device, const g16_srs_desc* srs, const u
     add_items(items, true, false, G16_SRS_Q_SINGLES, 0, srs->beta_g2, 1, nullptr, chunk);
 
     G16_HIP(hipSetDevice(device));
-    const HostConsts& H = host_consts();
-    std::unique_ptr<VkDev> hv(new VkDev());
-    memset(hv.get(), 0, sizeof(VkDev));
-    hv->frob_x = H.frob_x;
-    hv->frob_y = H.frob_y;
-    hv->b_twist = H.b_twist;
-    memcpy(hv->frob, H.frob, sizeof H.frob);
     ScKey hk;
     memcpy(&hk.tau1, srs->tau_g1 + 64, 64);
     memcpy(&hk.beta1, srs->beta_tau_g1, 64);
@@ -399,54 +249,33 @@ extern "C" g16_status g16_srs_check(int device, const g16_srs_desc* srs, const u
     memcpy(&hk.g2, G2_GEN_WORDS, 128);
     std::unique_ptr<ScState> hs(new ScState());
     memset(hs.get(), 0, sizeof(ScState));
-    hs->n_points[G16_SRS_Q_TAU_G1] = n1;
-    hs->n_points[G16_SRS_Q_TAU_G2] = hs->n_points[G16_SRS_Q_ALPHA_TAU_G1] = hs->n_points[G16_SRS_Q_BETA_TAU_G1] = n2;
-    hs->n_points[G16_SRS_Q_SINGLES] = 1;
+    uint64_t* n_points = hs->tally.n_points;
+    n_points[G16_SRS_Q_TAU_G1] = n1;
+    n_points[G16_SRS_Q_TAU_G2] = n_points[G16_SRS_Q_ALPHA_TAU_G1] = n_points[G16_SRS_Q_BETA_TAU_G1] = n2;
+    n_points[G16_SRS_Q_SINGLES] = 1;
 
-    // every allocation of the call: nothing is allocated inside the chunk loop
     const size_t off_rho = (size_t)chunk * 128;  // a slot: points | chunk + 1 coefficients
-    const size_t slot_bytes = off_rho + ((size_t)chunk + 1) * 16;
-    PinnedBuf pin[2];
-    DevBuf<uint8_t> dslot[2], dflags;
-    DevBuf<VkDev> dvk;
+    CheckStage stage(off_rho + ((size_t)chunk + 1) * 16, chunk, G16_SRS_N_QUERIES, bad_cap);
     DevBuf<ScKey> dkey;
     DevBuf<ScState> dst;
     DevBuf<G1XYZZ> dpart1;
     DevBuf<G2XYZZ> dpart2;
-    DevBuf<g16_key_bad_point> dlists, dout;
-    StreamBox copy, comp;
-    EventBox copied[2], done[2];
-    for (int s = 0; s < 2; ++s) {
-      pin[s].alloc(slot_bytes);
-      dslot[s].alloc(slot_bytes);
-      copied[s].create();
-      done[s].create();
-    }
-    dflags.alloc(chunk);
-    dvk.alloc(1);
     dkey.alloc(1);
     dst.alloc(1);
     dpart1.alloc(2 * (size_t)nb_max);
     dpart2.alloc(2 * (size_t)nb_max);
-    dlists.alloc((size_t)G16_SRS_N_QUERIES * (cap ? cap : 1));
-    dout.alloc(cap ? cap : 1);
-    copy.create();
-    comp.create();
-    G16_HIP(hipMemcpy(dvk.p, hv.get(), sizeof(VkDev), hipMemcpyHostToDevice));
     G16_HIP(hipMemcpy(dkey.p, &hk, sizeof hk, hipMemcpyHostToDevice));
     G16_HIP(hipMemcpy(dst.p, hs.get(), sizeof(ScState), hipMemcpyHostToDevice));
+    const hipStream_t copy = stage.copy.s, comp = stage.comp.s;
+    uint8_t* flags = stage.dflags.p;
 
     uint64_t carry[2] = {0, 0};  // drawn rho: the last coefficient of the chunk before, the first of this one's
-    for (size_t k = 0; k < items.size(); ++k) {
-      const Item& it = items[k];
-      const int s = (int)(k & 1);
-      if (k >= 2) G16_HIP(hipEventSynchronize(done[s].e));  // the kernels that read this slot two chunks ago
-      uint8_t* h = pin[s].p;
-      uint8_t* d = dslot[s].p;
+    for (const Item& it : items) {
+      const auto [h, d] = stage.begin();
       const uint32_t n = it.count;
       const size_t bytes = (size_t)n * (it.g2 ? 128 : 64);
       memcpy(h, it.src, bytes);
-      G16_HIP(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, copy.s));
+      G16_HIP(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, copy));
       if (it.sums) {
         // entry e of the slot = rho_{base - 1 + e}, e <= n; rho_{-1} = rho_{total - 1} = 0
         uint64_t* hr = (uint64_t*)(h + off_rho);
@@ -464,56 +293,45 @@ extern "C" g16_status g16_srs_check(int device, const g16_srs_desc* srs, const u
             hr[1] = carry[1];
             from = 1;
           }
-          bool drawn = last < from || os_random(hr + 2 * from, (size_t)(last - from + 1) * 16);
-          for (uint64_t i = from; drawn && i <= last; ++i)
-            while (drawn && !(hr[2 * i] | hr[2 * i + 1])) drawn = os_random(&hr[2 * i], 16);  // probability 2^-128
-          if (!drawn) {  // never a fixed fallback; the chunks in flight still read the slots
-            (void)hipStreamSynchronize(copy.s);
-            (void)hipStreamSynchronize(comp.s);
+          if (last >= from && !draw_rho(hr + 2 * from, (size_t)(last - from + 1))) {
+            stage.drain();
             return G16_ERR_INTERNAL;
           }
           carry[0] = hr[2 * (size_t)n];
           carry[1] = hr[2 * (size_t)n + 1];
         }
-        G16_HIP(hipMemcpyAsync(d + off_rho, h + off_rho, ((size_t)n + 1) * 16, hipMemcpyHostToDevice, copy.s));
+        G16_HIP(hipMemcpyAsync(d + off_rho, h + off_rho, ((size_t)n + 1) * 16, hipMemcpyHostToDevice, copy));
       }
-      G16_HIP(hipEventRecord(copied[s].e, copy.s));
-      G16_HIP(hipStreamWaitEvent(comp.s, copied[s].e, 0));
+      stage.staged();
       const uint32_t nb = ceil_div(n, KC_BLOCK);
       const uint64_t* drho = (const uint64_t*)(d + off_rho);
       if (it.g2) {
-        G16_LAUNCH(k_sc_g2, nb, KC_BLOCK, 0, comp.s, (const VkDev*)dvk.p, (const G2Affine*)d, n, dflags.p);
+        G16_LAUNCH(k_chk_flags_g2, nb, KC_BLOCK, 0, comp, (const VkDev*)stage.dvk.p, (const G2Affine*)d, n, 1u, flags);
         if (it.sums) {
           if (sliced)
-            G16_LAUNCH(k_sc_pair_g2_sliced, dim3(nb, 2), KC_BLOCK, 0, comp.s, (const G2Affine*)d, drho,
-                       (const uint8_t*)dflags.p, n, dpart2.p);
+            G16_LAUNCH(k_sc_pair_g2_sliced, dim3(nb, 2), KC_BLOCK, 0, comp, (const G2Affine*)d, drho,
+                       (const uint8_t*)flags, n, dpart2.p);
           else
-            G16_LAUNCH(k_sc_pair_g2, nb, KC_BLOCK, 0, comp.s, (const G2Affine*)d, drho, (const uint8_t*)dflags.p, n,
+            G16_LAUNCH(k_sc_pair_g2, nb, KC_BLOCK, 0, comp, (const G2Affine*)d, drho, (const uint8_t*)flags, n,
                        dpart2.p);
-          G16_LAUNCH(k_sc_fold_g2, 1, KC_BLOCK, 0, comp.s, (const G2XYZZ*)dpart2.p, nb, dst.p);
+          G16_LAUNCH(k_chk_fold<G2XYZZ>, 1, KC_BLOCK, 0, comp, (const G2XYZZ*)dpart2.p, nb, 2u, dst.p->sum2);
         }
       } else {
-        G16_LAUNCH(k_sc_g1, nb, KC_BLOCK, 0, comp.s, (const G1Affine*)d, n, dflags.p);
+        G16_LAUNCH(k_chk_flags_g1, nb, KC_BLOCK, 0, comp, (const G1Affine*)d, n, flags);
         if (sliced)
-          G16_LAUNCH(k_sc_pair_g1_sliced, dim3(nb, 2), KC_BLOCK, 0, comp.s, (const G1Affine*)d, drho,
-                     (const uint8_t*)dflags.p, n, dpart1.p);
+          G16_LAUNCH(k_sc_pair_g1_sliced, dim3(nb, 2), KC_BLOCK, 0, comp, (const G1Affine*)d, drho,
+                     (const uint8_t*)flags, n, dpart1.p);
         else
-          G16_LAUNCH(k_sc_pair_g1, nb, KC_BLOCK, 0, comp.s, (const G1Affine*)d, drho, (const uint8_t*)dflags.p, n,
+          G16_LAUNCH(k_sc_pair_g1, nb, KC_BLOCK, 0, comp, (const G1Affine*)d, drho, (const uint8_t*)flags, n,
                      dpart1.p);
-        G16_LAUNCH(k_sc_fold_g1, 1, KC_BLOCK, 0, comp.s, (const G1XYZZ*)dpart1.p, nb, it.which, dst.p);
+        G16_LAUNCH(k_chk_fold<G1XYZZ>, 1, KC_BLOCK, 0, comp, (const G1XYZZ*)dpart1.p, nb, 2u, dst.p->sum1[it.which]);
       }
-      G16_LAUNCH(k_sc_collect, 1, KC_SCAN, 0, comp.s, (const uint8_t*)dflags.p, n, it.query, it.base, dst.p, dlists.p,
-                 cap);
-      G16_HIP(hipEventRecord(done[s].e, comp.s));
+      stage.collect(flags, n, it.query, it.query, it.base, &dst.p->tally);
+      stage.end();
     }
-    G16_LAUNCH(k_sc_final, 1, KC_BLOCK, 0, comp.s, (const VkDev*)dvk.p, (const ScKey*)dkey.p, dst.p,
-               (const g16_key_bad_point*)dlists.p, cap, host_bits, dout.p);
-    G16_HIP(hipGetLastError());
-    G16_HIP(hipStreamSynchronize(comp.s));  // the one synchronisation before the download
-    G16_HIP(hipMemcpy(hs.get(), dst.p, sizeof(ScState), hipMemcpyDeviceToHost));
-    *report = hs->report;
-    if (report->n_listed)
-      G16_HIP(hipMemcpy(bad_out, dout.p, (size_t)report->n_listed * sizeof(g16_key_bad_point), hipMemcpyDeviceToHost));
+    G16_LAUNCH(k_sc_final, 1, KC_BLOCK, 0, comp, (const VkDev*)stage.dvk.p, (const ScKey*)dkey.p, dst.p,
+               (const g16_key_bad_point*)stage.dlists.p, stage.cap, host_bits, stage.dout.p);
+    stage.finish(hs.get(), dst.p, report, bad_out);
     return G16_OK;
   } catch (const HipError&) {
     return G16_ERR_HIP;

@@ -11,21 +11,17 @@
 //   k_lc_rho_fr + ntt29_dif + k_lc_accum   C = sum_p iNTT_{2^p}(rho^(p)): the level's 128-bit coefficients as Fr,
 //                                the inverse Fr transform of the witness map (ntt29.h, 1/2^p fused), and the
 //                                bit-reversed result added into C[0 .. 2^p)
-//   k_lc_flags_g1 / _g2          one reason byte per point: the predicates of keycheck.h (monomial G2 points: canonical
+//   k_chk_flags_g1 / _g2         one reason byte per point: the predicates of keycheck.h (monomial G2 points: canonical
 //                                and on the curve only -- the string is expected to have passed g16_srs_check)
 //   k_lc_rho                     Lagrange side: one lane per point, rho P by a 128-step double-and-add of mixed
 //                                additions on the lazy limbs of ec29.h, then the block's sum (kc_block_sum)
 //   k_lc_coeff                   monomial side: one lane per point, C_i P by a NAF ladder over the full width
-//   k_lc_fold                    one block: the chunk's block sums into the running sum of the side
-//   k_lc_collect                 one block: counts the flags, appends the bad points in index order (a scan)
+//   k_chk_fold                   one block: the chunk's block sums into the running sum of the side
+//   k_chk_collect                one block: counts the flags, appends the bad points in index order (a scan)
 // and once at the end k_lc_final: the two sums of every array compared as group elements (their difference is the
-// point at infinity), the report and the bad-point list assembled on the device.  The arrays are STREAMED as in
-// srs_check.hip: two page-locked host slots and two device slots of `chunk` points, the copy of chunk k + 1 under
-// the kernels of chunk k.  One synchronisation precedes the download of the report.  No atomics anywhere.
-#include <stdlib.h>
-
-#include <memory>
-
+// point at infinity), the report and the bad-point list assembled on the device.  The arrays are STREAMED through
+// the CheckStage of keycheck.h: two page-locked host slots and two device slots of `chunk` points, the copy of chunk
+// k + 1 under the kernels of chunk k.  One synchronisation precedes the download of the report.  No atomics anywhere.
 #include "gtransform.h"
 #include "keycheck.h"
 #include "ntt29.h"
@@ -39,37 +35,11 @@ constexpr uint32_t LC_N = G16_LAGRANGE_N_ARRAYS;
 thread_local float t_prepare_ms[7];  // the phases of g16_setup_from_srs_times
 
 struct LcState {  // device-resident for the whole call
-  uint64_t n_points[LC_N], n_bad[LC_N], n_infinity[LC_N];
-  uint32_t n_list[LC_N];
+  CheckTally tally;
   G1XYZZ29 sum1[3][2];  // [tau_g1, alpha_tau_g1, beta_tau_g1][Lagrange side, monomial side]
   G2XYZZ29 sum2[2];
   g16_srs_lagrange_report report;
 };
-
-__global__ void __launch_bounds__(KC_BLOCK) k_lc_flags_g1(const G1Affine* pts, uint32_t n, uint8_t* flags) {
-  const uint32_t i = blockIdx.x * KC_BLOCK + threadIdx.x;
-  if (i >= n) return;
-  flags[i] = g1_flag(pts[i]);
-}
-
-// subgroup = 0 (monomial points): canonical words and the curve equation only
-__global__ void __launch_bounds__(KC_BLOCK) k_lc_flags_g2(const VkDev* vk, const G2Affine* pts, uint32_t n,
-                                                          uint32_t subgroup, uint8_t* flags) {
-  const uint32_t i = blockIdx.x * KC_BLOCK + threadIdx.x;
-  if (i >= n) return;
-  const G2Affine p = pts[i];
-  uint8_t f;
-  if (subgroup) {
-    f = g2_flag(p, vk);
-  } else if (!(fq2_words_canonical(p.x) && fq2_words_canonical(p.y))) {
-    f = G16_KEY_BAD_NONCANONICAL;
-  } else if (p.is_inf()) {
-    f = KC_INF;
-  } else {
-    f = on_curve_g2(p, vk) ? 0 : G16_KEY_BAD_OFF_CURVE;
-  }
-  flags[i] = f;
-}
 
 // part[block] = sum over the block of rho_i P_i, rho_i = rho[2i] + 2^64 rho[2i + 1].  A malformed or infinite
 // point is left out (the relations are not reported when a point is malformed).
@@ -124,69 +94,6 @@ __global__ void __launch_bounds__(KC_BLOCK) k_lc_coeff(const Affine<F>* pts, con
   if (t == 0) part[blockIdx.x] = sh[0];
 }
 
-// one block: *sum += the chunk's nb block sums
-template <class LF>
-__global__ void __launch_bounds__(KC_BLOCK) k_lc_fold(const XYZZ29<LF>* part, uint32_t nb, XYZZ29<LF>* sum) {
-  __shared__ XYZZ29<LF> sh[KC_BLOCK];
-  const uint32_t t = threadIdx.x;
-  XYZZ29<LF> a = XYZZ29<LF>::infinity();
-#pragma unroll 1
-  for (uint32_t k = t; k < nb; k += KC_BLOCK) a.add(part[k]);
-  kc_block_sum(sh, a);
-  if (t == 0) {
-    XYZZ29<LF> s = *sum;
-    s.add(sh[0]);
-    *sum = s;
-  }
-}
-
-// k_sc_collect of srs_check.hip on this call's state
-__global__ void __launch_bounds__(KC_SCAN) k_lc_collect(const uint8_t* flags, uint32_t n, uint32_t query, uint32_t base,
-                                                        LcState* st, g16_key_bad_point* lists, uint32_t cap) {
-  __shared__ uint32_t sh_bad[KC_SCAN], sh_inf[KC_SCAN];
-  __shared__ uint32_t sh_start;
-  const uint32_t t = threadIdx.x;
-  const uint32_t seg = (n + KC_SCAN - 1) / KC_SCAN;
-  const uint32_t lo = t * seg < n ? t * seg : n, hi = lo + seg < n ? lo + seg : n;
-  uint32_t bad = 0, inf = 0;
-#pragma unroll 1
-  for (uint32_t i = lo; i < hi; ++i) {
-    const uint8_t f = flags[i];
-    bad += (f & ~KC_INF) ? 1 : 0;
-    inf += (f == KC_INF) ? 1 : 0;
-  }
-  sh_bad[t] = bad;
-  sh_inf[t] = inf;
-  __syncthreads();
-  if (t == 0) {
-    uint32_t run = 0, infs = 0;
-#pragma unroll 1
-    for (uint32_t k = 0; k < KC_SCAN; ++k) {
-      const uint32_t c = sh_bad[k];
-      sh_bad[k] = run;
-      run += c;
-      infs += sh_inf[k];
-    }
-    const uint32_t start = st->n_list[query];
-    sh_start = start;
-    st->n_bad[query] += run;
-    st->n_infinity[query] += infs;
-    st->n_list[query] = (uint64_t)start + run < cap ? start + run : cap;
-  }
-  __syncthreads();
-  uint64_t at = (uint64_t)sh_start + sh_bad[t];
-  g16_key_bad_point* list = lists + (size_t)query * cap;
-#pragma unroll 1
-  for (uint32_t i = lo; i < hi && bad && at < cap; ++i) {
-    const uint8_t f = flags[i] & ~KC_INF;
-    if (!f) continue;
-    list[at].query = query;
-    list[at].index = base + i;
-    list[at].reason = f;
-    ++at;
-  }
-}
-
 // rho (2 x u64, a plain integer < 2^128) -> Montgomery Fr
 __global__ void __launch_bounds__(256) k_lc_rho_fr(const uint64_t* rho, uint32_t n, Fr* out) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -205,18 +112,9 @@ __global__ void __launch_bounds__(256) k_lc_accum(const Fr* v, uint32_t n, int k
 // the sums of each array compared (their difference is the point at infinity), then the report and the list
 __global__ void __launch_bounds__(KC_BLOCK) k_lc_final(LcState* st, const g16_key_bad_point* lists, uint32_t cap,
                                                        g16_key_bad_point* out_list) {
-  __shared__ uint32_t sh_off[LC_N + 1];
-  const uint32_t t = threadIdx.x;
-  if (t == 0) {
-    uint64_t bad = 0;
-    uint32_t off = 0;
-    for (uint32_t q = 0; q < LC_N; ++q) {
-      bad += st->n_bad[q];
-      sh_off[q] = off;
-      const uint32_t room = cap - off;
-      off += st->n_list[q] < room ? st->n_list[q] : room;
-    }
-    sh_off[LC_N] = off;
+  __shared__ uint32_t sh_off[LC_N + 2];
+  const bool bad = chk_offsets(&st->tally, LC_N, cap, sh_off);
+  if (threadIdx.x == 0) {
     g16_srs_lagrange_report r;
     memset(&r, 0, sizeof r);
     r.relations_checked = bad ? 0 : 1;
@@ -232,21 +130,11 @@ __global__ void __launch_bounds__(KC_BLOCK) k_lc_final(LcState* st, const g16_ke
       if (!d2.is_inf()) r.relations_failed |= 1u << G16_SRS_Q_TAU_G2;
     }
     r.ok = (!bad && !r.relations_failed) ? 1 : 0;
-    for (uint32_t q = 0; q < LC_N; ++q) {
-      r.n_points[q] = st->n_points[q];
-      r.n_bad[q] = st->n_bad[q];
-      r.n_infinity[q] = st->n_infinity[q];
-    }
-    r.n_listed = off;
+    chk_counts(&r, &st->tally, LC_N);
+    r.n_listed = sh_off[LC_N];
     st->report = r;
   }
-  __syncthreads();
-#pragma unroll 1
-  for (uint32_t q = 0; q < LC_N; ++q) {
-    const uint32_t cnt = sh_off[q + 1] - sh_off[q];
-#pragma unroll 1
-    for (uint32_t k = t; k < cnt; k += KC_BLOCK) out_list[sh_off[q] + k] = lists[(size_t)q * cap + k];
-  }
+  chk_emit_lists(sh_off, LC_N, lists, cap, out_list);
 }
 
 struct LcArray {
@@ -272,9 +160,7 @@ g16_status g16_srs_prepare(int device, const g16_srs_desc* srs, uint32_t power, 
   if (!srs->tau_g1 || !srs->tau_g2 || !srs->alpha_tau_g1 || !srs->beta_tau_g1) return G16_ERR_INVALID;
   const uint32_t nP = 1u << power, n_top = 2 * nP;
   if ((uint64_t)srs->n_tau_g1 < (uint64_t)n_top - 1 || srs->n_tau < nP) return G16_ERR_INVALID;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return G16_ERR_NO_DEVICE;
-  if (device < 0 || device >= ndev) return G16_ERR_INVALID;
+  if (const g16_status ds = device_ok(device)) return ds;
   try {
     G16_HIP(hipSetDevice(device));
     hipStream_t s = nullptr;
@@ -351,23 +237,11 @@ g16_status g16_srs_lagrange_check(int device, const g16_srs_desc* srs, const g16
   const uint64_t nP = (uint64_t)1 << P, n_top = 2 * nP;
   if ((uint64_t)srs->n_tau_g1 < n_top - 1 || srs->n_tau < nP) return G16_ERR_INVALID;
   const uint64_t m1 = 2 * n_top - 1, m2 = n_top - 1;  // points of section 12 / of sections 13-15
-  const uint64_t n_rho = m1 + 3 * m2;
-  if (rho)
-    for (uint64_t i = 0; i < n_rho; ++i)
-      if (!(rho[2 * i] | rho[2 * i + 1])) return G16_ERR_INVALID;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return G16_ERR_NO_DEVICE;
-  if (device < 0 || device >= ndev) return G16_ERR_INVALID;
+  if (!rho_all_nonzero(rho, m1 + 3 * m2)) return G16_ERR_INVALID;
+  if (const g16_status ds = device_ok(device)) return ds;
   try {
-    // G16_LAGCHECK_CHUNK=<points> (tests): points per staged chunk; never more than the longest array needs
-    uint32_t chunk = LC_DEFAULT_CHUNK;
-    if (const char* e = getenv("G16_LAGCHECK_CHUNK")) {
-      const unsigned long long v = strtoull(e, nullptr, 0);
-      if (v >= 1 && v <= (1ull << 24)) chunk = (uint32_t)v;
-    }
-    if (chunk > m1) chunk = (uint32_t)m1;
+    const uint32_t chunk = chunk_from_env("G16_LAGCHECK_CHUNK", LC_DEFAULT_CHUNK, m1);
     const uint32_t nb_max = ceil_div(chunk, KC_BLOCK);
-    const uint32_t cap = bad_cap < KC_MAX_LISTED ? bad_cap : KC_MAX_LISTED;
 
     const LcArray arrays[LC_N] = {
         {false, G16_SRS_Q_TAU_G1, 0, (int)P + 1, lag->tau_g1, srs->tau_g1, n_top - 1},
@@ -376,58 +250,33 @@ g16_status g16_srs_lagrange_check(int device, const g16_srs_desc* srs, const g16
         {false, G16_SRS_Q_BETA_TAU_G1, 2, (int)P, lag->beta_tau_g1, srs->beta_tau_g1, nP}};
 
     G16_HIP(hipSetDevice(device));
-    const HostConsts& H = host_consts();
-    std::unique_ptr<VkDev> hv(new VkDev());
-    memset(hv.get(), 0, sizeof(VkDev));
-    hv->frob_x = H.frob_x;
-    hv->frob_y = H.frob_y;
-    hv->b_twist = H.b_twist;
-    memcpy(hv->frob, H.frob, sizeof H.frob);
     std::unique_ptr<LcState> hs(new LcState());
     memset(hs.get(), 0, sizeof(LcState));
-    hs->n_points[G16_SRS_Q_TAU_G1] = m1;
-    hs->n_points[G16_SRS_Q_TAU_G2] = hs->n_points[G16_SRS_Q_ALPHA_TAU_G1] = hs->n_points[G16_SRS_Q_BETA_TAU_G1] = m2;
+    uint64_t* n_points = hs->tally.n_points;
+    n_points[G16_SRS_Q_TAU_G1] = m1;
+    n_points[G16_SRS_Q_TAU_G2] = n_points[G16_SRS_Q_ALPHA_TAU_G1] = n_points[G16_SRS_Q_BETA_TAU_G1] = m2;
 
     // every allocation of the call but the transform plans: nothing else is allocated inside the loops
     const size_t off_rho = (size_t)chunk * 128;  // a slot: points | chunk coefficients
-    const size_t slot_bytes = off_rho + (size_t)chunk * 16;
-    PinnedBuf pin[2];
-    DevBuf<uint8_t> dslot[2], dflags;
-    DevBuf<VkDev> dvk;
+    CheckStage stage(off_rho + (size_t)chunk * 16, chunk, LC_N, bad_cap);
     DevBuf<LcState> dst;
     DevBuf<G1XYZZ29> dpart1;
     DevBuf<G2XYZZ29> dpart2;
-    DevBuf<g16_key_bad_point> dlists, dout;
     DevBuf<Fr> dC, dv;
     DevBuf<uint64_t> drho_lvl;
     DevBuf<int32_t> dplanes;
-    StreamBox copy, comp;
-    EventBox copied[2], done[2];
-    for (int s = 0; s < 2; ++s) {
-      pin[s].alloc(slot_bytes);
-      dslot[s].alloc(slot_bytes);
-      copied[s].create();
-      done[s].create();
-    }
-    dflags.alloc(chunk);
-    dvk.alloc(1);
     dst.alloc(1);
     dpart1.alloc(nb_max);
     dpart2.alloc(nb_max);
-    dlists.alloc((size_t)LC_N * (cap ? cap : 1));
-    dout.alloc(cap ? cap : 1);
     dC.alloc(n_top);
     dv.alloc(n_top);
     drho_lvl.alloc(2 * n_top);
     dplanes.alloc((size_t)NTT29_LIMBS * n_top);
-    copy.create();
-    comp.create();
-    G16_HIP(hipMemcpy(dvk.p, hv.get(), sizeof(VkDev), hipMemcpyHostToDevice));
     G16_HIP(hipMemcpy(dst.p, hs.get(), sizeof(LcState), hipMemcpyHostToDevice));
+    const hipStream_t copy = stage.copy.s, comp = stage.comp.s;
 
     std::vector<uint64_t> drawn;  // the array's rho when the caller gave none
     const uint64_t* rho_at = rho;
-    size_t k = 0;                 // chunks staged so far: the slot is k & 1
     for (uint32_t a = 0; a < LC_N; ++a) {
       const LcArray& A = arrays[a];
       const uint64_t m = ((uint64_t)2 << A.top) - 1;
@@ -435,12 +284,8 @@ g16_status g16_srs_lagrange_check(int device, const g16_srs_desc* srs, const g16
       if (!rho) {
         // the slots in flight do not read `drawn`, but the level uploads below do: they are synchronous
         drawn.resize(2 * m);
-        bool ok = os_random(drawn.data(), (size_t)m * 16);
-        for (uint64_t i = 0; ok && i < m; ++i)
-          while (ok && !(drawn[2 * i] | drawn[2 * i + 1])) ok = os_random(&drawn[2 * i], 16);  // probability 2^-128
-        if (!ok) {  // never a fixed fallback; the chunks in flight still read the slots
-          (void)hipStreamSynchronize(copy.s);
-          (void)hipStreamSynchronize(comp.s);
+        if (!draw_rho(drawn.data(), (size_t)m)) {
+          stage.drain();
           return G16_ERR_INTERNAL;
         }
         r = drawn.data();
@@ -449,18 +294,18 @@ g16_status g16_srs_lagrange_check(int device, const g16_srs_desc* srs, const g16
       }
 
       // ---- C = sum_p iNTT_{2^p}(rho^(p)), on the compute stream behind the array before
-      G16_HIP(hipMemsetAsync(dC.p, 0, ((size_t)1 << A.top) * sizeof(Fr), comp.s));
+      G16_HIP(hipMemsetAsync(dC.p, 0, ((size_t)1 << A.top) * sizeof(Fr), comp));
       for (int p = 0; p <= A.top; ++p) {
         const uint32_t n = 1u << p;
         Ntt29Plan plan;
-        plan.build(p, comp.s);
-        G16_HIP(hipMemcpyAsync(drho_lvl.p, r + 2 * ((size_t)n - 1), (size_t)n * 16, hipMemcpyHostToDevice, comp.s));
-        G16_LAUNCH(k_lc_rho_fr, ceil_div(n, 256), 256, 0, comp.s, (const uint64_t*)drho_lvl.p, n, dv.p);
-        ntt29_to_planes(dv.p, dplanes.p, n, comp.s);
-        ntt29_dif(plan, dplanes.p, (size_t)NTT29_LIMBS * n, 1, true, NTT_FUSE_SCALE, comp.s);
-        ntt29_from_planes(dplanes.p, dv.p, n, comp.s);
-        G16_LAUNCH(k_lc_accum, ceil_div(n, 256), 256, 0, comp.s, (const Fr*)dv.p, n, p, dC.p);
-        G16_HIP(hipStreamSynchronize(comp.s));  // the plan's tables are released at the end of this scope
+        plan.build(p, comp);
+        G16_HIP(hipMemcpyAsync(drho_lvl.p, r + 2 * ((size_t)n - 1), (size_t)n * 16, hipMemcpyHostToDevice, comp));
+        G16_LAUNCH(k_lc_rho_fr, ceil_div(n, 256), 256, 0, comp, (const uint64_t*)drho_lvl.p, n, dv.p);
+        ntt29_to_planes(dv.p, dplanes.p, n, comp);
+        ntt29_dif(plan, dplanes.p, (size_t)NTT29_LIMBS * n, 1, true, NTT_FUSE_SCALE, comp);
+        ntt29_from_planes(dplanes.p, dv.p, n, comp);
+        G16_LAUNCH(k_lc_accum, ceil_div(n, 256), 256, 0, comp, (const Fr*)dv.p, n, p, dC.p);
+        G16_HIP(hipStreamSynchronize(comp));  // the plan's tables are released at the end of this scope
       }
 
       // ---- the two sides: the Lagrange section under rho, then the monomial array under C
@@ -468,57 +313,49 @@ g16_status g16_srs_lagrange_check(int device, const g16_srs_desc* srs, const g16
         const uint64_t total = side ? A.n_mono : m;
         const uint8_t* src = side ? A.mono : A.lag;
         const size_t w = A.g2 ? 128 : 64;
-        for (uint64_t base = 0; base < total; base += chunk, ++k) {
+        for (uint64_t base = 0; base < total; base += chunk) {
           const uint32_t n = (uint32_t)(total - base < chunk ? total - base : chunk);
-          const int s = (int)(k & 1);
-          if (k >= 2) G16_HIP(hipEventSynchronize(done[s].e));  // the kernels that read this slot two chunks ago
-          uint8_t* h = pin[s].p;
-          uint8_t* d = dslot[s].p;
+          const auto [h, d] = stage.begin();
           memcpy(h, src + base * w, (size_t)n * w);
-          G16_HIP(hipMemcpyAsync(d, h, (size_t)n * w, hipMemcpyHostToDevice, copy.s));
+          G16_HIP(hipMemcpyAsync(d, h, (size_t)n * w, hipMemcpyHostToDevice, copy));
           if (!side) {
             memcpy(h + off_rho, r + 2 * base, (size_t)n * 16);
-            G16_HIP(hipMemcpyAsync(d + off_rho, h + off_rho, (size_t)n * 16, hipMemcpyHostToDevice, copy.s));
+            G16_HIP(hipMemcpyAsync(d + off_rho, h + off_rho, (size_t)n * 16, hipMemcpyHostToDevice, copy));
           }
-          G16_HIP(hipEventRecord(copied[s].e, copy.s));
-          G16_HIP(hipStreamWaitEvent(comp.s, copied[s].e, 0));
+          stage.staged();
           const uint32_t nb = ceil_div(n, KC_BLOCK);
           const uint64_t* drho = (const uint64_t*)(d + off_rho);
-          const uint8_t* fl = dflags.p;
+          const uint8_t* fl = stage.dflags.p;
           if (A.g2) {
-            G16_LAUNCH(k_lc_flags_g2, nb, KC_BLOCK, 0, comp.s, (const VkDev*)dvk.p, (const G2Affine*)d, n,
-                       (uint32_t)(side ? 0 : 1), dflags.p);
+            G16_LAUNCH(k_chk_flags_g2, nb, KC_BLOCK, 0, comp, (const VkDev*)stage.dvk.p, (const G2Affine*)d, n,
+                       (uint32_t)(side ? 0 : 1), stage.dflags.p);  // monomial points: no subgroup test
             if (side)
-              G16_LAUNCH((k_lc_coeff<Fq2>), nb, KC_BLOCK, 0, comp.s, (const G2Affine*)d, (const Fr*)(dC.p + base), fl,
-                         n, dpart2.p);
+              G16_LAUNCH((k_lc_coeff<Fq2>), nb, KC_BLOCK, 0, comp, (const G2Affine*)d, (const Fr*)(dC.p + base), fl, n,
+                         dpart2.p);
             else
-              G16_LAUNCH((k_lc_rho<Fq2>), nb, KC_BLOCK, 0, comp.s, (const G2Affine*)d, drho, fl, n, dpart2.p);
-            G16_LAUNCH((k_lc_fold<Fq2x29>), 1, KC_BLOCK, 0, comp.s, (const G2XYZZ29*)dpart2.p, nb,
+              G16_LAUNCH((k_lc_rho<Fq2>), nb, KC_BLOCK, 0, comp, (const G2Affine*)d, drho, fl, n, dpart2.p);
+            G16_LAUNCH(k_chk_fold<G2XYZZ29>, 1, KC_BLOCK, 0, comp, (const G2XYZZ29*)dpart2.p, nb, 1u,
                        &dst.p->sum2[side]);
           } else {
-            G16_LAUNCH(k_lc_flags_g1, nb, KC_BLOCK, 0, comp.s, (const G1Affine*)d, n, dflags.p);
+            G16_LAUNCH(k_chk_flags_g1, nb, KC_BLOCK, 0, comp, (const G1Affine*)d, n, stage.dflags.p);
             if (side)
-              G16_LAUNCH((k_lc_coeff<Fq>), nb, KC_BLOCK, 0, comp.s, (const G1Affine*)d, (const Fr*)(dC.p + base), fl,
-                         n, dpart1.p);
+              G16_LAUNCH((k_lc_coeff<Fq>), nb, KC_BLOCK, 0, comp, (const G1Affine*)d, (const Fr*)(dC.p + base), fl, n,
+                         dpart1.p);
             else
-              G16_LAUNCH((k_lc_rho<Fq>), nb, KC_BLOCK, 0, comp.s, (const G1Affine*)d, drho, fl, n, dpart1.p);
-            G16_LAUNCH((k_lc_fold<Fq29>), 1, KC_BLOCK, 0, comp.s, (const G1XYZZ29*)dpart1.p, nb,
+              G16_LAUNCH((k_lc_rho<Fq>), nb, KC_BLOCK, 0, comp, (const G1Affine*)d, drho, fl, n, dpart1.p);
+            G16_LAUNCH(k_chk_fold<G1XYZZ29>, 1, KC_BLOCK, 0, comp, (const G1XYZZ29*)dpart1.p, nb, 1u,
                        &dst.p->sum1[A.which][side]);
           }
           if (!side)  // only the Lagrange points are counted and listed
-            G16_LAUNCH(k_lc_collect, 1, KC_SCAN, 0, comp.s, fl, n, A.query, (uint32_t)base, dst.p, dlists.p, cap);
-          G16_HIP(hipEventRecord(done[s].e, comp.s));
+            stage.collect(fl, n, A.query, A.query, (uint32_t)base, &dst.p->tally);
+          stage.end();
         }
       }
       // `drawn` is overwritten for the next array: every copy out of it (pinned slots, level uploads) is done
     }
-    G16_LAUNCH(k_lc_final, 1, KC_BLOCK, 0, comp.s, dst.p, (const g16_key_bad_point*)dlists.p, cap, dout.p);
-    G16_HIP(hipGetLastError());
-    G16_HIP(hipStreamSynchronize(comp.s));  // the one synchronisation before the download
-    G16_HIP(hipMemcpy(hs.get(), dst.p, sizeof(LcState), hipMemcpyDeviceToHost));
-    *report = hs->report;
-    if (report->n_listed)
-      G16_HIP(hipMemcpy(bad_out, dout.p, (size_t)report->n_listed * sizeof(g16_key_bad_point), hipMemcpyDeviceToHost));
+    G16_LAUNCH(k_lc_final, 1, KC_BLOCK, 0, comp, dst.p, (const g16_key_bad_point*)stage.dlists.p, stage.cap,
+               stage.dout.p);
+    stage.finish(hs.get(), dst.p, report, bad_out);
     return G16_OK;
   } catch (const HipError&) {
     return G16_ERR_HIP;

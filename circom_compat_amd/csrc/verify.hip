@@ -21,6 +21,7 @@
 
 #include <memory>
 
+#include "keycheck.h"
 #include "pairing.h"
 #include "verify_agg.h"
 
@@ -266,13 +267,10 @@ extern "C" g16_status g16_verify_batch(int device, const g16_vk_desc* vk, const 
   if (!vk || !vk->ic || vk->ic_count < 1 || (n_proofs && (!proofs || !ok_out))) return G16_ERR_INVALID;
   const uint32_t n_pub = vk->ic_count - 1;
   if (n_proofs && n_pub && !public_inputs) return G16_ERR_INVALID;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return G16_ERR_NO_DEVICE;
-  if (device < 0 || device >= ndev) return G16_ERR_INVALID;
+  if (const g16_status ds = device_ok(device)) return ds;
   if (!n_proofs) return G16_OK;
   try {
     G16_HIP(hipSetDevice(device));
-    const HostConsts& H = host_consts();
     VkDev* hv = new VkDev();
     std::unique_ptr<VkDev> keep(hv);
     G1Affine alpha;
@@ -281,10 +279,7 @@ extern "C" g16_status g16_verify_batch(int device, const g16_vk_desc* vk, const 
     memcpy(&hv->beta, vk->beta_g2, 128);
     memcpy(&hv->gamma, vk->gamma_g2, 128);
     memcpy(&hv->delta, vk->delta_g2, 128);
-    hv->frob_x = H.frob_x;
-    hv->frob_y = H.frob_y;
-    hv->b_twist = H.b_twist;
-    memcpy(hv->frob, H.frob, sizeof H.frob);
+    vk_consts(hv);
     DevBuf<VkDev> dvk;
     DevBuf<G1Affine> dic;
     DevBuf<uint8_t> dproofs, dok;
@@ -322,9 +317,7 @@ extern "C" g16_status g16_verify_aggregate(int device, const g16_vk_desc* vk, co
   if (rho)
     for (uint32_t i = 0; i < n_proofs; ++i)
       if (!(rho[2 * (size_t)i] | rho[2 * (size_t)i + 1])) return G16_ERR_INVALID;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return G16_ERR_NO_DEVICE;
-  if (device < 0 || device >= ndev) return G16_ERR_INVALID;
+  if (const g16_status ds = device_ok(device)) return ds;
   if (!n_proofs) {
     *ok_out = 1;
     return G16_OK;
@@ -359,7 +352,6 @@ extern "C" g16_status g16_verify_aggregate(int device, const g16_vk_desc* vk, co
       }
     }
     G16_HIP(hipSetDevice(device));
-    const HostConsts& H = host_consts();
     std::unique_ptr<VkDev> hv(new VkDev());
     G1Affine alpha;
     memcpy(&alpha, vk->alpha_g1, 64);
@@ -367,10 +359,7 @@ extern "C" g16_status g16_verify_aggregate(int device, const g16_vk_desc* vk, co
     memcpy(&hv->beta, vk->beta_g2, 128);
     memcpy(&hv->gamma, vk->gamma_g2, 128);
     memcpy(&hv->delta, vk->delta_g2, 128);
-    hv->frob_x = H.frob_x;
-    hv->frob_y = H.frob_y;
-    hv->b_twist = H.b_twist;
-    memcpy(hv->frob, H.frob, sizeof H.frob);
+    vk_consts(hv.get());
     hv->ml_alpha_beta = f12_one();  // not used on this path (alpha is scaled by the sum of the coefficients)
     const uint32_t nb = ceil_div(n_proofs, AGG_BLOCK);                 // blocks of the per-proof front
     const uint32_t nbm = ceil_div((uint64_t)n_proofs + 3, AGG_BLOCK);  // blocks of the n + 3 Miller lanes

@@ -37,6 +37,7 @@
 
 #include <vector>
 
+#include "keycheck.h"
 #include "pairing.h"
 #include "verify_agg.h"
 
@@ -339,7 +340,6 @@ struct Plan {
 // rho: the coefficients of all proofs, or NULL on the per-proof path (rho_sum stays 0, no Miller blocks)
 void make_plan(Plan& pl, const g16_vk_desc* const* vks, const uint32_t* counts, uint32_t n_keys,
                const uint64_t* rho) {
-  const HostConsts& H = host_consts();
   pl.keys.resize(n_keys);
   pl.vks.resize(n_keys);
   uint64_t first = 0, ic_off = 0;
@@ -352,10 +352,7 @@ void make_plan(Plan& pl, const g16_vk_desc* const* vks, const uint32_t* counts, 
     memcpy(&hv.beta, vk->beta_g2, 128);
     memcpy(&hv.gamma, vk->gamma_g2, 128);
     memcpy(&hv.delta, vk->delta_g2, 128);
-    hv.frob_x = H.frob_x;
-    hv.frob_y = H.frob_y;
-    hv.b_twist = H.b_twist;
-    memcpy(hv.frob, H.frob, sizeof H.frob);
+    vk_consts(&hv);
     hv.ml_alpha_beta = f12_one();  // the per-proof path fills it in k_verifyk_prepare; the aggregate path does not use it
     pl.ic.insert(pl.ic.end(), vk->ic, vk->ic + (size_t)vk->ic_count * 64);
 
@@ -437,9 +434,7 @@ extern "C" g16_status g16_verify_batch_keys(int device, const g16_vk_desc* const
   uint64_t n = 0;
   if (check_groups(vks, counts, n_keys, proofs, public_inputs, &n) != G16_OK || (n && !ok_out))
     return G16_ERR_INVALID;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return G16_ERR_NO_DEVICE;
-  if (device < 0 || device >= ndev) return G16_ERR_INVALID;
+  if (const g16_status ds = device_ok(device)) return ds;
   if (!n) return G16_OK;
   try {
     G16_HIP(hipSetDevice(device));
@@ -474,9 +469,7 @@ extern "C" g16_status g16_verify_aggregate_keys(int device, const g16_vk_desc* c
   if (rho)
     for (uint64_t i = 0; i < n; ++i)
       if (!(rho[2 * i] | rho[2 * i + 1])) return G16_ERR_INVALID;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return G16_ERR_NO_DEVICE;
-  if (device < 0 || device >= ndev) return G16_ERR_INVALID;
+  if (const g16_status ds = device_ok(device)) return ds;
   if (!n_keys) return G16_OK;
   if (!n) {
     memset(ok_out, 1, n_keys);

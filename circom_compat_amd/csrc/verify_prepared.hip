@@ -208,11 +208,7 @@ struct GrowPinned {
 };
 
 void fill_consts(VkDev* hv) {
-  const HostConsts& H = host_consts();
-  hv->frob_x = H.frob_x;
-  hv->frob_y = H.frob_y;
-  hv->b_twist = H.b_twist;
-  memcpy(hv->frob, H.frob, sizeof H.frob);
+  vk_consts(hv);
   hv->ml_alpha_beta = f12_one();
 }
 
@@ -265,9 +261,9 @@ extern "C" g16_status g16_pvk_create(int device, const g16_vk_desc* vk, g16_pvk*
     set_create_error("g16_pvk_create: a NULL argument or a key without gamma_abc_g1");
     return G16_ERR_INVALID;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return G16_ERR_NO_DEVICE;
-  if (device < 0 || device >= ndev) {
+  const g16_status ds = device_ok(device);
+  if (ds == G16_ERR_NO_DEVICE) return ds;
+  if (ds != G16_OK) {
     set_create_error("g16_pvk_create: device out of range");
     return G16_ERR_INVALID;
   }
@@ -420,9 +416,7 @@ extern "C" g16_status g16_verify_prepared(g16_pvk* h, const uint8_t* proofs, con
 extern "C" g16_status g16_pairing_check(int device, const uint8_t* g1, const uint8_t* g2, uint32_t n_pairs,
                                         uint8_t* ok_out) {
   if (!g1 || !g2 || !ok_out || n_pairs < 1 || n_pairs > COOP_MAX_PAIRS) return G16_ERR_INVALID;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return G16_ERR_NO_DEVICE;
-  if (device < 0 || device >= ndev) return G16_ERR_INVALID;
+  if (const g16_status ds = device_ok(device)) return ds;
   try {
     G16_HIP(hipSetDevice(device));
     std::unique_ptr<VkDev> hv(new VkDev());
