@@ -47,7 +47,8 @@ __all__ = ["read_zkey", "R1CSFile", "R1CS", "CircomCircuit", "CircomBuilder", "C
            "rerandomize_times", "PreparedVerifyingKey", "prepare_verifying_key", "verify_prepared", "pairing_check",
            "verify_prepared_times", "Witness", "open_wtns", "write_wtns", "fr_from_canonical", "fr_from_canonical_times", "read_proof_json",
            "write_proof_json", "read_public_json", "write_public_json", "read_vk_json", "write_vk_json",
-           "inputs_to_eth", "solidity_calldata"]
+           "inputs_to_eth", "solidity_calldata", "GT", "gt_multiexp", "gt_from_ark", "gt_times", "pairing_products",
+           "pairing", "prepare_inputs", "verify_prepared_inputs"]
 
 FR_MODULUS = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 
@@ -2095,6 +2096,13 @@ class PreparedVerifyingKey:
         self.lib.check(self.lib.g16_pvk_alpha_beta(self._handle(), _np_ptr(out)))
         return out.tobytes()
 
+    def alpha_g1_beta_g2(self) -> "GT":
+        """e(alpha_g1, beta_g2), the field of arkworks' PreparedVerifyingKey and snarkjs' vk_alphabeta_12
+        (g16_pvk_alpha_g1_beta_g2: paired on first use, then kept in the handle)"""
+        out = np.zeros(384, dtype=np.uint8)
+        self.lib.check(self.lib.g16_pvk_alpha_g1_beta_g2(self._handle(), _np_ptr(out)))
+        return GT(out.tobytes(), self.lib, self.device)
+
     def _handle(self):
         if not self._ptr:
             raise G16Error(B.G16_ERR_INVALID, "the prepared verifying key is closed")
@@ -2162,6 +2170,253 @@ def pairing_check(g1_points, g2_points, device=0, lib: Optional[B.Library] = Non
     if st != B.G16_OK:
         raise G16Error(st, "g16_pairing_check failed: 1 to 16 pairs")
     return bool(ok[0])
+
+
+def prepare_inputs(pvk: PreparedVerifyingKey, public_inputs) -> List[bytes]:
+    """Groth16::prepare_inputs(&pvk, inputs) for a batch (g16_pvk_prepare_inputs): per input vector the point
+    X = IC_0 + sum_j pub_j IC_{j+1} as 64 packed bytes (all-zero = infinity) -- the sum verify_prepared forms per proof,
+    normalised.  public_inputs: one vector per result, as verify_prepared takes them."""
+    lib = pvk.lib
+    n = len(public_inputs)
+    flat = []
+    for pi in public_inputs:
+        if len(pi) != pvk.n_public:
+            raise G16Error(B.G16_ERR_INVALID, "MalformedVerifyingKey: wrong number of public inputs")
+        flat.extend(pi)
+    pubs = _as_fr(flat, lib) if (flat and not isinstance(flat[0], np.ndarray)) else \
+        (np.ascontiguousarray(np.stack(flat)) if flat else np.zeros((0, 4), np.uint64))
+    out = np.zeros(max(n, 1) * 64, dtype=np.uint8)
+    st = lib.g16_pvk_prepare_inputs(pvk._handle(), _np_ptr(pubs) if len(flat) else None, n, _np_ptr(out))
+    if st != B.G16_OK:
+        raise G16Error(st, "g16_pvk_prepare_inputs failed")
+    raw = out.tobytes()
+    return [raw[64 * i:64 * i + 64] for i in range(n)]
+
+
+def verify_prepared_inputs(pvk: PreparedVerifyingKey, proofs, prepared) -> List[bool]:
+    """Groth16::verify_proof_with_prepared_inputs for a batch (g16_verify_prepared_inputs): verify_prepared with the
+    points of prepare_inputs given, so the input ladder is skipped.  The verdicts are verify_prepared's; a prepared
+    point with a non-canonical word or off the curve gives False for that proof only."""
+    lib = pvk.lib
+    raw = b"".join(p.raw if isinstance(p, Proof) else bytes(p) for p in proofs)
+    n = len(raw) // B.G16_PROOF_BYTES
+    pts = b"".join(bytes(x) for x in prepared)
+    if len(prepared) != n or len(pts) != 64 * n:
+        raise G16Error(B.G16_ERR_INVALID, "one 64-byte prepared point per proof")
+    buf = np.frombuffer(raw, dtype=np.uint8)
+    xs = np.frombuffer(pts, dtype=np.uint8)
+    ok = np.zeros(max(n, 1), dtype=np.uint8)
+    st = lib.g16_verify_prepared_inputs(pvk._handle(), _np_ptr(buf) if n else None, _np_ptr(xs) if n else None, n,
+                                        _np_ptr(ok))
+    if st != B.G16_OK:
+        raise G16Error(st, "g16_verify_prepared_inputs failed")
+    return [bool(x) for x in ok[:n]]
+
+
+# ---- pairing values ----------------------------------------------------------------------------------------------
+FQ_MODULUS = 21888242871839275222246405745257275088696311157297823662689037894645226208583
+GT_BYTES = 384
+_GT_ONE = ((1 << 256) % FQ_MODULUS).to_bytes(32, "little") + bytes(GT_BYTES - 32)   # Montgomery 1 at w^0
+_GT_REASONS = {B.KEY_BAD_NONCANONICAL: "a coordinate >= q", B.KEY_BAD_SUBGROUP: "not in GT (g^r != 1)"}
+
+
+def _gt_error(lib, st, what):
+    msg = lib.g16_last_error(None).decode() if st == B.G16_ERR_INVALID else ""
+    return G16Error(st, msg if what.split(" ")[0] in msg else what)
+
+
+class GT:
+    """An element of GT, the target group of the pairing: an immutable wrapper of the library's 384 flat bytes (12 Fq
+    in Montgomery form, the coefficient of w^i of Fq12 = Fq[w] / (w^12 - 18 w^6 + 82) at 32 i).  Values are the ones
+    arkworks' Bn254::pairing and snarkjs give (the reduced pairing raised to the hard part's cofactor
+    m = 2x(6x^2 + 3x + 1): include/g16_amd.h).  All arithmetic runs on the device (g16_gt_multiexp); equality and hash
+    are those of the bytes, which are unique per element.  to_ark / to_snarkjs give the forms other software reads."""
+    __slots__ = ("raw", "lib", "device")
+
+    def __init__(self, raw, lib: Optional[B.Library] = None, device=0):
+        raw = bytes(raw)
+        if len(raw) != GT_BYTES:
+            raise G16Error(B.G16_ERR_INVALID, "a GT element is 384 bytes")
+        object.__setattr__(self, "raw", raw)
+        object.__setattr__(self, "lib", lib)
+        object.__setattr__(self, "device", device)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("GT is immutable")
+
+    def __delattr__(self, name):
+        raise AttributeError("GT is immutable")
+
+    def __eq__(self, other):
+        return isinstance(other, GT) and self.raw == other.raw
+
+    def __ne__(self, other):
+        return not self == other
+
+    def __hash__(self):
+        return hash(self.raw)
+
+    def __bytes__(self):
+        return self.raw
+
+    def __repr__(self):
+        return "GT(" + self.raw[:8].hex() + "...)"
+
+    @staticmethod
+    def one(lib: Optional[B.Library] = None, device=0) -> "GT":
+        return GT(_GT_ONE, lib, device)
+
+    def is_one(self) -> bool:
+        return self.raw == _GT_ONE
+
+    def __mul__(self, other):
+        if not isinstance(other, GT):
+            return NotImplemented
+        return gt_multiexp([[(self, 1), (other, 1)]], device=self.device, lib=self.lib)[0]
+
+    def __pow__(self, e):
+        """self ** e for any int e, reduced mod r (a negative e included: in GT the inverse is the (r - 1)-th power)"""
+        if isinstance(e, bool) or not isinstance(e, int):
+            return NotImplemented
+        return gt_multiexp([[(self, e)]], device=self.device, lib=self.lib)[0]
+
+    def inverse(self) -> "GT":
+        return self ** -1
+
+    def to_ark(self) -> bytes:
+        """ark-ff's Fq12::serialize: 12 canonical little-endian Fq in tower order (g16_gt_to_ark)"""
+        lib = self.lib or B.load()
+        src = np.frombuffer(self.raw, dtype=np.uint8)
+        out = np.zeros(GT_BYTES, dtype=np.uint8)
+        st = lib.g16_gt_to_ark(self.device, _np_ptr(src), 1, _np_ptr(out))
+        if st != B.G16_OK:
+            raise G16Error(st, "g16_gt_to_ark failed")
+        return out.tobytes()
+
+    @staticmethod
+    def from_ark(b, validate=True, lib: Optional[B.Library] = None, device=0) -> "GT":
+        """the inverse (g16_gt_from_ark).  G16Error: a coordinate >= q or, with validate, an element outside GT"""
+        return gt_from_ark(b, validate=validate, lib=lib, device=device)[0]
+
+    def to_snarkjs(self):
+        """snarkjs' JSON form: [2][3][2] decimal strings, Fq12.c_i / Fq6.c_j / Fq2.c_k"""
+        a = self.to_ark()
+        word = lambda k: str(int.from_bytes(a[32 * k:32 * k + 32], "little"))   # noqa: E731
+        return [[[word(2 * (3 * c + v)), word(2 * (3 * c + v) + 1)] for v in range(3)] for c in range(2)]
+
+    @staticmethod
+    def from_snarkjs(j, validate=True, lib: Optional[B.Library] = None, device=0) -> "GT":
+        """the inverse.  G16Error: not [2][3][2] decimal strings, a coordinate >= q or, with validate, outside GT"""
+        try:
+            if len(j) != 2 or any(len(c) != 3 or any(len(v) != 2 for v in c) for c in j):
+                raise ValueError
+            words = [int(w, 10) if isinstance(w, str) else int(w) for c in j for v in c for w in v]
+            if any(isinstance(w, bool) for c in j for v in c for w in v) or any(not 0 <= w < 1 << 256 for w in words):
+                raise ValueError
+        except (TypeError, ValueError):
+            raise G16Error(B.G16_ERR_INVALID, "a GT value is [2][3][2] non-negative decimal strings") from None
+        return GT.from_ark(b"".join(w.to_bytes(32, "little") for w in words), validate, lib, device)
+
+
+def gt_from_ark(data, validate=True, lib: Optional[B.Library] = None, device=0) -> List[GT]:
+    """n x 384 bytes of ark-serialized Fq12 -> n GT (g16_gt_from_ark, one call).  G16Error names the first refused
+    element and the reason: a coordinate >= q or, with validate, g^r != 1."""
+    lib = lib or B.load()
+    data = bytes(data)
+    if len(data) % GT_BYTES:
+        raise G16Error(B.G16_ERR_INVALID, "an ark-serialized Fq12 element is 384 bytes")
+    n = len(data) // GT_BYTES
+    src = np.frombuffer(data, dtype=np.uint8)
+    out = np.zeros(max(n, 1) * GT_BYTES, dtype=np.uint8)
+    why = np.zeros(max(n, 1), dtype=np.uint8)
+    st = lib.g16_gt_from_ark(device, _np_ptr(src) if n else None, n, 1 if validate else 0, _np_ptr(out), _np_ptr(why))
+    if st != B.G16_OK:
+        raise G16Error(st, "g16_gt_from_ark failed")
+    bad = np.flatnonzero(why[:n])
+    if len(bad):
+        i = int(bad[0])
+        raise G16Error(B.G16_ERR_INVALID, f"GT element {i}: {_GT_REASONS.get(int(why[i]), 'rejected')}")
+    raw = out.tobytes()
+    return [GT(raw[GT_BYTES * i:GT_BYTES * (i + 1)], lib, device) for i in range(n)]
+
+
+def gt_multiexp(groups, device=0, lib: Optional[B.Library] = None) -> List[GT]:
+    """out_i = prod_j g_ij ** s_ij for every group i, a sequence of (GT, int) pairs, in ONE call (g16_gt_multiexp, one
+    workgroup per group).  The exponents are reduced mod r here; the elements are taken as members of GT.  An empty
+    group gives one."""
+    groups = [list(g) for g in groups]
+    for g in groups:
+        for x, _ in g:
+            if not isinstance(x, GT):
+                raise G16Error(B.G16_ERR_INVALID, "gt_multiexp takes (GT, int) pairs")
+            lib = lib or x.lib
+    lib = lib or B.load()
+    n = len(groups)
+    off = np.zeros(n + 1, dtype=np.uint32)
+    off[1:] = np.cumsum([len(g) for g in groups], dtype=np.uint64)
+    total = int(off[n])
+    elems = np.frombuffer(b"".join(x.raw for g in groups for x, _ in g), dtype=np.uint8)
+    sc = np.frombuffer(b"".join((int(e) % FR_MODULUS).to_bytes(32, "little") for g in groups for _, e in g),
+                       dtype=np.uint64)
+    out = np.zeros(max(n, 1) * GT_BYTES, dtype=np.uint8)
+    st = lib.g16_gt_multiexp(device, _np_ptr(elems) if total else None, _np_ptr(sc) if total else None, _np_ptr(off), n,
+                             _np_ptr(out))
+    if st != B.G16_OK:
+        raise _gt_error(lib, st, "g16_gt_multiexp failed")
+    raw = out.tobytes()
+    return [GT(raw[GT_BYTES * i:GT_BYTES * (i + 1)], lib, device) for i in range(n)]
+
+
+def pairing_products(groups, device=0, lib: Optional[B.Library] = None, return_ok=False):
+    """The VALUES prod_k e(P_k, Q_k) of many products in one call (g16_pairing_products): one workgroup per product,
+    0 to 16 pairs each in one Miller loop.  groups: (g1_points, g2_points) per product, 64-byte packed G1 and 128-byte
+    packed G2 points (all-zero = infinity: the pair contributes 1; an empty product is one).  A product with a
+    malformed point (non-canonical word, off its curve, Q outside G2) comes back as the all-zero element, which is no
+    member of GT; return_ok=True returns (values, [well formed]) to tell.  More than 16 pairs in a product raises."""
+    lib = lib or B.load()
+    groups = [(list(a), list(b)) for a, b in groups]
+    n = len(groups)
+    if any(len(a) != len(b) for a, b in groups):
+        raise G16Error(B.G16_ERR_INVALID, "one 64-byte G1 point per 128-byte G2 point")
+    off = np.zeros(n + 1, dtype=np.uint32)
+    off[1:] = np.cumsum([len(a) for a, _ in groups], dtype=np.uint64)
+    total = int(off[n])
+    g1 = np.frombuffer(b"".join(bytes(p) for a, _ in groups for p in a), dtype=np.uint8)
+    g2 = np.frombuffer(b"".join(bytes(q) for _, b in groups for q in b), dtype=np.uint8)
+    if g1.shape[0] != 64 * total or g2.shape[0] != 128 * total:
+        raise G16Error(B.G16_ERR_INVALID, "one 64-byte G1 point per 128-byte G2 point")
+    out = np.zeros(max(n, 1) * GT_BYTES, dtype=np.uint8)
+    ok = np.zeros(max(n, 1), dtype=np.uint8)
+    st = lib.g16_pairing_products(device, _np_ptr(g1) if total else None, _np_ptr(g2) if total else None, _np_ptr(off),
+                                  n, _np_ptr(out), _np_ptr(ok))
+    if st != B.G16_OK:
+        raise _gt_error(lib, st, "g16_pairing_products failed")
+    raw = out.tobytes()
+    res = [GT(raw[GT_BYTES * i:GT_BYTES * (i + 1)], lib, device) for i in range(n)]
+    if return_ok:
+        return res, [bool(x) for x in ok[:n]]
+    return res
+
+
+def pairing(p, q, device=0, lib: Optional[B.Library] = None) -> GT:
+    """e(p, q) for one packed G1 point and one packed G2 point (pairing_products with one product of one pair); a
+    malformed point raises"""
+    vals, ok = pairing_products([([p], [q])], device=device, lib=lib, return_ok=True)
+    if not ok[0]:
+        raise G16Error(B.G16_ERR_INVALID, "pairing: a malformed point (non-canonical, off its curve or outside G2)")
+    return vals[0]
+
+
+GT_PHASES = ("upload", "g2_tests", "kernels", "download")
+
+
+def gt_times(lib: Optional[B.Library] = None) -> dict:
+    """milliseconds of device time per phase of this thread's last pairing_products / gt_multiexp / codec call
+    (g16_gt_times); g2_tests runs beside kernels on a second stream"""
+    lib = lib or B.load()
+    ms = (C.c_float * len(GT_PHASES))()
+    lib.check(lib.g16_gt_times(ms, len(GT_PHASES)))
+    return dict(zip(GT_PHASES, (float(x) for x in ms)))
 
 
 VERIFY_PREPARED_PHASES = ("upload", "inputs", "g2_tests", "pairing", "download", "prepare")
@@ -2242,6 +2497,16 @@ class Groth16:
     def verify_with_processed_vk(pvk: PreparedVerifyingKey, public_inputs, proof) -> bool:
         """Groth16::verify_with_processed_vk(&pvk, inputs, &proof) on the GPU, one workgroup for the proof"""
         return verify_prepared(pvk, [proof], [list(public_inputs)])[0]
+
+    @staticmethod
+    def prepare_inputs(pvk: PreparedVerifyingKey, public_inputs) -> bytes:
+        """Groth16::prepare_inputs(&pvk, inputs) on the GPU: IC_0 + sum_j inputs_j IC_{j+1}, 64 packed bytes"""
+        return prepare_inputs(pvk, [list(public_inputs)])[0]
+
+    @staticmethod
+    def verify_proof_with_prepared_inputs(pvk: PreparedVerifyingKey, proof, prepared_inputs) -> bool:
+        """Groth16::verify_proof_with_prepared_inputs(&pvk, &proof, &prepared_inputs) on the GPU"""
+        return verify_prepared_inputs(pvk, [proof], [prepared_inputs])[0]
 
     @staticmethod
     def rerandomize_proof(vk: "VerifyingKey", proof, rng=None, **kw) -> Proof:

@@ -2,8 +2,8 @@
 
     prove <circuit.zkey> <witness.wtns> <proof.json> <public.json>     rapidsnark prover, snarkjs groth16 prove
     prove-batch <circuit.zkey> <outdir> <witness.wtns>...              one batched pass; <stem>.proof.json, <stem>.public.json
-    verify <verification_key.json> <public.json> <proof.json>          snarkjs groth16 verify: OK / INVALID
-    export-vkey <circuit.zkey> <verification_key.json>                 snarkjs zkey export verificationkey
+    verify [--check-alphabeta] <verification_key.json> <public.json> <proof.json>     snarkjs groth16 verify: OK / INVALID
+    export-vkey [--alphabeta] <circuit.zkey> <verification_key.json>   snarkjs zkey export verificationkey
     calldata <public.json> <proof.json>                                snarkjs zkey export soliditycalldata
     wtns-check <circuit.r1cs> <witness.wtns>                           snarkjs wtns check
 
@@ -33,9 +33,12 @@ def _parser():
     s = sub.add_parser("verify", help="verify one proof")
     for a in ("vkey", "public", "proof"):
         s.add_argument(a)
+    s.add_argument("--check-alphabeta", action="store_true",
+                   help="recompute e(alpha, beta) and compare it with the key's vk_alphabeta_12, if it has one")
     s = sub.add_parser("export-vkey", help="write the verification key of a zkey")
     for a in ("zkey", "vkey"):
         s.add_argument(a)
+    s.add_argument("--alphabeta", action="store_true", help="write vk_alphabeta_12 = e(alpha, beta), as snarkjs does")
     s = sub.add_parser("calldata", help="print the arguments of verifyProof")
     for a in ("public", "proof"):
         s.add_argument(a)
@@ -76,14 +79,14 @@ def _run(a, lib) -> int:
         return 0
     if a.cmd == "verify":
         _need(a.vkey, a.public, a.proof)
-        vk = cc.read_vk_json(a.vkey, device=dev, lib=lib)
+        vk = cc.read_vk_json(a.vkey, device=dev, lib=lib, check_alphabeta=a.check_alphabeta)
         ok = cc.verify_batch(vk, [cc.read_proof_json(a.proof, device=dev, lib=lib)], [cc.read_public_json(a.public)],
                              device=dev, lib=lib)[0]
         print("OK" if ok else "INVALID")
         return 0 if ok else 1
     if a.cmd == "export-vkey":
         _need(a.zkey)
-        cc.write_vk_json(a.vkey, cc.read_zkey(a.zkey, lib=lib)[0].vk, device=dev, lib=lib)
+        cc.write_vk_json(a.vkey, cc.read_zkey(a.zkey, lib=lib)[0].vk, device=dev, lib=lib, alphabeta=a.alphabeta)
         return 0
     if a.cmd == "calldata":
         _need(a.public, a.proof)

@@ -193,6 +193,9 @@ ABI_SYMBOLS = [
     "g16_proofs_rerandomize", "g16_proofs_rerandomize_keys", "g16_proofs_rerandomize_times",
     "g16_pvk_create", "g16_pvk_destroy", "g16_pvk_alpha_beta", "g16_verify_prepared", "g16_pairing_check",
     "g16_verify_prepared_times",
+    "g16_pvk_prepare_inputs", "g16_verify_prepared_inputs",
+    "g16_pairing_products", "g16_gt_multiexp", "g16_gt_to_ark", "g16_gt_from_ark", "g16_pvk_alpha_g1_beta_g2",
+    "g16_gt_times",
     "g16_fr_convert", "g16_fr_convert_times", "g16_witness_upload_canonical", "g16_prove_canonical", "g16_prove_batch_canonical",
     "g16_wtns_open", "g16_wtns_open_mem", "g16_wtns_count", "g16_wtns_values", "g16_wtns_close",
 ]
@@ -357,6 +360,14 @@ class Library:
             "g16_verify_prepared": (C.c_int, [vp, vp, vp, C.c_uint32, vp]),
             "g16_pairing_check": (C.c_int, [C.c_int, vp, vp, C.c_uint32, vp]),
             "g16_verify_prepared_times": (C.c_int, [C.POINTER(C.c_float), C.c_uint32]),
+            "g16_pvk_prepare_inputs": (C.c_int, [vp, vp, C.c_uint32, vp]),
+            "g16_verify_prepared_inputs": (C.c_int, [vp, vp, vp, C.c_uint32, vp]),
+            "g16_pairing_products": (C.c_int, [C.c_int, vp, vp, vp, C.c_uint32, vp, vp]),
+            "g16_gt_multiexp": (C.c_int, [C.c_int, vp, vp, vp, C.c_uint32, vp]),
+            "g16_gt_to_ark": (C.c_int, [C.c_int, vp, C.c_uint32, vp]),
+            "g16_gt_from_ark": (C.c_int, [C.c_int, vp, C.c_uint32, C.c_int, vp, vp]),
+            "g16_pvk_alpha_g1_beta_g2": (C.c_int, [vp, vp]),
+            "g16_gt_times": (C.c_int, [C.POINTER(C.c_float), C.c_uint32]),
             "g16_fr_convert": (C.c_int, [C.c_int, vp, vp, C.c_size_t, C.POINTER(C.c_int64)]),
             "g16_fr_convert_times": (C.c_int, [C.POINTER(C.c_float), C.c_uint32]),
             "g16_witness_upload_canonical": (C.c_int, [vp, vp, C.c_size_t, C.POINTER(C.c_int64)]),

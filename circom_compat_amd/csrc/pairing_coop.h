@@ -17,8 +17,9 @@
 //                 G2Prepared).  The loop is pairing.h's: 6x + 2 from the second-highest bit, then the two Frobenius
 //                 steps.  Projective lines differ from pairing.h's affine ones by factors in Fq2, and a projective
 //                 G1 side scales a line by a factor in Fq: the final exponentiation removes both.
-//   coop_final_exp_is_one   the easy part with ONE inversion through the norms Fq12 -> Fq6 -> Fq2 -> Fq (one Fermat
-//                 inversion in Fq, in one lane), then the Fuentes-Castaneda hard part of pairing.h.
+//   coop_final_exp   the easy part with ONE inversion through the norms Fq12 -> Fq6 -> Fq2 -> Fq (one Fermat
+//                 inversion in Fq, in one lane), then the Fuentes-Castaneda hard part of pairing.h; the value stays
+//                 in LDS.  coop_final_exp_is_one compares it with 1.
 // Everything here uses only __syncthreads and LDS, so the same source runs under the CPU emulator of the tests.
 #pragma once
 #include "keycheck.h"
@@ -161,9 +162,10 @@ __device__ __forceinline__ void coop_embed(F12* l, const Fq2& z, int shift) {
   l->c[shift + 6] = b;
 }
 
-// L.f^((q^12 - 1) / r * cofactor) == 1.  Destroys L.f and L.y.
-__device__ __attribute__((noinline)) bool coop_final_exp_is_one(CoopLds& L, const VkDev* vk) {
-  const uint32_t t = threadIdx.x;
+// L.y[0] <- L.f^((q^12 - 1) / r * m), m = 2 x (6 x^2 + 3 x + 1) the cofactor of the Fuentes-Castaneda hard part: the
+// VALUE form (gt.hip hands it out; it is the GT element ark-ec's final_exponentiation and snarkjs return).  Destroys
+// L.f and the rest of L.y; ends behind a barrier.
+__device__ __attribute__((noinline)) void coop_final_exp(CoopLds& L, const VkDev* vk) {
   F12* y = L.y;
   F12* f = &L.f;
   // 1 / f = conj(f) * g^(q^2) * g^(q^4) / N, g = f conj(f) in Fq6, N = g g^(q^2) g^(q^4) in Fq2
@@ -173,7 +175,7 @@ __device__ __attribute__((noinline)) bool coop_final_exp_is_one(CoopLds& L, cons
   coop_frob(L, &y[3], &y[2], vk->frob[1]);
   coop_mul_dense(L, &y[2], &y[2], &y[3]);  // g^(q^2) g^(q^4)
   coop_mul_dense(L, &y[3], &y[1], &y[2]);  // N: c[0] and c[6] only
-  if (t == 0) {
+  if (threadIdx.x == 0) {
     const Fq b = y[3].c[6];
     const Fq a = y[3].c[0] + (b.dbl().dbl().dbl() + b);
     const Fq ni = (a.sqr() + b.sqr()).inv();
@@ -210,7 +212,12 @@ __device__ __attribute__((noinline)) bool coop_final_exp_is_one(CoopLds& L, cons
   coop_mul_dense(L, &y[1], r, &y[9]);          // y15
   coop_frob(L, &y[1], &y[1], vk->frob[2]);
   coop_mul_dense(L, &y[0], &y[1], &y[0]);
-  if (t == 0) L.flag[3] = f12_is_one(y[0]) ? 1u : 0u;
+}
+
+// L.f^((q^12 - 1) / r * m) == 1: the check form.  Destroys L.f and L.y.
+__device__ __forceinline__ bool coop_final_exp_is_one(CoopLds& L, const VkDev* vk) {
+  coop_final_exp(L, vk);
+  if (threadIdx.x == 0) L.flag[3] = f12_is_one(L.y[0]) ? 1u : 0u;
   __syncthreads();
   return L.flag[3] != 0;
 }
@@ -443,6 +450,32 @@ __device__ __forceinline__ bool coop_g2_in_subgroup(const G2Affine& p, const VkD
   if (acc.is_inf()) return false;
   const G2Affine psi = frob_g2(p, vk);
   return acc.x == psi.x * acc.zz && acc.y == psi.y * acc.zzz;
+}
+
+
+// pts + i * stride: a G2 point as stored.  ok[i] = canonical words, on the twist, in G2.
+__global__ void __launch_bounds__(COOP_LANES) k_vp_g2(const VkDev* vk, const uint8_t* pts, uint32_t stride, uint32_t n,
+                                                      uint64_t k_lo, uint64_t k_hi, uint8_t* ok) {
+  const uint32_t i = blockIdx.x * COOP_LANES + threadIdx.x;
+  if (i >= n) return;
+  G2Affine B;
+  memcpy(&B, pts + (size_t)i * stride, 128);
+  bool good = fq2_words_canonical(B.x) && fq2_words_canonical(B.y);
+  if (good && !B.is_inf()) good = on_curve_g2(B, vk) && coop_g2_in_subgroup(B, vk, k_lo, k_hi);
+  ok[i] = good ? 1 : 0;
+}
+
+// q - r = 6 x^2 as two 64-bit words (it has 127 bits)
+inline void six_x_squared(uint64_t* lo, uint64_t* hi) {
+  uint32_t d[8];
+  uint64_t br = 0;
+  for (int i = 0; i < 8; ++i) {
+    const uint64_t t = (uint64_t)FqParams::MOD[i] - FrParams::MOD[i] - br;
+    d[i] = (uint32_t)t;
+    br = (t >> 32) & 1;
+  }
+  *lo = (uint64_t)d[0] | ((uint64_t)d[1] << 32);
+  *hi = (uint64_t)d[2] | ((uint64_t)d[3] << 32);
 }
 
 }  // namespace

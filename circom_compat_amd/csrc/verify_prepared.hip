@@ -5,13 +5,14 @@
 //                   line coefficients of gamma and of delta for every step of the loop (PvkTable)
 //   k_vp_inputs     one workgroup per proof: X = IC_0 + sum_j pub_j IC_{j+1}, one lane per term (striding past 64), a
 //                   fixed LDS tree; -X leaves PROJECTIVE (ScaledG1): the Fq factor vanishes in the final exponentiation
-//   k_vp_g2         one lane per G2 point, on a SECOND STREAM beside the other two: every word canonical, the point
+//   k_vp_g2         (pairing_coop.h: gt.hip launches it too) one lane per G2 point, on a SECOND STREAM beside the other two: every word canonical, the point
 //                   on the twist, and psi(B) = [6 x^2] B (a 127-bit ladder instead of the 254 bits of [r] B)
 //   k_vp_pairing    one workgroup per proof: the tests of A and C, then ONE Miller loop for the three pairs
 //                   (A, B) on the fly, (-X, gamma) and (-C, delta) from the tables, times the stored (beta, -alpha)
 //                   value, and the final exponentiation
 //   k_pc_pairing    g16_pairing_check: up to 16 pairs, all on the fly, one workgroup
 //   k_vp_and        verdict = pairing AND the G2 tests
+//   k_vp_inputs_affine / k_vp_inputs_given   prepare_inputs (X normalised) and verify_prepared_inputs (X given)
 // A call uses the handle's two streams and synchronises those, not the device.
 #include <stdlib.h>
 
@@ -69,16 +70,38 @@ __global__ void __launch_bounds__(COOP_LANES) k_vp_inputs(const G1Affine* ic, ui
   }
 }
 
-// pts + i * stride: a G2 point as stored.  ok[i] = canonical words, on the twist, in G2.
-__global__ void __launch_bounds__(COOP_LANES) k_vp_g2(const VkDev* vk, const uint8_t* pts, uint32_t stride, uint32_t n,
-                                                      uint64_t k_lo, uint64_t k_hi, uint8_t* ok) {
-  const uint32_t i = blockIdx.x * COOP_LANES + threadIdx.x;
+// prepare_inputs: k_vp_inputs' sum NORMALISED, X as a packed affine point (one inversion per proof; all-zero = infinity)
+__global__ void k_vp_inputs_affine(const ScaledG1* xs, uint32_t n, G1Affine* out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  G2Affine B;
-  memcpy(&B, pts + (size_t)i * stride, 128);
-  bool good = fq2_words_canonical(B.x) && fq2_words_canonical(B.y);
-  if (good && !B.is_inf()) good = on_curve_g2(B, vk) && coop_g2_in_subgroup(B, vk, k_lo, k_hi);
-  ok[i] = good ? 1 : 0;
+  const ScaledG1 s = xs[i];
+  G1Affine p;
+  if (s.inf) {
+    p.x = Fq::zero();
+    p.y = Fq::zero();
+  } else {
+    const Fq zi = s.zs.inv();
+    p.x = s.xs * zi;
+    p.y = (s.ys * zi).neg();
+  }
+  out[i] = p;
+}
+
+// verify_prepared_inputs: the caller's X, tested like a proof's point, as the G1 side of (-X, gamma).  A malformed X
+// leaves as infinity (its pair is skipped) with good[i] = 0: that proof alone is refused.
+__global__ void k_vp_inputs_given(const G1Affine* pts, uint32_t n, ScaledG1* xs, uint8_t* good) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const G1Affine X = pts[i];
+  const bool ok = g1_well_formed(X);
+  ScaledG1 o;
+  o.xs = X.x;
+  o.ys = X.y.neg();
+  o.zs = Fq::one();
+  o.inf = (!ok || X.is_inf()) ? 1u : 0u;
+  o.pad[0] = o.pad[1] = o.pad[2] = 0;
+  xs[i] = o;
+  good[i] = ok ? 1 : 0;
 }
 
 __global__ void __launch_bounds__(COOP_LANES) k_vp_pairing(const VkDev* vk, const PvkTable* tabs, const uint8_t* proofs,
@@ -212,19 +235,6 @@ void fill_consts(VkDev* hv) {
   hv->ml_alpha_beta = f12_one();
 }
 
-// q - r = 6 x^2 as two 64-bit words (it has 127 bits)
-void six_x_squared(uint64_t* lo, uint64_t* hi) {
-  uint32_t d[8];
-  uint64_t br = 0;
-  for (int i = 0; i < 8; ++i) {
-    const uint64_t t = (uint64_t)FqParams::MOD[i] - FrParams::MOD[i] - br;
-    d[i] = (uint32_t)t;
-    br = (t >> 32) & 1;
-  }
-  *lo = (uint64_t)d[0] | ((uint64_t)d[1] << 32);
-  *hi = (uint64_t)d[2] | ((uint64_t)d[3] << 32);
-}
-
 const char* reason_of(uint8_t flag) {
   return flag == G16_KEY_BAD_NONCANONICAL ? "non-canonical coordinate"
          : flag == G16_KEY_BAD_OFF_CURVE  ? "off the curve"
@@ -246,11 +256,14 @@ struct g16_pvk {
   DevBuf<PvkTable> dtab;
   DevBuf<G1Affine> dic;
   F12 ml_alpha_beta;
+  uint8_t alpha[64], beta[128];   // as given: what g16_pvk_alpha_g1_beta_g2 pairs on first use
+  uint8_t gt_alpha_beta[384];
+  bool gt_made = false;
   uint64_t k_lo = 0, k_hi = 0;
   StreamBox s1, s2;
   TimedEvent ev[E_COUNT];
   GrowPinned pin;
-  GrowBuf<uint8_t> dproofs, dok, dg2ok;
+  GrowBuf<uint8_t> dproofs, dok, dg2ok, dxok;
   GrowBuf<Fr> dpub;
   GrowBuf<ScaledG1> dxs;
 };
@@ -300,6 +313,8 @@ extern "C" g16_status g16_pvk_create(int device, const g16_vk_desc* vk, g16_pvk*
     std::unique_ptr<g16_pvk> h(new g16_pvk());
     h->device = device;
     h->n_pub = vk->ic_count - 1;
+    memcpy(h->alpha, vk->alpha_g1, 64);
+    memcpy(h->beta, vk->beta_g2, 128);
     six_x_squared(&h->k_lo, &h->k_hi);
     h->dvk.alloc(1);
     h->dtab.alloc(2);
@@ -343,17 +358,20 @@ extern "C" g16_status g16_pvk_alpha_beta(const g16_pvk* pvk, uint8_t out[384]) {
   return G16_OK;
 }
 
-extern "C" g16_status g16_verify_prepared(g16_pvk* h, const uint8_t* proofs, const uint64_t* public_inputs,
-                                          uint32_t n, uint8_t* ok_out) {
+// g16_verify_prepared (prepared == NULL: X from public_inputs by k_vp_inputs) and g16_verify_prepared_inputs (X given:
+// n x 64 bytes, the input ladder is skipped)
+static g16_status verify_prepared_run(g16_pvk* h, const uint8_t* proofs, const uint64_t* public_inputs,
+                                      const uint8_t* prepared, uint32_t n, uint8_t* ok_out) {
   if (!h || (n && (!proofs || !ok_out))) return G16_ERR_INVALID;
-  const uint32_t n_pub = h->n_pub;
-  if (n && n_pub && !public_inputs) return G16_ERR_INVALID;
+  const uint32_t n_pub = prepared ? 2 : h->n_pub;   // words of 32 bytes per proof in the input block
+  if (n && n_pub && !public_inputs && !prepared) return G16_ERR_INVALID;
   if ((uint64_t)n * n_pub > 0xffffffffull / 32 || n > 0xffffffffu / G16_PROOF_BYTES) return G16_ERR_INVALID;
   if (!n) return G16_OK;
   std::lock_guard<std::mutex> guard(h->mu);
   try {
     G16_HIP(hipSetDevice(h->device));
     const size_t pbytes = (size_t)n * G16_PROOF_BYTES, ibytes = (size_t)n * n_pub * 32;
+    if (prepared) h->dxok.need(n);
     h->pin.need(pbytes + ibytes + n);
     h->dproofs.need(pbytes);
     h->dpub.need((size_t)n * n_pub + 1);
@@ -364,7 +382,7 @@ extern "C" g16_status g16_verify_prepared(g16_pvk* h, const uint8_t* proofs, con
     auto* ev = h->ev;
     uint8_t* pin_ok = h->pin.p + pbytes + ibytes;
     memcpy(h->pin.p, proofs, pbytes);
-    if (ibytes) memcpy(h->pin.p + pbytes, public_inputs, ibytes);
+    if (ibytes) memcpy(h->pin.p + pbytes, prepared ? (const void*)prepared : (const void*)public_inputs, ibytes);
 
     G16_LAUNCH(k_vp_mark, 1, 1, 0, s1);
     G16_HIP(hipEventRecord(ev[E_UP0].e, s1));
@@ -380,14 +398,19 @@ extern "C" g16_status g16_verify_prepared(g16_pvk* h, const uint8_t* proofs, con
                (const uint8_t*)h->dproofs.d.p + 64, (uint32_t)G16_PROOF_BYTES, n, h->k_lo, h->k_hi, h->dg2ok.d.p);
     G16_HIP(hipEventRecord(ev[E_G2B].e, s2));
 
-    G16_LAUNCH(k_vp_inputs, n, COOP_LANES, 0, s1, (const G1Affine*)h->dic.p, n_pub, (const Fr*)h->dpub.d.p, n,
-               h->dxs.d.p);
+    if (prepared)
+      G16_LAUNCH(k_vp_inputs_given, ceil_div(n, 256), 256, 0, s1, (const G1Affine*)h->dpub.d.p, n, h->dxs.d.p,
+                 h->dxok.d.p);
+    else
+      G16_LAUNCH(k_vp_inputs, n, COOP_LANES, 0, s1, (const G1Affine*)h->dic.p, n_pub, (const Fr*)h->dpub.d.p, n,
+                 h->dxs.d.p);
     G16_HIP(hipEventRecord(ev[E_IN].e, s1));
     G16_LAUNCH(k_vp_pairing, n, COOP_LANES, 0, s1, (const VkDev*)h->dvk.p, (const PvkTable*)h->dtab.p,
                (const uint8_t*)h->dproofs.d.p, (const ScaledG1*)h->dxs.d.p, n, h->dok.d.p);
     G16_HIP(hipEventRecord(ev[E_PAIR].e, s1));
     G16_HIP(hipStreamWaitEvent(s1, ev[E_G2B].e, 0));
     G16_LAUNCH(k_vp_and, ceil_div(n, 256), 256, 0, s1, h->dok.d.p, (const uint8_t*)h->dg2ok.d.p, n, n, 0);
+    if (prepared) G16_LAUNCH(k_vp_and, ceil_div(n, 256), 256, 0, s1, h->dok.d.p, (const uint8_t*)h->dxok.d.p, n, n, 0);
     G16_HIP(hipEventRecord(ev[E_DN0].e, s1));
     G16_HIP(hipMemcpyAsync(pin_ok, h->dok.d.p, n, hipMemcpyDeviceToHost, s1));
     G16_HIP(hipEventRecord(ev[E_DN1].e, s1));
@@ -411,6 +434,63 @@ extern "C" g16_status g16_verify_prepared(g16_pvk* h, const uint8_t* proofs, con
   } catch (const std::exception&) {
     return G16_ERR_INTERNAL;
   }
+}
+
+extern "C" g16_status g16_verify_prepared(g16_pvk* h, const uint8_t* proofs, const uint64_t* public_inputs,
+                                          uint32_t n, uint8_t* ok_out) {
+  return verify_prepared_run(h, proofs, public_inputs, nullptr, n, ok_out);
+}
+
+extern "C" g16_status g16_verify_prepared_inputs(g16_pvk* h, const uint8_t* proofs, const uint8_t* prepared, uint32_t n,
+                                                 uint8_t* ok_out) {
+  if (n && !prepared) return G16_ERR_INVALID;
+  return verify_prepared_run(h, proofs, nullptr, n ? prepared : nullptr, n, ok_out);
+}
+
+extern "C" g16_status g16_pvk_prepare_inputs(g16_pvk* h, const uint64_t* public_inputs, uint32_t n, uint8_t* out) {
+  if (!h || (n && !out)) return G16_ERR_INVALID;
+  const uint32_t n_pub = h->n_pub;
+  if (n && n_pub && !public_inputs) return G16_ERR_INVALID;
+  if ((uint64_t)n * n_pub > 0xffffffffull / 32 || n > 0xffffffffu / 64) return G16_ERR_INVALID;
+  if (!n) return G16_OK;
+  std::lock_guard<std::mutex> guard(h->mu);
+  try {
+    G16_HIP(hipSetDevice(h->device));
+    const size_t ibytes = (size_t)n * n_pub * 32;
+    h->dpub.need((size_t)n * n_pub + 1);
+    h->dxs.need(n);
+    h->dproofs.need((size_t)n * 64);   // the normalised points leave through the proof buffer
+    hipStream_t s1 = h->s1.s;
+    if (ibytes) G16_HIP(hipMemcpyAsync(h->dpub.d.p, public_inputs, ibytes, hipMemcpyHostToDevice, s1));
+    G16_LAUNCH(k_vp_inputs, n, COOP_LANES, 0, s1, (const G1Affine*)h->dic.p, n_pub, (const Fr*)h->dpub.d.p, n,
+               h->dxs.d.p);
+    G16_LAUNCH(k_vp_inputs_affine, ceil_div(n, 64), 64, 0, s1, (const ScaledG1*)h->dxs.d.p, n,
+               (G1Affine*)h->dproofs.d.p);
+    G16_HIP(hipMemcpyAsync(out, h->dproofs.d.p, (size_t)n * 64, hipMemcpyDeviceToHost, s1));
+    G16_HIP(hipGetLastError());
+    G16_HIP(hipStreamSynchronize(s1));
+    return G16_OK;
+  } catch (const HipError&) {
+    return G16_ERR_HIP;
+  } catch (const std::exception&) {
+    return G16_ERR_INTERNAL;
+  }
+}
+
+extern "C" g16_status g16_pvk_alpha_g1_beta_g2(const g16_pvk* pvk, uint8_t out[384]) {
+  if (!pvk || !out) return G16_ERR_INVALID;
+  g16_pvk* h = const_cast<g16_pvk*>(pvk);   // the cache is not part of the key
+  std::lock_guard<std::mutex> guard(h->mu);
+  if (!h->gt_made) {  // first use: one product of one pair, (alpha, beta) as the key gave them
+    const uint32_t off[2] = {0, 1};
+    uint8_t ok = 0;
+    const g16_status st = g16_pairing_products(h->device, h->alpha, h->beta, off, 1, h->gt_alpha_beta, &ok);
+    if (st != G16_OK) return st;
+    if (!ok) return G16_ERR_INTERNAL;  // g16_pvk_create has tested both points
+    h->gt_made = true;
+  }
+  memcpy(out, h->gt_alpha_beta, 384);
+  return G16_OK;
 }
 
 extern "C" g16_status g16_pairing_check(int device, const uint8_t* g1, const uint8_t* g2, uint32_t n_pairs,

@@ -23,7 +23,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _binding as B
-from . import FR_MODULUS, G16Error, Proof, VerifyingKey, points_from_ark, points_to_ark
+from . import FR_MODULUS, GT, G16Error, Proof, VerifyingKey, pairing, points_from_ark, points_to_ark
 
 FQ_MODULUS = 21888242871839275222246405745257275088696311157297823662689037894645226208583
 
@@ -203,19 +203,25 @@ def read_public_json(src) -> List[int]:
 
 
 # ---- verification_key.json -------------------------------------------------------------------------------------
-def vk_to_json(vk: VerifyingKey, device=0, lib: Optional[B.Library] = None) -> dict:
-    """protocol, curve, nPublic, vk_alpha_1, vk_beta_2, vk_gamma_2, vk_delta_2, IC.  vk_alphabeta_12 is NOT written:
-    snarkjs' verifier does not read it, and the library has no call that returns a GT value."""
+def vk_to_json(vk: VerifyingKey, device=0, lib: Optional[B.Library] = None, alphabeta=False) -> dict:
+    """protocol, curve, nPublic, vk_alpha_1, vk_beta_2, vk_gamma_2, vk_delta_2, IC.  alphabeta=True adds
+    vk_alphabeta_12 = e(alpha, beta) right after vk_delta_2, where snarkjs writes it (one pairing on the device:
+    pairing / GT.to_snarkjs); off by default, snarkjs' own verifier does not read the field."""
     ic = np.ascontiguousarray(vk.gamma_abc_g1, dtype=np.uint8).reshape(-1, 64)
     g1 = _decode(bytes(vk.alpha_g1) + ic.tobytes(), "g1", device, lib)
     g2 = _decode(bytes(vk.beta_g2) + bytes(vk.gamma_g2) + bytes(vk.delta_g2), "g2", device, lib)
-    return {"protocol": "groth16", "curve": "bn128", "nPublic": ic.shape[0] - 1, "vk_alpha_1": _g1_to_json(g1[0]),
-            "vk_beta_2": _g2_to_json(g2[0]), "vk_gamma_2": _g2_to_json(g2[1]), "vk_delta_2": _g2_to_json(g2[2]),
-            "IC": [_g1_to_json(p) for p in g1[1:]]}
+    j = {"protocol": "groth16", "curve": "bn128", "nPublic": ic.shape[0] - 1, "vk_alpha_1": _g1_to_json(g1[0]),
+         "vk_beta_2": _g2_to_json(g2[0]), "vk_gamma_2": _g2_to_json(g2[1]), "vk_delta_2": _g2_to_json(g2[2])}
+    if alphabeta:
+        j["vk_alphabeta_12"] = pairing(bytes(vk.alpha_g1), bytes(vk.beta_g2), device=device, lib=lib).to_snarkjs()
+    j["IC"] = [_g1_to_json(p) for p in g1[1:]]
+    return j
 
 
-def vk_from_json(src, device=0, lib: Optional[B.Library] = None) -> VerifyingKey:
-    """the inverse; vk_alphabeta_12 is ignored (see vk_to_json), nPublic must agree with len(IC) - 1"""
+def vk_from_json(src, device=0, lib: Optional[B.Library] = None, check_alphabeta=False) -> VerifyingKey:
+    """the inverse; nPublic must agree with len(IC) - 1.  vk_alphabeta_12 is ignored unless check_alphabeta=True: then
+    a present field is decoded (G16Error naming it if it is malformed or outside GT), e(alpha, beta) is recomputed on
+    the device and a mismatch raises G16Error naming the field; an absent field is accepted."""
     j = _load(src)
     _header(j, "verification_key.json")
     try:
@@ -230,16 +236,23 @@ def vk_from_json(src, device=0, lib: Optional[B.Library] = None) -> VerifyingKey
         raise _bad(f"verification_key.json: no {e.args[0]}") from None
     b1 = _encode(g1, "g1", device, lib, "vk_alpha_1/IC")
     b2 = _encode(g2, "g2", device, lib, "vk_beta_2/vk_gamma_2/vk_delta_2")
+    if check_alphabeta and "vk_alphabeta_12" in j:
+        try:
+            given = GT.from_snarkjs(j["vk_alphabeta_12"], validate=True, lib=lib, device=device)
+        except G16Error as e:
+            raise _bad(f"vk_alphabeta_12: {e}") from None
+        if given != pairing(b1[:64], b2[:128], device=device, lib=lib):
+            raise _bad("vk_alphabeta_12: not e(vk_alpha_1, vk_beta_2)")
     return VerifyingKey(b1[:64], b2[:128], b2[128:256], b2[256:],
                         np.frombuffer(b1[64:], dtype=np.uint8).reshape(-1, 64).copy())
 
 
-def write_vk_json(path, vk: VerifyingKey, device=0, lib: Optional[B.Library] = None) -> str:
-    return _dump(vk_to_json(vk, device, lib), path)
+def write_vk_json(path, vk: VerifyingKey, device=0, lib: Optional[B.Library] = None, alphabeta=False) -> str:
+    return _dump(vk_to_json(vk, device, lib, alphabeta), path)
 
 
-def read_vk_json(src, device=0, lib: Optional[B.Library] = None) -> VerifyingKey:
-    return vk_from_json(src, device, lib)
+def read_vk_json(src, device=0, lib: Optional[B.Library] = None, check_alphabeta=False) -> VerifyingKey:
+    return vk_from_json(src, device, lib, check_alphabeta)
 
 
 # ---- Ethereum forms --------------------------------------------------------------------------------------------

@@ -1036,6 +1036,59 @@ g16_status g16_pairing_check(int device, const uint8_t* g1 /* n x 64 */, const u
                              uint32_t n_pairs, uint8_t* ok_out);
 g16_status g16_verify_prepared_times(float* ms, uint32_t cap);
 
+/* ---- prepared inputs: arkworks' prepare_inputs / verify_proof_with_prepared_inputs ----------------------- */
+/* g16_pvk_prepare_inputs: out[64 i ..] = X_i = IC_0 + sum_j pub_ij IC_{j+1} for n input vectors (public_inputs as
+ *   g16_verify_prepared's), a packed affine G1 point (Montgomery; all-zero = infinity): the sum g16_verify_prepared
+ *   forms per proof, normalised.  n == 0: G16_OK, nothing is written.
+ * g16_verify_prepared_inputs: g16_verify_prepared with X_i GIVEN (prepared: n x 64 bytes) instead of computed: the
+ *   input ladder is skipped, every other rule and the verdicts are g16_verify_prepared's.  A prepared point with a
+ *   non-canonical word or off the curve gives ok_out[i] = 0 for that proof only.                                    */
+g16_status g16_pvk_prepare_inputs(g16_pvk* pvk, const uint64_t* public_inputs, uint32_t n, uint8_t* out /* n x 64 */);
+g16_status g16_verify_prepared_inputs(g16_pvk* pvk, const uint8_t* proofs, const uint8_t* prepared /* n x 64 */,
+                                      uint32_t n_proofs, uint8_t* ok_out);
+
+/* ---- pairing values: elements of GT (not on the proving path) ------------------------------------------------- */
+/* Every other pairing call answers "is this product 1?".  These return the VALUE, multiply and raise such values and
+ * carry them to and from the forms other software reads.
+ *
+ * Convention: a pairing value is ML(Q, P)^((q^12 - 1) / r * m) with m = 2 x (6 x^2 + 3 x + 1), x = 4965661367192848881:
+ *   the m-th power of the "plain" reduced pairing.  m is the cofactor of the Fuentes-Castaneda hard part, gcd(m, r) = 1,
+ *   and this is the value arkworks' Bn254::pairing and snarkjs (vk_alphabeta_12) give.
+ * Flat form: 12 x 32 bytes, the coefficient of w^i in Fq12 = Fq[w] / (w^12 - 18 w^6 + 82) at 32 i, 8 x u32 Montgomery
+ *   (g16_pvk_alpha_beta's basis).  Every gt / gt_out below is in it, 384 bytes per element.
+ * Ark form: ark-ff's Fq12::serialize, 384 bytes, 12 canonical little-endian Fq in tower order: for i < 6 the Fq2
+ *   coefficient (a_i + 9 a_{i+6}, a_{i+6}) is slot 3 (i & 1) + (i >> 1) of six 64-byte slots.  snarkjs' JSON nests
+ *   the same order as [2][3][2] decimal strings.
+ *
+ * g16_pairing_products: gt_out[i] = prod_{p in offsets[i] .. offsets[i+1]} e(g1[p], g2[p]) for n_products products,
+ *   one workgroup each, 0 to 16 pairs per product in ONE Miller loop (offsets: n_products + 1 entries from 0, non-
+ *   decreasing).  The structural rules are g16_pairing_check's: every word canonical, P on the curve, Q on the twist
+ *   and in G2; a pair with an infinite side contributes 1; an empty product is 1.  A product with a malformed point
+ *   is written as the all-zero element (not a member of GT) with ok_out[i] = 0, its neighbours are untouched.
+ *   ok_out may be NULL.  More than 16 pairs in a product: G16_ERR_INVALID, g16_last_error(NULL) names the product.
+ * g16_gt_multiexp: gt_out[i] = prod_{j in offsets[i] .. offsets[i+1]} gt[j]^scalars[j], one workgroup per output,
+ *   plain square-and-multiply in input order: the bytes depend on the input alone.  scalars: 4 x u64 little-endian
+ *   canonical integers, each BELOW r -- a scalar >= r is REFUSED (G16_ERR_INVALID, g16_last_error(NULL) names it),
+ *   never reduced silently.  The inverse of an element of GT is its (r - 1)-th power.  The inputs are not tested.
+ * g16_gt_to_ark / g16_gt_from_ark: the codec, one lane per element.  Decoding tests every word against q; with
+ *   validate != 0 it also tests membership, g^r = 1 (the same square-and-multiply with the exponent r).
+ *   reason_out[i] (may be NULL): 0 accepted, G16_KEY_BAD_NONCANONICAL, G16_KEY_BAD_SUBGROUP (outside GT); a refused
+ *   element is written as all-zero.  The status stays G16_OK.
+ * g16_pvk_alpha_g1_beta_g2: e(alpha_g1, beta_g2) of a prepared key, arkworks' PreparedVerifyingKey::alpha_g1_beta_g2,
+ *   flat form; computed on first use and kept.  (g16_pvk_alpha_beta is the raw Miller value of (beta, -alpha).)
+ * g16_gt_times: device milliseconds of the calling thread's last call above in 0 upload, 1 the G2 tests (products
+ *   only; beside 2 on a second stream), 2 kernels, 3 download; entries from 4 on are 0.
+ * n == 0: G16_OK and nothing is written.  Each call has its own streams and synchronises those, not the device.
+ * G16_ERR_NO_DEVICE without a device: there is no CPU fallback.                                                   */
+g16_status g16_pairing_products(int device, const uint8_t* g1, const uint8_t* g2, const uint32_t* offsets,
+                                uint32_t n_products, uint8_t* gt_out /* n x 384 */, uint8_t* ok_out);
+g16_status g16_gt_multiexp(int device, const uint8_t* gt, const uint64_t* scalars, const uint32_t* offsets,
+                           uint32_t n_out, uint8_t* gt_out);
+g16_status g16_gt_to_ark(int device, const uint8_t* gt, uint32_t n, uint8_t* out);
+g16_status g16_gt_from_ark(int device, const uint8_t* in, uint32_t n, int validate, uint8_t* gt_out, uint8_t* reason_out);
+g16_status g16_pvk_alpha_g1_beta_g2(const g16_pvk* pvk, uint8_t out[384]);
+g16_status g16_gt_times(float* ms, uint32_t cap);
+
 /* ---- loaders (host side, C++): see g16_loaders.h ---------------------------------------------- */
 
 #ifdef __cplusplus

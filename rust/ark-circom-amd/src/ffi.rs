@@ -393,6 +393,14 @@ extern "C" {
     pub fn g16_verify_prepared(pvk: *mut g16_pvk, proofs: *const u8, public_inputs: *const u64, n_proofs: u32, ok_out: *mut u8) -> g16_status;
     pub fn g16_pairing_check(device: c_int, g1: *const u8, g2: *const u8, n_pairs: u32, ok_out: *mut u8) -> g16_status;
     pub fn g16_verify_prepared_times(ms: *mut c_float, cap: u32) -> g16_status;
+    pub fn g16_pvk_prepare_inputs(pvk: *mut g16_pvk, public_inputs: *const u64, n: u32, out: *mut u8) -> g16_status;
+    pub fn g16_verify_prepared_inputs(pvk: *mut g16_pvk, proofs: *const u8, prepared: *const u8, n_proofs: u32, ok_out: *mut u8) -> g16_status;
+    pub fn g16_pairing_products(device: c_int, g1: *const u8, g2: *const u8, offsets: *const u32, n_products: u32, gt_out: *mut u8, ok_out: *mut u8) -> g16_status;
+    pub fn g16_gt_multiexp(device: c_int, gt: *const u8, scalars: *const u64, offsets: *const u32, n_out: u32, gt_out: *mut u8) -> g16_status;
+    pub fn g16_gt_to_ark(device: c_int, gt: *const u8, n: u32, out: *mut u8) -> g16_status;
+    pub fn g16_gt_from_ark(device: c_int, input: *const u8, n: u32, validate: c_int, gt_out: *mut u8, reason_out: *mut u8) -> g16_status;
+    pub fn g16_pvk_alpha_g1_beta_g2(pvk: *const g16_pvk, out: *mut u8) -> g16_status;
+    pub fn g16_gt_times(ms: *mut c_float, cap: u32) -> g16_status;
 
     // ---- include/g16_loaders.h -----------------------------------------------------------------
     pub fn g16_loader_last_error() -> *const c_char;
