@@ -48,7 +48,8 @@ __all__ = ["read_zkey", "R1CSFile", "R1CS", "CircomCircuit", "CircomBuilder", "C
            "verify_prepared_times", "Witness", "open_wtns", "write_wtns", "fr_from_canonical", "fr_from_canonical_times", "read_proof_json",
            "write_proof_json", "read_public_json", "write_public_json", "read_vk_json", "write_vk_json",
            "inputs_to_eth", "solidity_calldata", "GT", "gt_multiexp", "gt_from_ark", "gt_times", "pairing_products",
-           "pairing", "prepare_inputs", "verify_prepared_inputs"]
+           "pairing", "prepare_inputs", "verify_prepared_inputs", "MsmBases", "msm", "poly_divide_linear", "KzgKey",
+           "kzg_verify", "kzg_times"]
 
 FR_MODULUS = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 
@@ -2429,6 +2430,256 @@ def verify_prepared_times(lib: Optional[B.Library] = None) -> dict:
     ms = (C.c_float * len(VERIFY_PREPARED_PHASES))()
     lib.check(lib.g16_verify_prepared_times(ms, len(VERIFY_PREPARED_PHASES)))
     return dict(zip(VERIFY_PREPARED_PHASES, (float(x) for x in ms)))
+
+
+# ---- MSM over caller-supplied bases, division by (X - z), KZG (include/g16_amd.h) ---------------------------------
+GROUP_G1, GROUP_G2 = 0, 1
+MSM_SCALARS_CANONICAL, MSM_SCALARS_DEVICE, MSM_POINTS_DEVICE = 1, 2, 4
+POLY_RUN, POLY_BLOCK = 8, 256   # G16_POLY_RUN / G16_POLY_BLOCK: coefficients per lane, lanes per block of the division
+
+
+def _msm_group(group) -> int:
+    if group in (0, "g1", "G1"):
+        return GROUP_G1
+    if group in (1, "g2", "G2"):
+        return GROUP_G2
+    raise G16Error(B.G16_ERR_INVALID, "group is 'g1' or 'g2'")
+
+
+def _is_device_tensor(x) -> bool:
+    return hasattr(x, "data_ptr") and bool(getattr(x, "is_cuda", False))
+
+
+def _msm_points(points, group):
+    """packed affine points -> (pointer, count, flags, keepalive): an (n, 64 / 128) uint8 array, raw bytes, a list of
+    packed points, or a contiguous uint8 device tensor"""
+    width = 128 if group == GROUP_G2 else 64
+    if _is_device_tensor(points):
+        if points.element_size() != 1 or points.numel() % width or not points.is_contiguous():
+            raise G16Error(B.G16_ERR_INVALID, f"device points: a contiguous uint8 tensor of {width} bytes per point")
+        return C.c_void_p(points.data_ptr()), points.numel() // width, MSM_POINTS_DEVICE, points
+    if isinstance(points, (list, tuple)):
+        points = b"".join(bytes(p) for p in points)
+    if isinstance(points, (bytes, bytearray, memoryview)):
+        points = np.frombuffer(bytes(points), dtype=np.uint8)
+    a = np.ascontiguousarray(points, dtype=np.uint8)
+    if a.size % width:
+        raise G16Error(B.G16_ERR_INVALID, f"points: {width} bytes per point")
+    a = a.reshape(-1, width)
+    return _np_ptr(a), a.shape[0], 0, a
+
+
+def _msm_scalars(scalars):
+    """scalar vectors -> (pointer, len, count, flags, keepalive, batched).  Accepted: ints (a sequence = one vector, a
+    sequence of sequences = a batch), canonical little-endian values ((len, 32) / (count, len, 32) uint8 array or
+    bytes), Montgomery limbs ((len, 4) / (count, len, 4) uint64 array), and contiguous device tensors of either
+    form (uint8 with 32 bytes per value: canonical; 64-bit with 4 words per value: Montgomery)."""
+    if _is_device_tensor(scalars):
+        t = scalars
+        if not t.is_contiguous() or t.dim() not in (2, 3):
+            raise G16Error(B.G16_ERR_INVALID, "device scalars: a contiguous (len, w) or (count, len, w) tensor")
+        canon = t.element_size() == 1 and t.shape[-1] == 32
+        if not canon and not (t.element_size() == 8 and t.shape[-1] == 4):
+            raise G16Error(B.G16_ERR_INVALID, "device scalars: uint8 x 32 (canonical) or 64-bit x 4 (Montgomery) per value")
+        batched = t.dim() == 3
+        return (C.c_void_p(t.data_ptr()), int(t.shape[-2]), int(t.shape[0]) if batched else 1,
+                MSM_SCALARS_DEVICE | (MSM_SCALARS_CANONICAL if canon else 0), t, batched)
+    if isinstance(scalars, np.ndarray) and scalars.dtype == np.uint64:
+        if scalars.ndim not in (2, 3) or scalars.shape[-1] != 4:
+            raise G16Error(B.G16_ERR_INVALID, "Montgomery scalars: a (len, 4) or (count, len, 4) uint64 array")
+        a = np.ascontiguousarray(scalars)
+        return _np_ptr(a), a.shape[-2], a.shape[0] if a.ndim == 3 else 1, 0, a, a.ndim == 3
+    if isinstance(scalars, np.ndarray) and scalars.dtype == np.uint8 and scalars.ndim == 3:
+        if scalars.shape[-1] != 32:
+            raise G16Error(B.G16_ERR_INVALID, "canonical scalars: 32 bytes per value")
+        a = np.ascontiguousarray(scalars)
+        return _np_ptr(a), a.shape[1], a.shape[0], MSM_SCALARS_CANONICAL, a, True
+    if isinstance(scalars, (np.ndarray, bytes, bytearray, memoryview)):
+        a = _canonical_bytes(scalars)
+        return _np_ptr(a), a.shape[0], 1, MSM_SCALARS_CANONICAL, a, False
+    rows = list(scalars)
+    if rows and isinstance(rows[0], (list, tuple, np.ndarray)):
+        if len({len(r) for r in rows}) != 1:
+            raise G16Error(B.G16_ERR_INVALID, "a batch of scalar vectors: every vector of the same length")
+        a = np.stack([_canonical_bytes([int(v) for v in r]) for r in rows]) if len(rows[0]) else \
+            np.zeros((len(rows), 0, 32), dtype=np.uint8)
+        return _np_ptr(a), a.shape[1], a.shape[0], MSM_SCALARS_CANONICAL, a, True
+    a = _canonical_bytes([int(v) for v in rows])
+    return _np_ptr(a), a.shape[0], 1, MSM_SCALARS_CANONICAL, a, False
+
+
+class MsmBases:
+    """The MSM engine over bases the caller supplies (ark-ec VariableBaseMSM::msm): g16_msm_bases_create.  points:
+    packed affine points in the zkey encoding (64 bytes for 'g1', 128 for 'g2'; Montgomery; all-zero = infinity) as
+    an array, bytes, a list of packed points or a uint8 device tensor.  planes: stored multiples per point (None: as
+    many as fit the device memory, 1: none precomputed); max_batch: scalar vectors summed in one pass; validate: test
+    every point first (canonical, on the curve, G2: in the subgroup) -- a bad point raises G16Error naming it."""
+
+    def __init__(self, points, group="g1", planes=None, max_batch=1, validate=False, window_bits=None, device=0,
+                 lib: Optional[B.Library] = None):
+        self.lib = lib or B.load()
+        self.group = _msm_group(group)
+        ptr, n, flags, keep = _msm_points(points, self.group)
+        opt = B.MsmOptions(int(window_bits or 0), int(planes or 0), int(max_batch), 1 if validate else 0)
+        h = C.c_void_p()
+        self.lib.check(self.lib.g16_msm_bases_create(device, self.group, ptr, n, flags, C.byref(opt), C.byref(h)))
+        self._h = _Handle(self.lib, h, self.lib.g16_msm_bases_destroy)
+        self.n = n
+        self.point_bytes = 128 if self.group == GROUP_G2 else 64
+
+    def info(self) -> dict:
+        out = (C.c_uint32 * 8)()
+        self.lib.check(self.lib.g16_msm_bases_info(self._h.ptr, out))
+        return dict(zip(("group", "n", "window_bits", "windows", "planes", "bucket_sets", "batch", "validated"),
+                        (int(x) for x in out)))
+
+    def msm(self, scalars):
+        """sum_i scalars[i] * points[i] over the first len(scalars) bases: the packed affine point (bytes; all-zero =
+        infinity).  A 2-D input (a sequence of vectors, a (count, len, w) array or tensor) is a batch: a list of
+        points, one per vector."""
+        ptr, ln, count, flags, keep, batched = _msm_scalars(scalars)
+        out = np.zeros((max(count, 1), self.point_bytes), dtype=np.uint8)
+        self.lib.check(self.lib.g16_msm(self._h.ptr, ptr, ln, count, ln, flags, _np_ptr(out)))
+        res = [out[k].tobytes() for k in range(count)]
+        return res if batched else res[0]
+
+    def close(self):
+        self._h.__del__()
+
+
+def msm(points, scalars, group="g1", device=0, lib: Optional[B.Library] = None) -> bytes:
+    """One MSM over bases used once (g16_msm_once; arkworks' G1Projective::msm(bases, scalars)): no planes are
+    precomputed and nothing stays on the device.  The packed affine point."""
+    lib = lib or B.load()
+    g = _msm_group(group)
+    pptr, n, pflags, pkeep = _msm_points(points, g)
+    sptr, ln, count, sflags, skeep, batched = _msm_scalars(scalars)
+    if batched or ln != n:
+        raise G16Error(B.G16_ERR_INVALID, "msm: one scalar per point (MsmBases.msm takes batches and shorter vectors)")
+    out = np.zeros(128 if g == GROUP_G2 else 64, dtype=np.uint8)
+    lib.check(lib.g16_msm_once(device, g, pptr, sptr, n, pflags | sflags, _np_ptr(out)))
+    return out.tobytes()
+
+
+def poly_divide_linear(coeffs, z, device=0, lib: Optional[B.Library] = None):
+    """p(X) = q(X) (X - z) + y on the GPU (g16_poly_divide_linear).  coeffs: one polynomial (coefficient of X^i at i)
+    or a batch of equally long ones, in any host form MsmBases.msm takes; z: one point per polynomial (ints or
+    Montgomery limbs).  Returns (q, y) as ints -- q a list of n - 1 coefficients -- or a list of such pairs for a batch."""
+    lib = lib or B.load()
+    ptr, n, count, flags, keep, batched = _msm_scalars(coeffs)
+    if flags & MSM_SCALARS_DEVICE:
+        raise G16Error(B.G16_ERR_INVALID, "poly_divide_linear: host coefficients (KzgKey.open keeps quotients on the device)")
+    zs = list(z) if isinstance(z, (list, tuple, np.ndarray)) else [z]
+    if isinstance(z, np.ndarray) and z.dtype == np.uint64:
+        zarr = np.ascontiguousarray(z).reshape(-1, 4)
+        zarr = zarr if not (flags & MSM_SCALARS_CANONICAL) else _canonical_bytes(fr_to_ints(zarr, lib))
+    else:
+        zarr = _canonical_bytes([int(v) for v in zs]) if flags & MSM_SCALARS_CANONICAL else fr_from_ints(zs, lib)
+    if zarr.shape[0] != count:
+        raise G16Error(B.G16_ERR_INVALID, "poly_divide_linear: one point z per polynomial")
+    quot = np.zeros((count, max(n - 1, 0), 4), dtype=np.uint64)
+    rem = np.zeros((count, 4), dtype=np.uint64)
+    lib.check(lib.g16_poly_divide_linear(device, ptr, n, count, _np_ptr(zarr), flags, _np_ptr(quot), _np_ptr(rem)))
+    ys = fr_to_ints(rem, lib)
+    res = [(fr_to_ints(quot[k], lib) if n > 1 else [], ys[k]) for k in range(count)]
+    return res if batched else res[0]
+
+
+KZG_PHASES = ("input", "divide_or_scalars", "msm", "output_or_pairing")
+
+
+def kzg_times(lib: Optional[B.Library] = None) -> dict:
+    """device milliseconds per phase of this thread's last KzgKey.open / kzg_verify (g16_kzg_times)"""
+    lib = lib or B.load()
+    ms = (C.c_float * len(KZG_PHASES))()
+    lib.check(lib.g16_kzg_times(ms, len(KZG_PHASES)))
+    return dict(zip(KZG_PHASES, (float(x) for x in ms)))
+
+
+def _kzg_points(x, what) -> np.ndarray:
+    if isinstance(x, (bytes, bytearray, memoryview)):
+        x = np.frombuffer(bytes(x), dtype=np.uint8)
+    elif isinstance(x, (list, tuple)):
+        x = np.frombuffer(b"".join(bytes(p) for p in x), dtype=np.uint8)
+    a = np.ascontiguousarray(x, dtype=np.uint8)
+    if a.size % 64:
+        raise G16Error(B.G16_ERR_INVALID, f"{what}: 64 bytes per G1 point")
+    return a.reshape(-1, 64)
+
+
+def kzg_verify(tau_g2, commitments, z, y, proofs, rho=None, device=0, lib: Optional[B.Library] = None) -> bool:
+    """One verdict for a batch of KZG openings (g16_kzg_verify) by a caller that holds only tau_g2 = tau G2 (128
+    bytes): e(sum rho_i (C_i - y_i G + z_i pi_i), G2) == e(sum rho_i pi_i, tau G2).  commitments, proofs: packed G1
+    points; z, y: ints or Montgomery limbs; rho: None (the library draws 128-bit coefficients) or ints in [1, 2^128)."""
+    lib = lib or B.load()
+    cm, pf = _kzg_points(commitments, "commitments"), _kzg_points(proofs, "proofs")
+    zz, yy = _as_fr(z, lib), _as_fr(y, lib)
+    n = cm.shape[0]
+    if not (pf.shape[0] == zz.shape[0] == yy.shape[0] == n):
+        raise G16Error(B.G16_ERR_INVALID, "kzg_verify: one commitment, point, value and proof per opening")
+    t2 = np.frombuffer(bytes(tau_g2), dtype=np.uint8)
+    if t2.size != 128:
+        raise G16Error(B.G16_ERR_INVALID, "kzg_verify: tau_g2 is one packed G2 point (128 bytes)")
+    r = _rho_array(rho, n, "kzg_verify: one coefficient per opening")
+    ok = C.c_uint8(0)
+    lib.check(lib.g16_kzg_verify(device, _np_ptr(t2), _np_ptr(cm), _np_ptr(zz), _np_ptr(yy), _np_ptr(pf), n,
+                                 None if r is None else _np_ptr(r), C.byref(ok)))
+    return bool(ok.value)
+
+
+class KzgKey:
+    """A KZG commitment key on a powers-of-tau string (g16_kzg_key_create): the MSM engine over srs.tau_g1[:max_len]
+    with precomputed planes, and tau_g2[1].  The string is used as it comes: check_srs verifies one."""
+
+    def __init__(self, srs: Srs, max_len=None, planes=None, max_batch=1, device=0, lib: Optional[B.Library] = None):
+        self.lib = lib or B.load()
+        self.device = device
+        d = srs.to_c()
+        opt = B.MsmOptions(0, int(planes or 0), int(max_batch), 0)
+        h = C.c_void_p()
+        self.lib.check(self.lib.g16_kzg_key_create(device, C.byref(d), int(max_len or 0), C.byref(opt), C.byref(h)))
+        self._h = _Handle(self.lib, h, self.lib.g16_kzg_key_destroy)
+        self.max_len = int(max_len or srs.tau_g1.shape[0])
+        self.tau_g2 = srs.tau_g2[1].tobytes()
+
+    def info(self) -> dict:
+        out = (C.c_uint32 * 8)()
+        self.lib.check(self.lib.g16_kzg_key_info(self._h.ptr, out))
+        return dict(zip(("group", "n", "window_bits", "windows", "planes", "bucket_sets", "batch", "validated"),
+                        (int(x) for x in out)))
+
+    def commit(self, coeffs):
+        """p(tau) G for one coefficient vector, or a list of commitments for a batch (forms: MsmBases.msm)"""
+        ptr, ln, count, flags, keep, batched = _msm_scalars(coeffs)
+        out = np.zeros((max(count, 1), 64), dtype=np.uint8)
+        self.lib.check(self.lib.g16_kzg_commit(self._h.ptr, ptr, ln, count, ln, flags, _np_ptr(out)))
+        res = [out[k].tobytes() for k in range(count)]
+        return res if batched else res[0]
+
+    def open(self, coeffs, z):
+        """(y, proof) = (p(z) as an int, q(tau) G as 64 bytes) with q = (p - y) / (X - z); a batch of polynomials with
+        one z each gives a list of pairs.  The quotients never leave the device."""
+        ptr, ln, count, flags, keep, batched = _msm_scalars(coeffs)
+        zs = list(z) if isinstance(z, (list, tuple, np.ndarray)) else [z]
+        zarr = _canonical_bytes([int(v) for v in zs]) if flags & MSM_SCALARS_CANONICAL else fr_from_ints(zs, self.lib)
+        if zarr.shape[0] != count:
+            raise G16Error(B.G16_ERR_INVALID, "open: one point z per polynomial")
+        y = np.zeros((max(count, 1), 4), dtype=np.uint64)
+        pf = np.zeros((max(count, 1), 64), dtype=np.uint8)
+        self.lib.check(self.lib.g16_kzg_open(self._h.ptr, ptr, ln, count, ln, _np_ptr(zarr), flags, _np_ptr(y),
+                                             _np_ptr(pf)))
+        ys = fr_to_ints(y[:count], self.lib)
+        res = [(ys[k], pf[k].tobytes()) for k in range(count)]
+        return res if batched else res[0]
+
+    def verify(self, commitments, z, y, proofs, rho=None) -> bool:
+        """kzg_verify under this key's tau_g2; single values are a batch of one"""
+        if isinstance(commitments, (bytes, bytearray)) and len(commitments) == 64 and not isinstance(z, (list, tuple, np.ndarray)):
+            z, y = [z], [y]
+        return kzg_verify(self.tau_g2, commitments, z, y, proofs, rho=rho, device=self.device, lib=self.lib)
+
+    def close(self):
+        self._h.__del__()
 
 
 class _Reduction:

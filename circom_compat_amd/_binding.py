@@ -138,6 +138,10 @@ class SrsLagrangeReportC(C.Structure):
                 ("n_listed", C.c_uint32)]
 
 
+class MsmOptions(C.Structure):
+    _fields_ = [("window_bits", C.c_int), ("planes", C.c_int), ("max_batch", C.c_int), ("validate", C.c_int)]
+
+
 class PtauHeader(C.Structure):
     _fields_ = [("n8q", C.c_uint32), ("q", C.c_uint8 * 32), ("power", C.c_uint32), ("ceremony_power", C.c_uint32)]
 
@@ -198,6 +202,10 @@ ABI_SYMBOLS = [
     "g16_gt_times",
     "g16_fr_convert", "g16_fr_convert_times", "g16_witness_upload_canonical", "g16_prove_canonical", "g16_prove_batch_canonical",
     "g16_wtns_open", "g16_wtns_open_mem", "g16_wtns_count", "g16_wtns_values", "g16_wtns_close",
+    "g16_msm_bases_create", "g16_msm_bases_destroy", "g16_msm_bases_info", "g16_msm", "g16_msm_once",
+    "g16_poly_divide_linear",
+    "g16_kzg_key_create", "g16_kzg_key_destroy", "g16_kzg_key_info", "g16_kzg_commit", "g16_kzg_open", "g16_kzg_verify",
+    "g16_kzg_times",
 ]
 
 
@@ -379,6 +387,21 @@ class Library:
             "g16_wtns_count": (C.c_uint32, [vp]),
             "g16_wtns_values": (vp, [vp]),
             "g16_wtns_close": (None, [vp]),
+            "g16_msm_bases_create": (C.c_int, [C.c_int, C.c_int, vp, C.c_size_t, C.c_uint32, C.POINTER(MsmOptions),
+                                               C.POINTER(vp)]),
+            "g16_msm_bases_destroy": (None, [vp]),
+            "g16_msm_bases_info": (C.c_int, [vp, _u32p]),
+            "g16_msm": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint32, vp]),
+            "g16_msm_once": (C.c_int, [C.c_int, C.c_int, vp, vp, C.c_size_t, C.c_uint32, vp]),
+            "g16_poly_divide_linear": (C.c_int, [C.c_int, vp, C.c_size_t, C.c_size_t, vp, C.c_uint32, vp, vp]),
+            "g16_kzg_key_create": (C.c_int, [C.c_int, C.POINTER(SrsDesc), C.c_size_t, C.POINTER(MsmOptions),
+                                             C.POINTER(vp)]),
+            "g16_kzg_key_destroy": (None, [vp]),
+            "g16_kzg_key_info": (C.c_int, [vp, _u32p]),
+            "g16_kzg_commit": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint32, vp]),
+            "g16_kzg_open": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, vp, C.c_uint32, vp, vp]),
+            "g16_kzg_verify": (C.c_int, [C.c_int, vp, vp, vp, vp, vp, C.c_size_t, vp, vp]),
+            "g16_kzg_times": (C.c_int, [C.POINTER(C.c_float), C.c_uint32]),
         }
         # measurement builds only (make EXTRA=-DG16_DEBUG_ABI; include/g16_amd.h): not an ABI symbol, never "missing"
         optional = {"g16_debug_alu_bench": (C.c_int, [C.c_int, C.c_int, C.c_uint32, C.c_uint32,

@@ -1089,6 +1089,99 @@ g16_status g16_gt_from_ark(int device, const uint8_t* in, uint32_t n, int valida
 g16_status g16_pvk_alpha_g1_beta_g2(const g16_pvk* pvk, uint8_t out[384]);
 g16_status g16_gt_times(float* ms, uint32_t cap);
 
+/* ---- MSM over caller-supplied bases (ark-ec VariableBaseMSM::msm / msm_bigint) ---------------- */
+/* g16_msm_g1 / g16_msm_g2 run the MSM engine over the queries of a resident proving key.  The calls below point the
+ * same engine -- the digit sort, the entry-balanced accumulation, its fix-up and the bucket reduction, unchanged -- at
+ * any bases.
+ * Handle: g16_msm_bases_create uploads n packed affine points (64 / 128 bytes, Montgomery, all-zero = infinity: the
+ *   zkey encoding of every other call; group = G16_GROUP_G1 / G16_GROUP_G2), converts them to the engine's internal
+ *   form and fills the precomputed planes.  n <= 2^27.  flags: G16_MSM_POINTS_DEVICE when `points` is device memory.
+ *   opt may be NULL (all defaults).  opt->window_bits <= 0: the window msm_make_config picks for n.  opt->planes <= 0:
+ *   as many planes as fit the device memory free at the call (the plan of g16_ctx_create), 1: no precomputation.
+ *   opt->max_batch (<= 0: 1): scalar vectors handled by ONE sort, accumulation and reduction; the sort and partial-sum
+ *   workspaces are sized for it (it is lowered where max_batch x n x windows would not fit a 32-bit entry index;
+ *   g16_msm_bases_info out[6] has the value in use).  opt->validate != 0: every point is tested first with the
+ *   predicates of g16_key_check -- canonical words, the curve, and for G2 the prime-order subgroup; the first point
+ *   that fails gives G16_ERR_INVALID and g16_last_error(NULL) names its index and reason.  Without it the points are
+ *   taken as they come (as g16_setup_from_srs takes an SRS).
+ * g16_msm_bases_info: out[0] = group, [1] = n, [2] = window bits c, [3] = windows W, [4] = planes, [5] = bucket sets D,
+ *   [6] = vectors per chunk, [7] = 1 when the points were validated.
+ * g16_msm: out[k] = sum_{i < len} scalars[k * stride + i] * points[i] for k < count; len <= n, stride >= len (in
+ *   scalars; ignored for count == 1).  flags: G16_MSM_SCALARS_CANONICAL -- 32-byte little-endian integers below r
+ *   instead of 4 x u64 Montgomery Fr; they go through the conversion kernel of g16_fr_convert, and a value >= r gives
+ *   G16_ERR_INVALID with its index (vector * len + element) in g16_last_error(NULL).  G16_MSM_SCALARS_DEVICE: `scalars`
+ *   is device memory on the handle's device.  out: count affine points of 64 / 128 bytes on the host, all-zero =
+ *   infinity (also the answer for len == 0).  Vectors are processed in chunks of the handle's batch.  One call in
+ *   flight per handle (the handle holds a mutex); several handles run side by side.  The bytes do not depend on
+ *   planes, window, batch or chunking: affine points have one encoding.
+ * g16_msm_once: bases used once -- the planes = 1 configuration (as many bucket sets as windows, folded by the Horner
+ *   kernel): no plane is computed and nothing allocated outlives the call.  flags as above (both kinds).           */
+enum { G16_GROUP_G1 = 0, G16_GROUP_G2 = 1 };
+enum { G16_MSM_SCALARS_CANONICAL = 1, G16_MSM_SCALARS_DEVICE = 2, G16_MSM_POINTS_DEVICE = 4 };
+typedef struct {
+  int window_bits;
+  int planes;
+  int max_batch;
+  int validate;
+} g16_msm_options;
+typedef struct g16_msm_bases g16_msm_bases;
+g16_status g16_msm_bases_create(int device, int group, const void* points, size_t n, uint32_t flags,
+                                const g16_msm_options* opt, g16_msm_bases** out);
+void g16_msm_bases_destroy(g16_msm_bases* h);
+g16_status g16_msm_bases_info(const g16_msm_bases* h, uint32_t out[8]);
+g16_status g16_msm(g16_msm_bases* h, const void* scalars, size_t len, size_t count, size_t stride, uint32_t flags,
+                   uint8_t* out);
+g16_status g16_msm_once(int device, int group, const void* points, const void* scalars, size_t n, uint32_t flags,
+                        uint8_t* out);
+
+/* ---- division by (X - z) ---------------------------------------------------------------------------------------- */
+/* For each of count polynomials p_k of n coefficients (coeffs[k * n + i] is the coefficient of X^i) and its own point
+ * z[k]:  p_k(X) = q_k(X) (X - z_k) + y_k.  quot_out: count x (n - 1) coefficients, rem_out: count values y_k = p_k(z_k).
+ * 1 <= n <= 2^27.  Everything is 4 x u64 Montgomery Fr unless flags has G16_MSM_SCALARS_CANONICAL (then coeffs and z
+ * are 32-byte little-endian integers below r, refused with their index otherwise; the outputs stay Montgomery).
+ * G16_MSM_SCALARS_DEVICE: coeffs and quot_out are device memory (z and rem_out stay on the host).
+ * The suffix recurrence s_i = a_i + z s_(i+1) in three phases: every thread runs Horner over its own run of
+ * G16_POLY_RUN coefficients; the run values are combined across the G16_POLY_BLOCK threads of a block and then
+ * across blocks with the weights z^RUN and z^(RUN x BLOCK); a second pass over each run, seeded with the carry from
+ * the right, writes the quotient.  No atomics, a fixed combination order: the same bytes on every run.            */
+#define G16_POLY_RUN 8
+#define G16_POLY_BLOCK 256
+g16_status g16_poly_divide_linear(int device, const void* coeffs, size_t n, size_t count, const void* z,
+                                  uint32_t flags, void* quot_out, uint64_t* rem_out);
+
+/* ---- KZG on a powers-of-tau string ------------------------------------------------------------------------------ */
+/* Key: an MSM handle over srs->tau_g1[0, max_len) (max_len == 0: all n_tau_g1 entries) with planes -- a commitment key
+ *   is reused -- and tau_g2[1].  opt as for g16_msm_bases_create (validate is ignored).  The SRS is taken as it comes:
+ *   g16_srs_check is the call that verifies one, run it once on a string that was not minted locally.
+ * g16_kzg_commit: g16_msm on the key's bases: out[k] = p_k(tau) G for coefficient vectors of len <= max_len.
+ * g16_kzg_open: for each polynomial and its point z[k] (count x 32 bytes on the host, in the scalars' encoding):
+ *   y_out[k] = p_k(z_k) (4 x u64 Montgomery) and proof_out[k] = q_k(tau) G (64 bytes).  The division above leaves the
+ *   quotients in device memory and the chunked MSM reads them there: count x (32 + 64) bytes come back to the host.
+ *   len == 1: the proof is the point at infinity.  len == 0 or len > max_len: G16_ERR_INVALID.
+ * g16_kzg_verify: ONE verdict for n openings (C_i, z_i, y_i, pi_i):
+ *     e(sum_i rho_i (C_i - y_i G + z_i pi_i), G2) = e(sum_i rho_i pi_i, tau_g2)
+ *   two one-shot G1 MSMs, the scalar sum_i rho_i y_i and one two-pair pairing check.  commitments, proofs: n x 64
+ *   bytes; z, y: n x 4 u64 Montgomery Fr; tau_g2: tau_g2[1] of the string.  rho: n x 2 u64 (128-bit integers, every
+ *   one non-zero, else G16_ERR_INVALID) or NULL: drawn from the operating system's CSPRNG as g16_verify_aggregate
+ *   does (no fixed fallback); a wrong opening passes with probability at most 2^-127 when rho is unpredictable.
+ *   Commitments and proofs are tested for canonical words and the curve first, tau_g2 for the twist and the subgroup;
+ *   any failure makes *ok_out = 0.  n == 0: *ok_out = 1.  No per-item verdicts: a caller bisects.
+ * g16_kzg_times: device milliseconds of the calling thread's last open / verify: 0 upload + conversion, 1 division
+ *   (open) or scalar preparation (verify), 2 MSM, 3 download (open) or pairing check (verify); from 4 on 0.
+ * NOT built: multi-point openings, per-item verdicts, anything PLONK.                                              */
+typedef struct g16_kzg_key g16_kzg_key;
+g16_status g16_kzg_key_create(int device, const g16_srs_desc* srs, size_t max_len, const g16_msm_options* opt,
+                              g16_kzg_key** out);
+void g16_kzg_key_destroy(g16_kzg_key* k);
+g16_status g16_kzg_key_info(const g16_kzg_key* k, uint32_t out[8]);
+g16_status g16_kzg_commit(g16_kzg_key* k, const void* coeffs, size_t len, size_t count, size_t stride, uint32_t flags,
+                          uint8_t* out);
+g16_status g16_kzg_open(g16_kzg_key* k, const void* coeffs, size_t len, size_t count, size_t stride, const void* z,
+                        uint32_t flags, uint64_t* y_out, uint8_t* proof_out);
+g16_status g16_kzg_verify(int device, const uint8_t tau_g2[128], const uint8_t* commitments, const uint64_t* z,
+                          const uint64_t* y, const uint8_t* proofs, size_t n, const uint64_t* rho, uint8_t* ok_out);
+g16_status g16_kzg_times(float* ms, uint32_t cap);
+
 /* ---- loaders (host side, C++): see g16_loaders.h ---------------------------------------------- */
 
 #ifdef __cplusplus

@@ -84,6 +84,29 @@ pub struct g16_ark_pk {
 pub struct g16_pvk {
     _private: [u8; 0],
 }
+#[repr(C)]
+pub struct g16_msm_bases {
+    _private: [u8; 0],
+}
+#[repr(C)]
+pub struct g16_kzg_key {
+    _private: [u8; 0],
+}
+
+pub const G16_GROUP_G1: c_int = 0;
+pub const G16_GROUP_G2: c_int = 1;
+pub const G16_MSM_SCALARS_CANONICAL: u32 = 1;
+pub const G16_MSM_SCALARS_DEVICE: u32 = 2;
+pub const G16_MSM_POINTS_DEVICE: u32 = 4;
+
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct g16_msm_options {
+    pub window_bits: c_int,
+    pub planes: c_int,
+    pub max_batch: c_int,
+    pub validate: c_int,
+}
 
 // arkworks serialization (include/g16_amd.h): the extra per-point reason bit, the groups, the flags
 pub const G16_KEY_BAD_ENCODING: u32 = 8;
@@ -401,6 +424,19 @@ extern "C" {
     pub fn g16_gt_from_ark(device: c_int, input: *const u8, n: u32, validate: c_int, gt_out: *mut u8, reason_out: *mut u8) -> g16_status;
     pub fn g16_pvk_alpha_g1_beta_g2(pvk: *const g16_pvk, out: *mut u8) -> g16_status;
     pub fn g16_gt_times(ms: *mut c_float, cap: u32) -> g16_status;
+    pub fn g16_msm_bases_create(device: c_int, group: c_int, points: *const c_void, n: usize, flags: u32, opt: *const g16_msm_options, out: *mut *mut g16_msm_bases) -> g16_status;
+    pub fn g16_msm_bases_destroy(h: *mut g16_msm_bases);
+    pub fn g16_msm_bases_info(h: *const g16_msm_bases, out: *mut u32) -> g16_status;
+    pub fn g16_msm(h: *mut g16_msm_bases, scalars: *const c_void, len: usize, count: usize, stride: usize, flags: u32, out: *mut u8) -> g16_status;
+    pub fn g16_msm_once(device: c_int, group: c_int, points: *const c_void, scalars: *const c_void, n: usize, flags: u32, out: *mut u8) -> g16_status;
+    pub fn g16_poly_divide_linear(device: c_int, coeffs: *const c_void, n: usize, count: usize, z: *const c_void, flags: u32, quot_out: *mut c_void, rem_out: *mut u64) -> g16_status;
+    pub fn g16_kzg_key_create(device: c_int, srs: *const g16_srs_desc, max_len: usize, opt: *const g16_msm_options, out: *mut *mut g16_kzg_key) -> g16_status;
+    pub fn g16_kzg_key_destroy(k: *mut g16_kzg_key);
+    pub fn g16_kzg_key_info(k: *const g16_kzg_key, out: *mut u32) -> g16_status;
+    pub fn g16_kzg_commit(k: *mut g16_kzg_key, coeffs: *const c_void, len: usize, count: usize, stride: usize, flags: u32, out: *mut u8) -> g16_status;
+    pub fn g16_kzg_open(k: *mut g16_kzg_key, coeffs: *const c_void, len: usize, count: usize, stride: usize, z: *const c_void, flags: u32, y_out: *mut u64, proof_out: *mut u8) -> g16_status;
+    pub fn g16_kzg_verify(device: c_int, tau_g2: *const u8, commitments: *const u8, z: *const u64, y: *const u64, proofs: *const u8, n: usize, rho: *const u64, ok_out: *mut u8) -> g16_status;
+    pub fn g16_kzg_times(ms: *mut c_float, cap: u32) -> g16_status;
 
     // ---- include/g16_loaders.h -----------------------------------------------------------------
     pub fn g16_loader_last_error() -> *const c_char;
