@@ -1,4 +1,5 @@
-// verify.hip -- Groth16 batch verification on the GPU (first half).
+// verify.hip -- Groth16 verification on the GPU, per proof and aggregate, for proofs under one key or under many
+// (first half).
 //
 // Replaces, for a batch of proofs under one verifying key,
 //   let pvk = Groth16::<Bn254>::process_vk(&params.vk)?;
@@ -17,30 +18,115 @@
 // Off the proving path and deliberately simple: ONE LANE PER PROOF, saturated-limb field.h
 // arithmetic, ~1.4 x 10^5 Fq multiplications per proof -- a throughput kernel for large batches,
 // not a latency win over one CPU core for a single proof.
+//
+// Aggregate verification: the proofs of a GROUP (one key with the proofs under it) in ONE combined
+// pairing check.  With coefficients rho_i (128-bit, unknown to whoever made the proofs) the group's
+// per-proof equations fold into
+//   prod_i ML(B_i, rho_i A_i) * ML(beta, -(sum rho_i) alpha) * ML(gamma, -sum rho_i X_i)
+//       * ML(delta, -sum rho_i C_i)   --final exponentiation-->   1,
+//   sum_i rho_i X_i = (sum_i rho_i) IC_0 + sum_j (sum_i rho_i pub_ij) IC_{j+1}
+// (the small-exponent batch test).  Per proof that is one Miller loop, two 128-bit G1
+// multiplications and the structural checks; the key-side Miller loops and the final
+// exponentiation are paid once per group.  The long serial pieces sit in separate lanes:
+//   k_agg_front   grid (front blocks, 3).  blockIdx.y = 0: structural checks (incl. the 254-bit subgroup
+//                 multiplication); 1: P_i = rho_i A_i (affine); 2: rho_i C_i and rho_i pub_ij, summed
+//                 per block through LDS, the loop over j bounded by the block's own n_pub
+//   k_agg_sums    per group n_pub + 2 blocks over that group's block partials: -sum rho_i C_i, the
+//                 columns s_j = sum_i rho_i pub_ij, and one lane for -(sum rho_i) alpha
+//   k_agg_x       one block per group over its own IC range: -((sum rho) IC_0 + sum_j s_j IC_{j+1}),
+//                 one lane per term, LDS sum
+//   k_agg_miller  count + 3 lanes per group, one Miller loop each; per-block product through LDS
+//   k_agg_tail    one block per group: product of the group's block products, AND of its structural
+//                 flags, final exponentiation in one lane -- all groups side by side
+// Per-proof path: k_verify_prepare (ml_alpha_beta, one lane per key), k_verify_batch (one lane per proof,
+// the lane's key from front[]).
+// What a call costs is a serial chain -- front, one Miller loop, one final exponentiation -- that is
+// one lane's work and almost flat in the batch size.  Nothing in the chain depends on the key except
+// three G2 points and the IC row, so the groups of a call share every launch: the per-proof lanes of all
+// groups run side by side, every reduction is per group, and the K final exponentiations are K lanes of
+// one launch.  g16_verify_batch and g16_verify_aggregate are the calls with ONE group.
+//
+// Host tables (built once per call, uploaded in one copy each):
+//   KeyTab[k]      the group's key material offsets (VkDev k, first IC point, n_pub, first public input as
+//                  a 64-bit offset), its proofs [first, first + count), its blocks and sum_i rho_i
+//   front[b]       (key, first proof, live lanes) of block b of the per-proof front: a group of count
+//                  proofs owns ceil(count / AGG_BLOCK) blocks of its own, so NO BLOCK STRADDLES TWO
+//                  GROUPS and the LDS tree sums of the front are per group by construction
+//   miller[b]      (key, first lane within the group, live lanes) of block b of the Miller lanes: a
+//                  non-empty group owns ceil((count + 3) / AGG_BLOCK) blocks -- count proof lanes, then
+//                  its three key-side lanes.  Blocks do not mix groups (the block product is NOT
+//                  segmented), so a block product belongs to one group's equation
+// No atomics: every reduction is a fixed tree over a fixed range, so the bytes of every intermediate
+// do not depend on scheduling.  The number of launches, allocations, copies and synchronisations of a
+// call does not depend on the number of keys.
 #include "../../include/g16_amd.h"
 
-#include <memory>
+#include <vector>
 
 #include "keycheck.h"
 #include "pairing.h"
-#include "verify_agg.h"
 
 namespace g16 {
 namespace {
 
-__global__ void k_verify_prepare(VkDev* vk) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+constexpr uint32_t AGG_BLOCK = 64;  // lanes per block of every kernel here
+
+struct AggKey {
+  G1Affine p[3];  // G1 sides paired with beta, gamma, delta
+};
+
+struct KeyTab {
+  uint64_t pub_off;    // first Fr of the group's public-input block
+  uint64_t spart_off;  // first Fr of the group's per-block column partials (n_pub x nfb, column-major)
+  uint32_t ic_off;     // first IC point of the key; also its first scalar in scal[]
+  uint32_t n_pub;
+  uint32_t first, count;  // the group's proofs
+  uint32_t fb0, nfb;      // its blocks of the front
+  uint32_t mb0, nmb;      // its blocks of the Miller lanes
+  U256 rho_sum;           // sum of its coefficients (an integer < 2^160)
+};
+
+struct BlockTab {
+  uint32_t key, first, live;
+};
+
+// sh[0] <- sum of sh[0 .. AGG_BLOCK): every lane of the block calls it, v = the lane's own term
+__device__ __forceinline__ void block_sum_g1(G1XYZZ* sh, G1XYZZ v) {
+  const uint32_t t = threadIdx.x;
+  sh[t] = v;
+#pragma unroll 1
+  for (uint32_t s = AGG_BLOCK / 2; s > 0; s >>= 1) {
+    __syncthreads();  // lanes < s read the upper half [s, 2s) and write the lower: one barrier per round
+    if (t < s) {
+      v.add(sh[t + s]);
+      sh[t] = v;
+    }
+  }
+  __syncthreads();
+}
+
+// lane k: ml_alpha_beta of key k
+__global__ void __launch_bounds__(64) k_verify_prepare(VkDev* vks, const KeyTab* keys, uint32_t n_keys) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n_keys || !keys[k].count) return;
+  VkDev* vk = vks + k;
   F12 f = f12_one();
   miller_mul(&f, &vk->beta, &vk->alpha_neg, vk);
   vk->ml_alpha_beta = f;
 }
 
-// one lane per proof
-__global__ void __launch_bounds__(64) k_verify_batch(const VkDev* vk, const G1Affine* ic, uint32_t n_pub,
-                                                     const uint8_t* proofs, const Fr* pubs, uint32_t n,
-                                                     uint8_t* ok) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
+// one lane per proof, under the key of its block of front[]
+__global__ void __launch_bounds__(64) k_verify_batch(const VkDev* vks, const KeyTab* keys, const BlockTab* blocks,
+                                                      const G1Affine* ics, const uint8_t* proofs, const Fr* pubs,
+                                                      uint8_t* ok) {
+  const BlockTab blk = blocks[blockIdx.x];
+  if (threadIdx.x >= blk.live) return;
+  const uint32_t i = blk.first + threadIdx.x;
+  const KeyTab* kt = keys + blk.key;
+  const VkDev* vk = vks + blk.key;
+  const uint32_t n_pub = kt->n_pub;
+  const G1Affine* ic = ics + kt->ic_off;
+  const Fr* pub = pubs + kt->pub_off + (size_t)(i - kt->first) * n_pub;
   G1Affine A, C;
   G2Affine B;
   memcpy(&A, proofs + (size_t)i * G16_PROOF_BYTES, 64);
@@ -60,7 +146,7 @@ __global__ void __launch_bounds__(64) k_verify_batch(const VkDev* vk, const G1Af
   XYZZ<Fq> acc = XYZZ<Fq>::from_affine(ic[0]);
 #pragma unroll 1
   for (uint32_t j = 0; j < n_pub; ++j) {
-    const U256 s = pubs[(size_t)i * n_pub + j].to_canonical();
+    const U256 s = pub[j].to_canonical();
     XYZZ<Fq> t = XYZZ<Fq>::from_affine(ic[j + 1]).mul(s);
     acc.add(t);
   }
@@ -73,37 +159,18 @@ __global__ void __launch_bounds__(64) k_verify_batch(const VkDev* vk, const G1Af
   ok[i] = final_exp_is_one(&f, vk) ? 1 : 0;
 }
 
-// ---- aggregate verification: n proofs under one key in ONE combined pairing check ---------------
-// With coefficients rho_i (128-bit, unknown to whoever made the proofs) the n per-proof equations
-// fold into
-//   prod_i ML(B_i, rho_i A_i) * ML(beta, -(sum rho_i) alpha) * ML(gamma, -sum rho_i X_i)
-//       * ML(delta, -sum rho_i C_i)   --final exponentiation-->   1,
-//   sum_i rho_i X_i = (sum_i rho_i) IC_0 + sum_j (sum_i rho_i pub_ij) IC_{j+1}
-// (the small-exponent batch test).  Per proof that is one Miller loop, two 128-bit G1
-// multiplications and the structural checks; the key-side Miller loops and the final
-// exponentiation are paid once per batch.  The long serial pieces sit in separate lanes:
-//   k_agg_front   blockIdx.y = 0: structural checks (incl. the 254-bit subgroup multiplication)
-//                 blockIdx.y = 1: P_i = rho_i A_i (affine)
-//                 blockIdx.y = 2: rho_i C_i and rho_i pub_ij, summed per block through LDS
-//   k_agg_sums    one block per sum over the per-block partials: -sum rho_i C_i, the columns
-//                 s_j = sum_i rho_i pub_ij, and one lane for -(sum rho) alpha
-//   k_agg_x       -((sum rho) IC_0 + sum_j s_j IC_{j+1}), one lane per term, LDS sum
-//   k_agg_miller  n + 3 lanes, one Miller loop each; per-block product through LDS
-//   k_agg_tail    product of the per-block products, AND of the structural flags, final
-//                 exponentiation in one lane
-// No atomics: every reduction is a fixed tree, so the result does not depend on scheduling.
-// AGG_BLOCK lanes per block, AggKey and block_sum_g1: verify_agg.h (shared with verify_keys.hip)
-
-__global__ void __launch_bounds__(AGG_BLOCK) k_agg_front(const VkDev* vk, uint32_t n_pub, const uint8_t* proofs,
-                                                         const Fr* pubs, const uint64_t* rho, uint32_t n,
-                                                         uint8_t* structural, G1Affine* P, G1XYZZ* c_part,
-                                                         Fr* s_part) {
+// block b of front[], blockIdx.y = its role: structural[i] | P[i] | c_part[b], s_part[spart_off + j * nfb + (block - fb0)]
+__global__ void __launch_bounds__(AGG_BLOCK) k_agg_front(const VkDev* vks, const KeyTab* keys, const BlockTab* blocks,
+                                                          const uint8_t* proofs, const Fr* pubs, const uint64_t* rho,
+                                                          uint8_t* structural, G1Affine* P, G1XYZZ* c_part,
+                                                          Fr* s_part) {
   __shared__ G1XYZZ sh_c[AGG_BLOCK];
   __shared__ Fr sh_s[AGG_BLOCK];
-  const uint32_t t = threadIdx.x, i = blockIdx.x * AGG_BLOCK + t;
-  const bool live = i < n;
-  const uint8_t* proof = proofs + (size_t)(live ? i : 0) * G16_PROOF_BYTES;
-  if (blockIdx.y == 0) {  // what g16_verify_batch checks before it pairs
+  const BlockTab blk = blocks[blockIdx.x];
+  const uint32_t t = threadIdx.x, i = blk.first + t;
+  const bool live = t < blk.live;
+  const uint8_t* proof = proofs + (size_t)(live ? i : blk.first) * G16_PROOF_BYTES;
+  if (blockIdx.y == 0) {  // what k_verify_batch checks before it pairs
     if (!live) return;
     G1Affine A, C;
     G2Affine B;
@@ -112,7 +179,8 @@ __global__ void __launch_bounds__(AGG_BLOCK) k_agg_front(const VkDev* vk, uint32
     memcpy(&C, proof + 192, 64);
     const bool canonical = fq_words_canonical(B.x.c0) && fq_words_canonical(B.x.c1) &&
                            fq_words_canonical(B.y.c0) && fq_words_canonical(B.y.c1);
-    structural[i] = (canonical && g1_well_formed(A) && g1_well_formed(C) && on_curve_g2(B, vk) && g2_in_subgroup(B)) ? 1 : 0;
+    structural[i] = (canonical && g1_well_formed(A) && g1_well_formed(C) && on_curve_g2(B, vks + blk.key) &&
+                     g2_in_subgroup(B)) ? 1 : 0;
     return;
   }
   if (blockIdx.y == 1) {  // a malformed A is never paired (k_agg_miller skips the proof): any value will do
@@ -134,9 +202,13 @@ __global__ void __launch_bounds__(AGG_BLOCK) k_agg_front(const VkDev* vk, uint32
   }
   block_sum_g1(sh_c, acc);
   if (t == 0) c_part[blockIdx.x] = sh_c[0];
+  const KeyTab* kt = keys + blk.key;
+  const uint32_t n_pub = kt->n_pub, nfb = kt->nfb;
+  const Fr* pub = pubs + kt->pub_off + (size_t)(i - kt->first) * n_pub;  // read by live lanes only
+  Fr* part = s_part + kt->spart_off + (blockIdx.x - kt->fb0);
 #pragma unroll 1
   for (uint32_t j = 0; j < n_pub; ++j) {
-    Fr v = live ? rf * pubs[(size_t)i * n_pub + j] : Fr::zero();
+    Fr v = live ? rf * pub[j] : Fr::zero();
     sh_s[t] = v;
 #pragma unroll 1
     for (uint32_t s = AGG_BLOCK / 2; s > 0; s >>= 1) {
@@ -146,28 +218,34 @@ __global__ void __launch_bounds__(AGG_BLOCK) k_agg_front(const VkDev* vk, uint32
         sh_s[t] = v;
       }
     }
-    if (t == 0) s_part[(size_t)j * gridDim.x + blockIdx.x] = v;
+    if (t == 0) part[(size_t)j * nfb] = v;
     __syncthreads();
   }
 }
 
-// block 0: -sum rho_i C_i; block 1 + j: s_j (canonical, the scalar of IC_{j+1}); block n_pub + 1: -(sum rho) alpha
-__global__ void __launch_bounds__(AGG_BLOCK) k_agg_sums(const VkDev* vk, uint32_t n_pub, uint32_t nb,
-                                                        const G1XYZZ* c_part, const Fr* s_part, U256 rho_sum,
-                                                        AggKey* key, U256* scal) {
+// block k * stride + b of group k: b = 0: -sum rho_i C_i; b = 1 + j: s_j (canonical, the scalar of IC_{j+1});
+// b = n_pub + 1: -(sum rho) alpha; above (a key with fewer inputs than the widest) and empty groups: nothing
+__global__ void __launch_bounds__(AGG_BLOCK) k_agg_sums(const VkDev* vks, const KeyTab* keys, uint32_t stride,
+                                                         const G1XYZZ* c_part, const Fr* s_part, AggKey* key,
+                                                         U256* scal) {
   __shared__ G1XYZZ sh_c[AGG_BLOCK];
   __shared__ Fr sh_s[AGG_BLOCK];
-  const uint32_t t = threadIdx.x, b = blockIdx.x;
+  const uint32_t t = threadIdx.x, g = blockIdx.x / stride, b = blockIdx.x % stride;
+  const KeyTab* kt = keys + g;
+  const uint32_t n_pub = kt->n_pub, nb = kt->nfb;
+  if (!kt->count || b > n_pub + 1) return;
   if (b == 0) {
+    const G1XYZZ* cp = c_part + kt->fb0;
     G1XYZZ acc = G1XYZZ::infinity();
 #pragma unroll 1
-    for (uint32_t k = t; k < nb; k += AGG_BLOCK) acc.add(c_part[k]);
+    for (uint32_t k = t; k < nb; k += AGG_BLOCK) acc.add(cp[k]);
     block_sum_g1(sh_c, acc);
-    if (t == 0) key->p[2] = sh_c[0].to_affine().neg();
+    if (t == 0) key[g].p[2] = sh_c[0].to_affine().neg();
   } else if (b <= n_pub) {
+    const Fr* sp = s_part + kt->spart_off + (size_t)(b - 1) * nb;
     Fr v = Fr::zero();
 #pragma unroll 1
-    for (uint32_t k = t; k < nb; k += AGG_BLOCK) v = v + s_part[(size_t)(b - 1) * nb + k];
+    for (uint32_t k = t; k < nb; k += AGG_BLOCK) v = v + sp[k];
     sh_s[t] = v;
 #pragma unroll 1
     for (uint32_t s = AGG_BLOCK / 2; s > 0; s >>= 1) {
@@ -177,44 +255,56 @@ __global__ void __launch_bounds__(AGG_BLOCK) k_agg_sums(const VkDev* vk, uint32_
         sh_s[t] = v;
       }
     }
-    if (t == 0) scal[b] = v.to_canonical();
+    if (t == 0) scal[kt->ic_off + b] = v.to_canonical();
   } else if (t == 0) {
-    key->p[0] = G1XYZZ::from_affine(vk->alpha_neg).mul(rho_sum).to_affine();
-    scal[0] = rho_sum;  // the scalar of IC_0
+    key[g].p[0] = G1XYZZ::from_affine(vks[g].alpha_neg).mul(kt->rho_sum).to_affine();
+    scal[kt->ic_off] = kt->rho_sum;  // the scalar of IC_0
   }
 }
 
-// -(sum_j scal_j IC_j), j = 0 .. n_pub
-__global__ void __launch_bounds__(AGG_BLOCK) k_agg_x(const G1Affine* ic, uint32_t n_pub, const U256* scal,
-                                                     AggKey* key) {
+// block g: -(sum_j scal_j IC_j) over the key's own IC range, j = 0 .. n_pub
+__global__ void __launch_bounds__(AGG_BLOCK) k_agg_x(const KeyTab* keys, const G1Affine* ics, const U256* scal,
+                                                      AggKey* key) {
   __shared__ G1XYZZ sh_c[AGG_BLOCK];
   const uint32_t t = threadIdx.x;
+  const KeyTab* kt = keys + blockIdx.x;
+  if (!kt->count) return;
+  const G1Affine* ic = ics + kt->ic_off;
+  const U256* sc = scal + kt->ic_off;
+  const uint32_t n_pub = kt->n_pub;
   G1XYZZ acc = G1XYZZ::infinity();
 #pragma unroll 1
-  for (uint32_t j = t; j <= n_pub; j += AGG_BLOCK) acc.add(G1XYZZ::from_affine(ic[j]).mul(scal[j]));
+  for (uint32_t j = t; j <= n_pub; j += AGG_BLOCK) acc.add(G1XYZZ::from_affine(ic[j]).mul(sc[j]));
   block_sum_g1(sh_c, acc);
-  if (t == 0) key->p[1] = sh_c[0].to_affine().neg();
+  if (t == 0) key[blockIdx.x].p[1] = sh_c[0].to_affine().neg();
 }
 
-// lane i < n: ML(B_i, P_i), or 1 for a malformed proof; lanes n, n + 1, n + 2: the key side.
-// f_part[block] = product of the block's lanes
-__global__ void __launch_bounds__(AGG_BLOCK) k_agg_miller(const VkDev* vk, const uint8_t* proofs, const G1Affine* P,
-                                                          const uint8_t* structural, const AggKey* key, uint32_t n,
-                                                          F12* f_part) {
+// lane l = blk.first + t of the block's group: l < count: ML(B_i, P_i) of proof first + l, or 1 for a malformed
+// proof; l = count, count + 1, count + 2: the group's key side.  f_part[block] = product of the block's lanes
+__global__ void __launch_bounds__(AGG_BLOCK) k_agg_miller(const VkDev* vks, const KeyTab* keys,
+                                                           const BlockTab* blocks, const uint8_t* proofs,
+                                                           const G1Affine* P, const uint8_t* structural,
+                                                           const AggKey* key, F12* f_part) {
   __shared__ F12 sh[AGG_BLOCK];
+  const BlockTab blk = blocks[blockIdx.x];
   const uint32_t t = threadIdx.x;
-  const uint64_t i = (uint64_t)blockIdx.x * AGG_BLOCK + t;
+  const VkDev* vk = vks + blk.key;
+  const uint32_t count = keys[blk.key].count;
   G2Affine Q = G2Affine::infinity();
   G1Affine p = G1Affine::infinity();
-  if (i < n) {
-    if (structural[i]) {
-      memcpy(&Q, proofs + (size_t)i * G16_PROOF_BYTES + 64, 128);
-      p = P[i];
+  if (t < blk.live) {
+    const uint32_t l = blk.first + t;
+    if (l < count) {
+      const uint32_t i = keys[blk.key].first + l;
+      if (structural[i]) {
+        memcpy(&Q, proofs + (size_t)i * G16_PROOF_BYTES + 64, 128);
+        p = P[i];
+      }
+    } else {
+      const uint32_t k = l - count;
+      Q = k == 0 ? vk->beta : k == 1 ? vk->gamma : vk->delta;
+      p = key[blk.key].p[k];
     }
-  } else if (i < (uint64_t)n + 3) {
-    const uint32_t k = (uint32_t)(i - n);
-    Q = k == 0 ? vk->beta : k == 1 ? vk->gamma : vk->delta;
-    p = key->p[k];
   }
   F12 f = f12_one();
   miller_mul(&f, &Q, &p, vk);  // one call site for proof and key lanes: no divergent copies of the loop
@@ -230,17 +320,26 @@ __global__ void __launch_bounds__(AGG_BLOCK) k_agg_miller(const VkDev* vk, const
   if (t == 0) f_part[blockIdx.x] = f;
 }
 
-__global__ void __launch_bounds__(AGG_BLOCK) k_agg_tail(const VkDev* vk, const F12* f_part, uint32_t nb,
-                                                        const uint8_t* structural, uint32_t n, uint8_t* ok) {
+// block g: the verdict of group g (an empty group: 1)
+__global__ void __launch_bounds__(AGG_BLOCK) k_agg_tail(const VkDev* vks, const KeyTab* keys, const F12* f_part,
+                                                         const uint8_t* structural, uint8_t* ok) {
   __shared__ F12 sh[AGG_BLOCK];
   __shared__ uint32_t sh_ok[AGG_BLOCK];
   const uint32_t t = threadIdx.x;
+  const KeyTab* kt = keys + blockIdx.x;
+  const uint32_t nb = kt->nmb, n = kt->count;
+  if (!n) {
+    if (t == 0) ok[blockIdx.x] = 1;
+    return;
+  }
+  const F12* fp = f_part + kt->mb0;
+  const uint8_t* st = structural + kt->first;
   F12 f = f12_one();
 #pragma unroll 1
-  for (uint32_t k = t; k < nb; k += AGG_BLOCK) f12_mul(&f, &f, &f_part[k]);
+  for (uint32_t k = t; k < nb; k += AGG_BLOCK) f12_mul(&f, &f, &fp[k]);
   uint32_t sound = 1;
 #pragma unroll 1
-  for (uint32_t k = t; k < n; k += AGG_BLOCK) sound &= structural[k];
+  for (uint32_t k = t; k < n; k += AGG_BLOCK) sound &= st[k];
   sh[t] = f;
   sh_ok[t] = sound;
 #pragma unroll 1
@@ -253,7 +352,232 @@ __global__ void __launch_bounds__(AGG_BLOCK) k_agg_tail(const VkDev* vk, const F
       sh_ok[t] = sound;
     }
   }
-  if (t == 0) *ok = (sound && final_exp_is_one(&f, vk)) ? 1 : 0;
+  if (t == 0) ok[blockIdx.x] = (sound && final_exp_is_one(&f, vks + blockIdx.x)) ? 1 : 0;
+}
+
+// ---- host side ---------------------------------------------------------------------------------
+// what both entry points refuse; *n_total = sum of counts
+g16_status check_groups(const g16_vk_desc* const* vks, const uint32_t* counts, uint32_t n_keys,
+                        const uint8_t* proofs, const uint64_t* public_inputs, uint64_t* n_total) {
+  *n_total = 0;
+  if (!n_keys) return G16_OK;
+  if (!vks || !counts) return G16_ERR_INVALID;
+  uint64_t n = 0, n_ic = 0;
+  bool need_pub = false;
+  for (uint32_t k = 0; k < n_keys; ++k) {
+    if (!vks[k] || !vks[k]->ic || vks[k]->ic_count < 1) return G16_ERR_INVALID;
+    n += counts[k];
+    n_ic += vks[k]->ic_count;
+    if (counts[k] && vks[k]->ic_count > 1) need_pub = true;
+  }
+  // proof lanes + 3 key-side lanes per group are indexed in 32 bits, and so are the concatenated IC rows
+  if (n + 3 * (uint64_t)n_keys > 0xffffffffull || n_ic > 0xffffffffull) return G16_ERR_INVALID;
+  if (n && !proofs) return G16_ERR_INVALID;
+  if (need_pub && !public_inputs) return G16_ERR_INVALID;
+  *n_total = n;
+  return G16_OK;
+}
+
+struct Plan {
+  std::vector<KeyTab> keys;
+  std::vector<BlockTab> front, miller;
+  std::vector<VkDev> vks;
+  std::vector<uint8_t> ic;  // the keys' IC rows, one after the other
+  uint64_t n_pub_words = 0;  // Fr in public_inputs
+  uint64_t n_spart = 0;      // Fr in s_part
+  uint32_t max_pub = 0;
+};
+
+// rho: the coefficients of all proofs, or NULL on the per-proof path (rho_sum stays 0, no Miller blocks)
+void make_plan(Plan& pl, const g16_vk_desc* const* vks, const uint32_t* counts, uint32_t n_keys,
+               const uint64_t* rho) {
+  pl.keys.resize(n_keys);
+  pl.vks.resize(n_keys);
+  uint64_t first = 0, ic_off = 0;
+  for (uint32_t k = 0; k < n_keys; ++k) {
+    const g16_vk_desc* vk = vks[k];
+    VkDev& hv = pl.vks[k];
+    G1Affine alpha;
+    memcpy(&alpha, vk->alpha_g1, 64);
+    hv.alpha_neg = alpha.neg();
+    memcpy(&hv.beta, vk->beta_g2, 128);
+    memcpy(&hv.gamma, vk->gamma_g2, 128);
+    memcpy(&hv.delta, vk->delta_g2, 128);
+    vk_consts(&hv);
+    hv.ml_alpha_beta = f12_one();  // the per-proof path fills it in k_verify_prepare; the aggregate path does not use it
+    pl.ic.insert(pl.ic.end(), vk->ic, vk->ic + (size_t)vk->ic_count * 64);
+
+    KeyTab& kt = pl.keys[k];
+    const uint32_t n = counts[k];
+    kt.pub_off = pl.n_pub_words;
+    kt.spart_off = pl.n_spart;
+    kt.ic_off = (uint32_t)ic_off;
+    kt.n_pub = vk->ic_count - 1;
+    kt.first = (uint32_t)first;
+    kt.count = n;
+    kt.fb0 = (uint32_t)pl.front.size();
+    kt.nfb = ceil_div(n, AGG_BLOCK);
+    kt.mb0 = (uint32_t)pl.miller.size();
+    kt.nmb = (n && rho) ? ceil_div((uint64_t)n + 3, AGG_BLOCK) : 0;
+    for (uint32_t b = 0; b < kt.nfb; ++b) {
+      const uint32_t at = b * AGG_BLOCK;
+      pl.front.push_back(BlockTab{k, kt.first + at, n - at < AGG_BLOCK ? n - at : AGG_BLOCK});
+    }
+    for (uint32_t b = 0; b < kt.nmb; ++b) {
+      const uint64_t at = (uint64_t)b * AGG_BLOCK, left = (uint64_t)n + 3 - at;
+      pl.miller.push_back(BlockTab{k, (uint32_t)at, left < AGG_BLOCK ? (uint32_t)left : AGG_BLOCK});
+    }
+    // sum of the group's coefficients as an integer: < 2^160, far below r, so it is its own residue
+    uint64_t w0 = 0, w1 = 0, hi = 0;
+    if (rho)
+      for (uint64_t i = first; i < first + n; ++i) {
+        unsigned __int128 lo = (unsigned __int128)w0 + rho[2 * i];
+        w0 = (uint64_t)lo;
+        lo = (lo >> 64) + w1 + rho[2 * i + 1];
+        w1 = (uint64_t)lo;
+        hi += (uint64_t)(lo >> 64);
+      }
+    const uint64_t w[4] = {w0, w1, hi, 0};
+    for (int q = 0; q < 4; ++q) {
+      kt.rho_sum.v[2 * q] = (uint32_t)w[q];
+      kt.rho_sum.v[2 * q + 1] = (uint32_t)(w[q] >> 32);
+    }
+    pl.n_pub_words += (uint64_t)n * kt.n_pub;
+    pl.n_spart += (uint64_t)kt.nfb * kt.n_pub;
+    if (kt.n_pub > pl.max_pub) pl.max_pub = kt.n_pub;
+    first += n;
+    ic_off += vk->ic_count;
+  }
+}
+
+// the device copies both paths need
+struct PlanDev {
+  DevBuf<VkDev> vks;
+  DevBuf<KeyTab> keys;
+  DevBuf<BlockTab> front;
+  DevBuf<G1Affine> ic;
+  DevBuf<uint8_t> proofs;
+  DevBuf<Fr> pub;
+  void upload(const Plan& pl, const uint8_t* proofs_h, const uint64_t* pubs_h, uint64_t n) {
+    vks.alloc(pl.vks.size());
+    keys.alloc(pl.keys.size());
+    front.alloc(pl.front.size());
+    ic.alloc(pl.ic.size() / 64);
+    proofs.alloc((size_t)n * G16_PROOF_BYTES);
+    pub.alloc(pl.n_pub_words ? pl.n_pub_words : 1);
+    G16_HIP(hipMemcpy(vks.p, pl.vks.data(), pl.vks.size() * sizeof(VkDev), hipMemcpyHostToDevice));
+    G16_HIP(hipMemcpy(keys.p, pl.keys.data(), pl.keys.size() * sizeof(KeyTab), hipMemcpyHostToDevice));
+    G16_HIP(hipMemcpy(front.p, pl.front.data(), pl.front.size() * sizeof(BlockTab), hipMemcpyHostToDevice));
+    G16_HIP(hipMemcpy(ic.p, pl.ic.data(), pl.ic.size(), hipMemcpyHostToDevice));
+    G16_HIP(hipMemcpy(proofs.p, proofs_h, (size_t)n * G16_PROOF_BYTES, hipMemcpyHostToDevice));
+    if (pl.n_pub_words) G16_HIP(hipMemcpy(pub.p, pubs_h, pl.n_pub_words * 32, hipMemcpyHostToDevice));
+  }
+};
+
+// g16_verify_batch_keys; g16_verify_batch is the call with one group
+g16_status verify_batch_groups(int device, const g16_vk_desc* const* vks, const uint32_t* counts, uint32_t n_keys,
+                               const uint8_t* proofs, const uint64_t* public_inputs, uint8_t* ok_out) {
+  uint64_t n = 0;
+  if (check_groups(vks, counts, n_keys, proofs, public_inputs, &n) != G16_OK || (n && !ok_out))
+    return G16_ERR_INVALID;
+  if (const g16_status ds = device_ok(device)) return ds;
+  if (!n) return G16_OK;
+  try {
+    G16_HIP(hipSetDevice(device));
+    Plan pl;
+    make_plan(pl, vks, counts, n_keys, nullptr);
+    PlanDev d;
+    DevBuf<uint8_t> dok;
+    d.upload(pl, proofs, public_inputs, n);
+    dok.alloc(n);
+    G16_LAUNCH(k_verify_prepare, ceil_div(n_keys, 64), 64, 0, nullptr, d.vks.p, (const KeyTab*)d.keys.p, n_keys);
+    G16_LAUNCH(k_verify_batch, (uint32_t)pl.front.size(), 64, 0, nullptr, (const VkDev*)d.vks.p,
+               (const KeyTab*)d.keys.p, (const BlockTab*)d.front.p, (const G1Affine*)d.ic.p,
+               (const uint8_t*)d.proofs.p, (const Fr*)d.pub.p, dok.p);
+    G16_HIP(hipGetLastError());
+    G16_HIP(hipDeviceSynchronize());
+    G16_HIP(hipMemcpy(ok_out, dok.p, n, hipMemcpyDeviceToHost));
+    return G16_OK;
+  } catch (const HipError&) {
+    return G16_ERR_HIP;
+  } catch (const std::exception&) {
+    return G16_ERR_INTERNAL;
+  }
+}
+
+// g16_verify_aggregate_keys; g16_verify_aggregate is the call with one group
+g16_status verify_aggregate_groups(int device, const g16_vk_desc* const* vks, const uint32_t* counts, uint32_t n_keys,
+                                   const uint8_t* proofs, const uint64_t* public_inputs, const uint64_t* rho,
+                                   uint8_t* ok_out, uint8_t* structural_out) {
+  uint64_t n = 0;
+  if (check_groups(vks, counts, n_keys, proofs, public_inputs, &n) != G16_OK || (n_keys && !ok_out))
+    return G16_ERR_INVALID;
+  if (!rho_all_nonzero(rho, n)) return G16_ERR_INVALID;
+  if (const g16_status ds = device_ok(device)) return ds;
+  if (!n_keys) return G16_OK;
+  if (!n) {
+    memset(ok_out, 1, n_keys);
+    return G16_OK;
+  }
+  try {
+    std::vector<uint64_t> drawn;
+    if (!rho) {
+      drawn.resize(2 * (size_t)n);
+      if (!draw_rho(drawn.data(), (size_t)n)) return G16_ERR_INTERNAL;
+      rho = drawn.data();
+    }
+    G16_HIP(hipSetDevice(device));
+    Plan pl;
+    make_plan(pl, vks, counts, n_keys, rho);
+    const uint32_t nb = (uint32_t)pl.front.size(), nbm = (uint32_t)pl.miller.size();
+    const uint64_t sum_blocks = (uint64_t)n_keys * ((uint64_t)pl.max_pub + 2);
+    if (sum_blocks > 0x7fffffffull) return G16_ERR_INVALID;  // the grid of k_agg_sums
+    PlanDev d;
+    DevBuf<BlockTab> dmiller;
+    DevBuf<G1Affine> dP;
+    DevBuf<uint8_t> dstruct, dok;
+    DevBuf<Fr> dspart;
+    DevBuf<uint64_t> drho;
+    DevBuf<G1XYZZ> dcpart;
+    DevBuf<U256> dscal;
+    DevBuf<AggKey> dkey;
+    DevBuf<F12> dfpart;
+    d.upload(pl, proofs, public_inputs, n);
+    dmiller.alloc(nbm);
+    dP.alloc(n);
+    dstruct.alloc(n);
+    dok.alloc(n_keys);
+    dspart.alloc(pl.n_spart ? pl.n_spart : 1);
+    drho.alloc(2 * (size_t)n);
+    dcpart.alloc(nb);
+    dscal.alloc(pl.ic.size() / 64);
+    dkey.alloc(n_keys);
+    dfpart.alloc(nbm);
+    G16_HIP(hipMemcpy(dmiller.p, pl.miller.data(), (size_t)nbm * sizeof(BlockTab), hipMemcpyHostToDevice));
+    G16_HIP(hipMemcpy(drho.p, rho, (size_t)n * 16, hipMemcpyHostToDevice));
+    G16_LAUNCH(k_agg_front, dim3(nb, 3), AGG_BLOCK, 0, nullptr, (const VkDev*)d.vks.p, (const KeyTab*)d.keys.p,
+               (const BlockTab*)d.front.p, (const uint8_t*)d.proofs.p, (const Fr*)d.pub.p, (const uint64_t*)drho.p,
+               dstruct.p, dP.p, dcpart.p, dspart.p);
+    G16_LAUNCH(k_agg_sums, (uint32_t)sum_blocks, AGG_BLOCK, 0, nullptr, (const VkDev*)d.vks.p,
+               (const KeyTab*)d.keys.p, pl.max_pub + 2, (const G1XYZZ*)dcpart.p, (const Fr*)dspart.p, dkey.p,
+               dscal.p);
+    G16_LAUNCH(k_agg_x, n_keys, AGG_BLOCK, 0, nullptr, (const KeyTab*)d.keys.p, (const G1Affine*)d.ic.p,
+               (const U256*)dscal.p, dkey.p);
+    G16_LAUNCH(k_agg_miller, nbm, AGG_BLOCK, 0, nullptr, (const VkDev*)d.vks.p, (const KeyTab*)d.keys.p,
+               (const BlockTab*)dmiller.p, (const uint8_t*)d.proofs.p, (const G1Affine*)dP.p,
+               (const uint8_t*)dstruct.p, (const AggKey*)dkey.p, dfpart.p);
+    G16_LAUNCH(k_agg_tail, n_keys, AGG_BLOCK, 0, nullptr, (const VkDev*)d.vks.p, (const KeyTab*)d.keys.p,
+               (const F12*)dfpart.p, (const uint8_t*)dstruct.p, dok.p);
+    G16_HIP(hipGetLastError());
+    G16_HIP(hipDeviceSynchronize());
+    G16_HIP(hipMemcpy(ok_out, dok.p, n_keys, hipMemcpyDeviceToHost));
+    if (structural_out) G16_HIP(hipMemcpy(structural_out, dstruct.p, n, hipMemcpyDeviceToHost));
+    return G16_OK;
+  } catch (const HipError&) {
+    return G16_ERR_HIP;
+  } catch (const std::exception&) {
+    return G16_ERR_INTERNAL;
+  }
 }
 
 }  // namespace
@@ -261,154 +585,30 @@ __global__ void __launch_bounds__(AGG_BLOCK) k_agg_tail(const VkDev* vk, const F
 
 using namespace g16;
 
+// A single-key call is the call with one group.  check_groups refuses for that group what these calls always
+// refused, before the device is looked at: a NULL vk or ic, ic_count < 1, proofs or public inputs missing where
+// n_proofs > 0 needs them.  ok_out: needed by the per-proof call when n_proofs > 0, by the aggregate call always
+// (n_proofs == 0 writes 1 there).
 extern "C" g16_status g16_verify_batch(int device, const g16_vk_desc* vk, const uint8_t* proofs,
-                                       const uint64_t* public_inputs, uint32_t n_proofs,
-                                       uint8_t* ok_out) {
-  if (!vk || !vk->ic || vk->ic_count < 1 || (n_proofs && (!proofs || !ok_out))) return G16_ERR_INVALID;
-  const uint32_t n_pub = vk->ic_count - 1;
-  if (n_proofs && n_pub && !public_inputs) return G16_ERR_INVALID;
-  if (const g16_status ds = device_ok(device)) return ds;
-  if (!n_proofs) return G16_OK;
-  try {
-    G16_HIP(hipSetDevice(device));
-    VkDev* hv = new VkDev();
-    std::unique_ptr<VkDev> keep(hv);
-    G1Affine alpha;
-    memcpy(&alpha, vk->alpha_g1, 64);
-    hv->alpha_neg = alpha.neg();
-    memcpy(&hv->beta, vk->beta_g2, 128);
-    memcpy(&hv->gamma, vk->gamma_g2, 128);
-    memcpy(&hv->delta, vk->delta_g2, 128);
-    vk_consts(hv);
-    DevBuf<VkDev> dvk;
-    DevBuf<G1Affine> dic;
-    DevBuf<uint8_t> dproofs, dok;
-    DevBuf<Fr> dpub;
-    dvk.alloc(1);
-    dic.alloc(vk->ic_count);
-    dproofs.alloc((size_t)n_proofs * G16_PROOF_BYTES);
-    dok.alloc(n_proofs);
-    dpub.alloc((size_t)n_proofs * (n_pub ? n_pub : 1));
-    G16_HIP(hipMemcpy(dvk.p, hv, sizeof(VkDev), hipMemcpyHostToDevice));
-    G16_HIP(hipMemcpy(dic.p, vk->ic, (size_t)vk->ic_count * 64, hipMemcpyHostToDevice));
-    G16_HIP(hipMemcpy(dproofs.p, proofs, (size_t)n_proofs * G16_PROOF_BYTES, hipMemcpyHostToDevice));
-    if (n_pub)
-      G16_HIP(hipMemcpy(dpub.p, public_inputs, (size_t)n_proofs * n_pub * 32, hipMemcpyHostToDevice));
-    G16_LAUNCH(k_verify_prepare, 1, 64, 0, nullptr, dvk.p);
-    G16_LAUNCH(k_verify_batch, ceil_div(n_proofs, 64), 64, 0, nullptr, (const VkDev*)dvk.p,
-               (const G1Affine*)dic.p, n_pub, (const uint8_t*)dproofs.p, (const Fr*)dpub.p, n_proofs,
-               dok.p);
-    G16_HIP(hipDeviceSynchronize());
-    G16_HIP(hipMemcpy(ok_out, dok.p, n_proofs, hipMemcpyDeviceToHost));
-    return G16_OK;
-  } catch (const HipError&) {
-    return G16_ERR_HIP;
-  } catch (const std::exception&) {
-    return G16_ERR_INTERNAL;
-  }
+                                       const uint64_t* public_inputs, uint32_t n_proofs, uint8_t* ok_out) {
+  return verify_batch_groups(device, &vk, &n_proofs, 1, proofs, public_inputs, ok_out);
 }
 
 extern "C" g16_status g16_verify_aggregate(int device, const g16_vk_desc* vk, const uint8_t* proofs,
-                                           const uint64_t* public_inputs, uint32_t n_proofs,
-                                           const uint64_t* rho, uint8_t* ok_out, uint8_t* structural_out) {
-  if (!vk || !vk->ic || vk->ic_count < 1 || !ok_out || (n_proofs && !proofs)) return G16_ERR_INVALID;
-  const uint32_t n_pub = vk->ic_count - 1;
-  if (n_proofs && n_pub && !public_inputs) return G16_ERR_INVALID;
-  if (rho)
-    for (uint32_t i = 0; i < n_proofs; ++i)
-      if (!(rho[2 * (size_t)i] | rho[2 * (size_t)i + 1])) return G16_ERR_INVALID;
-  if (const g16_status ds = device_ok(device)) return ds;
-  if (!n_proofs) {
-    *ok_out = 1;
-    return G16_OK;
-  }
-  try {
-    std::vector<uint64_t> drawn;
-    if (!rho) {
-      drawn.resize(2 * (size_t)n_proofs);
-      if (!os_random(drawn.data(), drawn.size() * 8)) return G16_ERR_INTERNAL;
-      for (uint32_t i = 0; i < n_proofs; ++i)
-        while (!(drawn[2 * (size_t)i] | drawn[2 * (size_t)i + 1]))  // probability 2^-128 per entry
-          if (!os_random(&drawn[2 * (size_t)i], 16)) return G16_ERR_INTERNAL;
-      rho = drawn.data();
-    }
-    // sum of the coefficients as an integer: < 2^160, far below r, so it is its own residue
-    U256 rho_sum;
-    {
-      unsigned __int128 lo = 0;
-      uint64_t hi = 0;
-      uint64_t w0 = 0, w1 = 0;
-      for (uint32_t i = 0; i < n_proofs; ++i) {
-        lo = (unsigned __int128)w0 + rho[2 * (size_t)i];
-        w0 = (uint64_t)lo;
-        lo = (lo >> 64) + w1 + rho[2 * (size_t)i + 1];
-        w1 = (uint64_t)lo;
-        hi += (uint64_t)(lo >> 64);
-      }
-      const uint64_t w[4] = {w0, w1, hi, 0};
-      for (int k = 0; k < 4; ++k) {
-        rho_sum.v[2 * k] = (uint32_t)w[k];
-        rho_sum.v[2 * k + 1] = (uint32_t)(w[k] >> 32);
-      }
-    }
-    G16_HIP(hipSetDevice(device));
-    std::unique_ptr<VkDev> hv(new VkDev());
-    G1Affine alpha;
-    memcpy(&alpha, vk->alpha_g1, 64);
-    hv->alpha_neg = alpha.neg();
-    memcpy(&hv->beta, vk->beta_g2, 128);
-    memcpy(&hv->gamma, vk->gamma_g2, 128);
-    memcpy(&hv->delta, vk->delta_g2, 128);
-    vk_consts(hv.get());
-    hv->ml_alpha_beta = f12_one();  // not used on this path (alpha is scaled by the sum of the coefficients)
-    const uint32_t nb = ceil_div(n_proofs, AGG_BLOCK);                 // blocks of the per-proof front
-    const uint32_t nbm = ceil_div((uint64_t)n_proofs + 3, AGG_BLOCK);  // blocks of the n + 3 Miller lanes
-    DevBuf<VkDev> dvk;
-    DevBuf<G1Affine> dic, dP;
-    DevBuf<uint8_t> dproofs, dstruct, dok;
-    DevBuf<Fr> dpub, dspart;
-    DevBuf<uint64_t> drho;
-    DevBuf<G1XYZZ> dcpart;
-    DevBuf<U256> dscal;
-    DevBuf<AggKey> dkey;
-    DevBuf<F12> dfpart;
-    dvk.alloc(1);
-    dic.alloc(vk->ic_count);
-    dP.alloc(n_proofs);
-    dproofs.alloc((size_t)n_proofs * G16_PROOF_BYTES);
-    dstruct.alloc(n_proofs);
-    dok.alloc(1);
-    dpub.alloc((size_t)n_proofs * (n_pub ? n_pub : 1));
-    dspart.alloc((size_t)nb * (n_pub ? n_pub : 1));
-    drho.alloc(2 * (size_t)n_proofs);
-    dcpart.alloc(nb);
-    dscal.alloc((size_t)n_pub + 1);
-    dkey.alloc(1);
-    dfpart.alloc(nbm);
-    G16_HIP(hipMemcpy(dvk.p, hv.get(), sizeof(VkDev), hipMemcpyHostToDevice));
-    G16_HIP(hipMemcpy(dic.p, vk->ic, (size_t)vk->ic_count * 64, hipMemcpyHostToDevice));
-    G16_HIP(hipMemcpy(dproofs.p, proofs, (size_t)n_proofs * G16_PROOF_BYTES, hipMemcpyHostToDevice));
-    G16_HIP(hipMemcpy(drho.p, rho, (size_t)n_proofs * 16, hipMemcpyHostToDevice));
-    if (n_pub)
-      G16_HIP(hipMemcpy(dpub.p, public_inputs, (size_t)n_proofs * n_pub * 32, hipMemcpyHostToDevice));
-    G16_LAUNCH(k_agg_front, dim3(nb, 3), AGG_BLOCK, 0, nullptr, (const VkDev*)dvk.p, n_pub,
-               (const uint8_t*)dproofs.p, (const Fr*)dpub.p, (const uint64_t*)drho.p, n_proofs, dstruct.p, dP.p,
-               dcpart.p, dspart.p);
-    G16_LAUNCH(k_agg_sums, n_pub + 2, AGG_BLOCK, 0, nullptr, (const VkDev*)dvk.p, n_pub, nb,
-               (const G1XYZZ*)dcpart.p, (const Fr*)dspart.p, rho_sum, dkey.p, dscal.p);
-    G16_LAUNCH(k_agg_x, 1, AGG_BLOCK, 0, nullptr, (const G1Affine*)dic.p, n_pub, (const U256*)dscal.p, dkey.p);
-    G16_LAUNCH(k_agg_miller, nbm, AGG_BLOCK, 0, nullptr, (const VkDev*)dvk.p, (const uint8_t*)dproofs.p,
-               (const G1Affine*)dP.p, (const uint8_t*)dstruct.p, (const AggKey*)dkey.p, n_proofs, dfpart.p);
-    G16_LAUNCH(k_agg_tail, 1, AGG_BLOCK, 0, nullptr, (const VkDev*)dvk.p, (const F12*)dfpart.p, nbm,
-               (const uint8_t*)dstruct.p, n_proofs, dok.p);
-    G16_HIP(hipGetLastError());
-    G16_HIP(hipDeviceSynchronize());
-    G16_HIP(hipMemcpy(ok_out, dok.p, 1, hipMemcpyDeviceToHost));
-    if (structural_out) G16_HIP(hipMemcpy(structural_out, dstruct.p, n_proofs, hipMemcpyDeviceToHost));
-    return G16_OK;
-  } catch (const HipError&) {
-    return G16_ERR_HIP;
-  } catch (const std::exception&) {
-    return G16_ERR_INTERNAL;
-  }
+                                           const uint64_t* public_inputs, uint32_t n_proofs, const uint64_t* rho,
+                                           uint8_t* ok_out, uint8_t* structural_out) {
+  return verify_aggregate_groups(device, &vk, &n_proofs, 1, proofs, public_inputs, rho, ok_out, structural_out);
+}
+
+extern "C" g16_status g16_verify_batch_keys(int device, const g16_vk_desc* const* vks, const uint32_t* counts,
+                                            uint32_t n_keys, const uint8_t* proofs, const uint64_t* public_inputs,
+                                            uint8_t* ok_out) {
+  return verify_batch_groups(device, vks, counts, n_keys, proofs, public_inputs, ok_out);
+}
+
+extern "C" g16_status g16_verify_aggregate_keys(int device, const g16_vk_desc* const* vks, const uint32_t* counts,
+                                                uint32_t n_keys, const uint8_t* proofs,
+                                                const uint64_t* public_inputs, const uint64_t* rho, uint8_t* ok_out,
+                                                uint8_t* structural_out) {
+  return verify_aggregate_groups(device, vks, counts, n_keys, proofs, public_inputs, rho, ok_out, structural_out);
 }

@@ -350,7 +350,9 @@ typedef struct {
  * n_proofs x (ic_count - 1) x 4 u64 Montgomery Fr.  The reference only ever pairs a DESERIALISED
  * Proof, and ark-serialize (Validate::Yes) rejects what this call therefore rejects itself with
  * ok = 0 before any pairing: a coordinate that is not canonical (stored value >= q), a point off its
- * curve, a B outside the prime-order subgroup of the twist ([r] B != infinity).                     */
+ * curve, a B outside the prime-order subgroup of the twist ([r] B != infinity).
+ * This is g16_verify_batch_keys (below) with one group, and shares its limit: n_proofs + 3 lanes are
+ * indexed in 32 bits, so n_proofs > 2^32 - 4 is G16_ERR_INVALID.                                    */
 g16_status g16_verify_batch(int device, const g16_vk_desc* vk, const uint8_t* proofs,
                             const uint64_t* public_inputs, uint32_t n_proofs, uint8_t* ok_out);
 
@@ -375,7 +377,9 @@ g16_status g16_verify_batch(int device, const g16_vk_desc* vk, const uint8_t* pr
  *      learns which proofs were malformed without a second call).
  * proofs, public_inputs, vk and the treatment of infinity (a pair with an infinite side contributes
  * 1) are those of g16_verify_batch, so the verdict on a batch of one proof is g16_verify_batch's.
- * n_proofs == 0: G16_OK, *ok_out = 1.  A zero rho entry: G16_ERR_INVALID.                          */
+ * n_proofs == 0: G16_OK, *ok_out = 1.  A zero rho entry: G16_ERR_INVALID.
+ * This is g16_verify_aggregate_keys (below) with one group, and shares its limit: n_proofs + 3 lanes
+ * are indexed in 32 bits, so n_proofs > 2^32 - 4 is G16_ERR_INVALID.                                */
 g16_status g16_verify_aggregate(int device, const g16_vk_desc* vk, const uint8_t* proofs,
                                 const uint64_t* public_inputs, uint32_t n_proofs,
                                 const uint64_t* rho, uint8_t* ok_out, uint8_t* structural_out);

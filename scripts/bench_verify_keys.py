@@ -13,7 +13,9 @@ a time limit of its own (SIGALRM with its default action ends the process, also 
 What is measured against is the loop of the existing calls in this run, never a figure of another day.  The gate,
 per shape and per pair (single call, loop), with spread = the larger of the two differences between repetitions:
 K >= 2: the single call's slower repetition is faster than the loop's faster one; K = 1: the single call's faster
-repetition is within the spread of the loop's.  A shape that misses it is reported, the record is still written,
+repetition is within the spread of the loop's.  The single-key calls are the one-group case of the code the _keys calls
+run, so at K = 1 the script compares a code path with itself (the row shows the repetition spread and nothing else);
+the K >= 2 gate is the one that decides.  A shape that misses it is reported, the record is still written,
 and the exit status is 1."""
 import argparse
 import hashlib

@@ -137,3 +137,54 @@ def test_verify_batch_rejects_what_deserialisation_rejects(lib, golden):
     batch = [good, cof, mixed] + noncanon + [good]
     got = cc.verify_batch(vk, batch, [[33]] * len(batch), lib=lib)
     assert got == [True, False, False] + [False] * len(noncanon) + [True]
+
+
+def test_single_key_abi_refusals(lib, golden, request):
+    """what g16_verify_batch and g16_verify_aggregate refuse at the C ABI before any kernel runs, each with
+    G16_ERR_INVALID and ok_out untouched: a NULL vk, a NULL ic, ic_count = 0, NULL proofs or NULL public inputs
+    where n_proofs > 0 needs them, a NULL ok_out (the per-proof call needs it when n_proofs > 0, the aggregate call
+    always), a zero coefficient, a device number below 0 or past the last device.  n_proofs = 0 is G16_OK: the
+    aggregate call writes 1, the per-proof call writes nothing."""
+    import ctypes as C
+    import circom_compat_amd as cc
+    from circom_compat_amd import _binding as B
+    from test_verify_aggregate import _test_zkey_batch
+    vk, _opk, raws, pubs = _test_zkey_batch(lib, golden, 2)
+    d, buf, pb, n, _ic = cc._verify_args(vk, raws, pubs, lib)
+    assert n == 2 and d.ic_count == 2                                    # n_pub = 1
+    n_dev = 1                                                            # the emulator's
+    if request.node.callspec.params["lib"] == "gpu":
+        import torch
+        n_dev = torch.cuda.device_count()
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    ok = np.full(2, 7, dtype=np.uint8)
+
+    def desc(**kw):
+        c = B.VkDesc.from_buffer_copy(d)
+        for k, v in kw.items():
+            setattr(c, k, v)
+        return C.byref(c)
+
+    def batch(dev=0, vkp=C.byref(d), proofs=ptr(buf), pub=ptr(pb), cnt=2, out=ptr(ok)):
+        return lib.g16_verify_batch(dev, vkp, proofs, pub, cnt, out)
+
+    def agg(dev=0, vkp=C.byref(d), proofs=ptr(buf), pub=ptr(pb), cnt=2, out=ptr(ok), rho=None):
+        return lib.g16_verify_aggregate(dev, vkp, proofs, pub, cnt, rho, out, None)
+
+    zero = np.array([[5, 0], [0, 0]], dtype=np.uint64)
+    for call in (batch, agg):
+        for kw in (dict(vkp=None), dict(vkp=desc(ic=None)), dict(vkp=desc(ic_count=0)), dict(proofs=None),
+                   dict(pub=None), dict(dev=-1), dict(dev=n_dev)):
+            assert call(**kw) == B.G16_ERR_INVALID, (call.__name__, kw)
+            assert list(ok) == [7, 7], (call.__name__, kw)
+    assert batch(out=None) == B.G16_ERR_INVALID
+    assert agg(cnt=0, out=None) == B.G16_ERR_INVALID
+    assert agg(rho=ptr(zero)) == B.G16_ERR_INVALID
+    assert agg(rho=ptr(zero), dev=-1) == B.G16_ERR_INVALID
+    assert list(ok) == [7, 7]
+    # no proofs: nothing to refuse in proofs, public inputs or (per proof) ok_out
+    assert batch(cnt=0, proofs=None, pub=None, out=None) == B.G16_OK
+    assert batch(cnt=0) == B.G16_OK
+    assert list(ok) == [7, 7]
+    assert agg(cnt=0, proofs=None, pub=None) == B.G16_OK
+    assert list(ok) == [1, 7]

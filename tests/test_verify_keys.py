@@ -3,7 +3,8 @@ cc.verify_aggregate_keys / cc.verify_batch_keys / cc.verify_batch_fast_keys).  A
 under it; every verdict must be what the single-key call gives on that group alone.  Expected verdicts come from
 the oracle (o.verify_proof, and the combined equation as test_verify_aggregate._oracle_aggregate evaluates it)
 for groups of at most 5 proofs; larger groups are compared with the single-key calls cc.verify_aggregate /
-cc.verify_batch, which are the reference here and not the code under test."""
+cc.verify_batch on a planted wrong input.  The single-key calls are the one-group case of the same device code, so
+at that size the oracle-checked small groups and the planted input carry the meaning, not the comparison."""
 import ctypes as C
 import os
 import random
@@ -260,6 +261,27 @@ def test_structural_rejects_between_valid_groups(lib, golden):
     assert want == [[True] * 3, [i not in where for i in range(14)], [True] * 2]
     assert cc.verify_batch_keys([g.arg() for g in gs], lib=lib) == want
     assert cc.verify_batch_fast_keys([g.arg() for g in gs], lib=lib) == want
+
+
+def test_single_key_structural_out_matches_groups(lib, golden):
+    """structural_out of the single-key call at the C ABI is the flat structural array of the one-group call"""
+    import circom_compat_amd as cc
+    vk, opk, batch, bpubs, where = _malformed_batch(lib, golden)
+    n = 5
+    want = [i not in where for i in range(n)]
+    assert True in want and False in want
+    g = G((vk, opk, batch, bpubs), n)
+    rho = _rhos(9, [g])
+    d, buf, pb, cnt, _ic = cc._verify_args(g.vk, g.raws, g.pubs, lib)
+    assert cnt == n
+    rho_arr = cc._rho_array(rho[0], n, "one coefficient per proof")
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    ok = np.full(1, 7, dtype=np.uint8)
+    flat = np.full(n + 1, 7, dtype=np.uint8)
+    assert lib.g16_verify_aggregate(0, C.byref(d), ptr(buf), ptr(pb), n, ptr(rho_arr), ptr(ok), ptr(flat)) == 0
+    assert list(ok) == [0] and flat[n] == 7                                          # n bytes, no more
+    assert [bool(x) for x in flat[:n]] == want
+    assert _agg_keys(cc, lib, [g], rho, return_structural=True) == ([False], [want])
 
 
 def test_batch_fast_keys_makes_at_most_two_library_calls(lib, golden):
