@@ -301,6 +301,8 @@ class R1CS:
         h = file.header
         self.num_inputs = 1 + h.n_pub_in + h.n_pub_out
         self.num_variables = h.n_wires
+        if self.num_inputs > self.num_variables:    # the loader refuses such a header; one built by hand gets here
+            raise SerializationError(B.G16_ERR_IO, "1 + n_pub_in + n_pub_out exceeds n_wires")
         self.num_aux = self.num_variables - self.num_inputs
         self.a, self.b, self.c = file.a, file.b, file.c
         self.num_constraints = h.n_constraints

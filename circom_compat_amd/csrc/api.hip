@@ -719,18 +719,9 @@ g16_status ctx_create_impl(const g16_key_desc* key, const g16_csr* a, const g16_
     return bad(G16_ERR_INVALID, "n_vars < n_public+1");
   // the kernels index w[col[j]] and col/coeff[row_ptr[i] .. row_ptr[i+1]) unchecked: validate once
   // here (the reference panics on an out-of-bounds wire index in evaluate_constraint)
-  for (const g16_csr* mtx : {a, b}) {
-    if (!mtx->row_ptr || (mtx->nnz && (!mtx->col || !mtx->coeff)))
-      return bad(G16_ERR_INVALID, "matrix with null arrays");
-    if (mtx->row_ptr[0] != 0 || mtx->row_ptr[num_constraints] != mtx->nnz)
-      return bad(G16_ERR_INVALID, "matrix row_ptr does not span [0, nnz]");
-    for (uint32_t i = 0; i < num_constraints; ++i)
-      if (mtx->row_ptr[i] > mtx->row_ptr[i + 1])
-        return bad(G16_ERR_INVALID, "matrix row_ptr is not monotone");
-    for (uint64_t j = 0; j < mtx->nnz; ++j)
-      if (mtx->col[j] >= key->n_vars)
-        return bad(G16_ERR_INVALID, "matrix wire index >= n_vars");
-  }
+  for (const g16_csr* mtx : {a, b})
+    if (const char* why = csr_check(mtx, num_constraints, key->n_vars, "matrix wire index >= n_vars"))
+      return bad(G16_ERR_INVALID, why);
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
     return bad(G16_ERR_NO_DEVICE, "no HIP device visible: this library has no CPU fallback");

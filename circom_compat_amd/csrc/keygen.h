@@ -2,6 +2,7 @@
 // setup_srs.hip from a powers-of-tau string) and keygen.hip's power / fixed-base kernels behind host calls.
 #pragma once
 #include "msm.h"
+#include "spmv.h"
 
 struct g16_setup {
   uint32_t n_vars = 0, n_public = 0, domain = 0;
@@ -11,6 +12,14 @@ struct g16_setup {
 };
 
 namespace g16 {
+
+// The transposed matrices both key generators take (n_vars rows each, a column is a constraint), checked on the
+// host before anything is allocated, copied or launched (csr_check, spmv.h).  A column indexes the Lagrange basis
+// of the domain: `at` carries the n_public + 1 rows snarkjs appends behind the constraints and may name
+// num_constraints + n_public + 1 of them, bt and ct only the num_constraints proper -- both within the domain.
+// NULL when all three are sound, else what is wrong.
+const char* setup_matrices_check(const g16_csr* at, const g16_csr* bt, const g16_csr* ct, uint32_t n_vars,
+                                 uint32_t n_public, uint32_t num_constraints);
 
 G1Affine g1_generator();
 G2Affine g2_generator();

@@ -129,6 +129,15 @@ void download(std::vector<uint8_t>& dst, const T* dev, size_t count) {
 // ---- the pieces setup_srs.hip shares (keygen.h) --------------------------------------------------
 namespace g16 {
 
+const char* setup_matrices_check(const g16_csr* at, const g16_csr* bt, const g16_csr* ct, uint32_t n_vars,
+                                 uint32_t n_public, uint32_t num_constraints) {
+  if ((uint64_t)n_vars < (uint64_t)n_public + 1) return "n_vars < n_public + 1";
+  const char* const beyond = "transposed matrix names a constraint beyond num_constraints (+ n_public + 1 for at)";
+  if (const char* why = csr_check(at, n_vars, (uint64_t)num_constraints + n_public + 1, beyond)) return why;
+  if (const char* why = csr_check(bt, n_vars, num_constraints, beyond)) return why;
+  return csr_check(ct, n_vars, num_constraints, beyond);
+}
+
 G1Affine g1_generator() { return G1Affine{Fq::one(), Fq::one() + Fq::one()}; }
 
 G2Affine g2_generator() {  // reference src/zkey.rs:443-463
@@ -189,6 +198,12 @@ g16_status g16_setup_create_ex(int device, const g16_csr* at, const g16_csr* bt,
   if (!at || !bt || !ct || !toxic || !out) return G16_ERR_INVALID;
   if (reduction != G16_REDUCTION_CIRCOM && reduction != G16_REDUCTION_LIBSNARK) return G16_ERR_INVALID;
   *out = nullptr;
+  // the prover's own limit (qap.rs:63-68): n <= 2^27; on the sizes alone, as in g16_setup_from_srs
+  if ((uint64_t)num_constraints + n_public + 1 > ((uint64_t)1 << 27)) return G16_ERR_DOMAIN_TOO_LARGE;
+  if (const char* why = setup_matrices_check(at, bt, ct, n_vars, n_public, num_constraints)) {
+    t_setup_err = why;
+    return G16_ERR_INVALID;
+  }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return G16_ERR_NO_DEVICE;
   g16_setup* S = new g16_setup();

@@ -15,7 +15,11 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <exception>
 #include <map>
+#include <memory>
+#include <new>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -32,6 +36,24 @@ thread_local std::string t_err;
 g16_status fail(g16_status code, const std::string& m) {
   t_err = m;
   return code;
+}
+
+// No exception leaves an extern "C" function of g16_loaders.h: every entry point that allocates runs its body in
+// here.  A handle that is still half built sits in a unique_ptr inside the body, so it is freed on the way out and
+// *out stays NULL.
+template <class Body>
+g16_status guarded(Body&& body) {
+  try {
+    return body();
+  } catch (const std::bad_alloc&) {
+    return fail(G16_ERR_INTERNAL, "out of memory");
+  } catch (const std::length_error&) {
+    return fail(G16_ERR_INTERNAL, "out of memory");
+  } catch (const std::exception& e) {
+    return fail(G16_ERR_INTERNAL, e.what());
+  } catch (...) {
+    return fail(G16_ERR_INTERNAL, "unknown exception");
+  }
 }
 
 bool read_file(const char* path, std::vector<uint8_t>& out, std::string& err) {
@@ -395,8 +417,15 @@ g16_status r1cs_parse(const uint8_t* d, size_t n, g16_r1cs* R) {
     H.n_labels = h.u64();
     H.n_constraints = h.u32();
     if (!h.ok) return fail(G16_ERR_IO, "unexpected end of file");
+    // 64-bit: n_pub_in = 0xFFFFFFFF must not wrap num_inputs to 0, nor num_aux past n_wires (R1CS::from, :28-30)
+    if ((uint64_t)1 + H.n_pub_in + H.n_pub_out > (uint64_t)H.n_wires)
+      return fail(G16_ERR_IO, "1 + n_pub_in + n_pub_out exceeds n_wires");
   }
   if (!sec.count(2)) return fail(G16_ERR_IO, "No section offset for constraint type found");
+  // a constraint is at least its three term counts: a count the section cannot hold is refused before anything
+  // is reserved for it (n_constraints = 0xFFFFFFFF would ask for 3 x 16 GiB of row pointers)
+  if ((uint64_t)H.n_constraints > sec[2].size / 12)
+    return fail(G16_ERR_IO, "n_constraints exceeds what the constraint section can hold");
   {
     Cursor k(d, n, sec[2].pos);
     CsrOwned* M[3] = {&R->A, &R->B, &R->C};
@@ -501,33 +530,28 @@ const char* g16_loader_last_error(void) { return t_err.c_str(); }
 g16_status g16_zkey_open_mem(const uint8_t* data, size_t len, g16_zkey** out) {
   if (!data || !out) return fail(G16_ERR_INVALID, "null argument");
   *out = nullptr;
-  g16_zkey* z = new g16_zkey();
-  z->data.copy_of(data, len);
-  g16_status st = zkey_parse(z);
-  if (st != G16_OK) {
-    delete z;
-    return st;
-  }
-  *out = z;
-  return G16_OK;
+  return guarded([&]() -> g16_status {
+    std::unique_ptr<g16_zkey> z(new g16_zkey());
+    z->data.copy_of(data, len);
+    const g16_status st = zkey_parse(z.get());
+    if (st != G16_OK) return st;
+    *out = z.release();
+    return G16_OK;
+  });
 }
 
 g16_status g16_zkey_open(const char* path, g16_zkey** out) {
   if (!path || !out) return fail(G16_ERR_INVALID, "null argument");
   *out = nullptr;
-  g16_zkey* z = new g16_zkey();
-  std::string err;
-  if (!z->data.map_file(path, err)) {
-    delete z;
-    return fail(G16_ERR_IO, err);
-  }
-  g16_status st = zkey_parse(z);
-  if (st != G16_OK) {
-    delete z;
-    return st;
-  }
-  *out = z;
-  return G16_OK;
+  return guarded([&]() -> g16_status {
+    std::unique_ptr<g16_zkey> z(new g16_zkey());
+    std::string err;
+    if (!z->data.map_file(path, err)) return fail(G16_ERR_IO, err);
+    const g16_status st = zkey_parse(z.get());
+    if (st != G16_OK) return st;
+    *out = z.release();
+    return G16_OK;
+  });
 }
 
 void g16_zkey_close(g16_zkey* z) { delete z; }
@@ -564,8 +588,14 @@ const uint8_t* g16_zkey_ic(const g16_zkey* z, uint32_t* count) {
   return z->data.data() + z->sec.at(3).pos;
 }
 
+static g16_status zkey_matrices_body(g16_zkey* z, g16_matrices* out);
+
 g16_status g16_zkey_matrices(g16_zkey* z, g16_matrices* out) {
   if (!z || !out) return fail(G16_ERR_INVALID, "null argument");
+  return guarded([&] { return zkey_matrices_body(z, out); });
+}
+
+static g16_status zkey_matrices_body(g16_zkey* z, g16_matrices* out) {
   if (!z->have_matrices) {
     // BinFile::matrices (zkey.rs:151-196)
     const uint8_t* d = z->data.data();
@@ -638,33 +668,28 @@ g16_status g16_zkey_matrices(g16_zkey* z, g16_matrices* out) {
 g16_status g16_ptau_open_mem(const uint8_t* data, size_t len, g16_ptau** out) {
   if (!data || !out) return fail(G16_ERR_INVALID, "null argument");
   *out = nullptr;
-  g16_ptau* z = new g16_ptau();
-  z->data.copy_of(data, len);
-  g16_status st = ptau_parse(z);
-  if (st != G16_OK) {
-    delete z;
-    return st;
-  }
-  *out = z;
-  return G16_OK;
+  return guarded([&]() -> g16_status {
+    std::unique_ptr<g16_ptau> z(new g16_ptau());
+    z->data.copy_of(data, len);
+    const g16_status st = ptau_parse(z.get());
+    if (st != G16_OK) return st;
+    *out = z.release();
+    return G16_OK;
+  });
 }
 
 g16_status g16_ptau_open(const char* path, g16_ptau** out) {
   if (!path || !out) return fail(G16_ERR_INVALID, "null argument");
   *out = nullptr;
-  g16_ptau* z = new g16_ptau();
-  std::string err;
-  if (!z->data.map_file(path, err)) {
-    delete z;
-    return fail(G16_ERR_IO, err);
-  }
-  g16_status st = ptau_parse(z);
-  if (st != G16_OK) {
-    delete z;
-    return st;
-  }
-  *out = z;
-  return G16_OK;
+  return guarded([&]() -> g16_status {
+    std::unique_ptr<g16_ptau> z(new g16_ptau());
+    std::string err;
+    if (!z->data.map_file(path, err)) return fail(G16_ERR_IO, err);
+    const g16_status st = ptau_parse(z.get());
+    if (st != G16_OK) return st;
+    *out = z.release();
+    return G16_OK;
+  });
 }
 
 void g16_ptau_close(g16_ptau* p) { delete p; }
@@ -690,8 +715,14 @@ g16_status g16_ptau_srs(const g16_ptau* p, g16_srs_desc* out) {
   return G16_OK;
 }
 
+static g16_status ptau_lagrange_body(const g16_ptau* p, g16_srs_lagrange_desc* out);
+
 g16_status g16_ptau_lagrange(const g16_ptau* p, g16_srs_lagrange_desc* out) {
   if (!p || !out) return fail(G16_ERR_INVALID, "null argument");
+  return guarded([&] { return ptau_lagrange_body(p, out); });
+}
+
+static g16_status ptau_lagrange_body(const g16_ptau* p, g16_srs_lagrange_desc* out) {
   memset(out, 0, sizeof *out);
   const uint32_t power = p->hdr.power;
   if (power > 27) return fail(G16_ERR_IO, "ptau: Lagrange sections of power " + std::to_string(power) + " > 27");
@@ -717,7 +748,7 @@ static g16_status ptau_write_impl(const char* path, const g16_srs_desc* srs, con
                                   uint32_t power);
 
 g16_status g16_ptau_write(const char* path, const g16_srs_desc* srs, uint32_t power) {
-  return ptau_write_impl(path, srs, nullptr, power);
+  return guarded([&] { return ptau_write_impl(path, srs, nullptr, power); });
 }
 
 g16_status g16_ptau_write_prepared(const char* path, const g16_srs_desc* srs, const g16_srs_lagrange_desc* lag,
@@ -726,7 +757,7 @@ g16_status g16_ptau_write_prepared(const char* path, const g16_srs_desc* srs, co
     return fail(G16_ERR_INVALID, "null argument");
   if (power > 27) return fail(G16_ERR_INVALID, "ptau: Lagrange sections need power <= 27");
   if (lag->power != power) return fail(G16_ERR_INVALID, "ptau: the Lagrange set is not of this power");
-  return ptau_write_impl(path, srs, lag, power);
+  return guarded([&] { return ptau_write_impl(path, srs, lag, power); });
 }
 
 static g16_status ptau_write_impl(const char* path, const g16_srs_desc* srs, const g16_srs_lagrange_desc* lag,
@@ -778,22 +809,25 @@ static g16_status ptau_write_impl(const char* path, const g16_srs_desc* srs, con
 g16_status g16_r1cs_open_mem(const uint8_t* data, size_t len, g16_r1cs** out) {
   if (!data || !out) return fail(G16_ERR_INVALID, "null argument");
   *out = nullptr;
-  g16_r1cs* r = new g16_r1cs();
-  g16_status st = r1cs_parse(data, len, r);
-  if (st != G16_OK) {
-    delete r;
-    return st;
-  }
-  *out = r;
-  return G16_OK;
+  return guarded([&]() -> g16_status {
+    std::unique_ptr<g16_r1cs> r(new g16_r1cs());
+    const g16_status st = r1cs_parse(data, len, r.get());
+    if (st != G16_OK) return st;
+    *out = r.release();
+    return G16_OK;
+  });
 }
 
 g16_status g16_r1cs_open(const char* path, g16_r1cs** out) {
   if (!path || !out) return fail(G16_ERR_INVALID, "null argument");
-  std::vector<uint8_t> buf;
-  std::string err;
-  if (!read_file(path, buf, err)) return fail(G16_ERR_IO, err);
-  return g16_r1cs_open_mem(buf.data(), buf.size(), out);
+  *out = nullptr;
+  return guarded([&]() -> g16_status {
+    std::vector<uint8_t> buf;
+    std::string err;
+    if (!read_file(path, buf, err)) return fail(G16_ERR_IO, err);
+    if (buf.empty()) return fail(G16_ERR_IO, "Invalid magic number");  // no data() of an empty vector downstream
+    return g16_r1cs_open_mem(buf.data(), buf.size(), out);
+  });
 }
 
 void g16_r1cs_close(g16_r1cs* r) { delete r; }
@@ -820,15 +854,17 @@ const uint64_t* g16_r1cs_wire_mapping(const g16_r1cs* r, uint32_t* count) {
 
 g16_status g16_wtns_read_mem(const uint8_t* data, size_t len, uint64_t** out, uint32_t* n) {
   if (!data || !out || !n) return fail(G16_ERR_INVALID, "null argument");
-  return wtns_parse(data, len, out, n);
+  return guarded([&] { return wtns_parse(data, len, out, n); });
 }
 
 g16_status g16_wtns_read(const char* path, uint64_t** out, uint32_t* n) {
   if (!path || !out || !n) return fail(G16_ERR_INVALID, "null argument");
-  std::vector<uint8_t> buf;
-  std::string err;
-  if (!read_file(path, buf, err)) return fail(G16_ERR_IO, err);
-  return wtns_parse(buf.data(), buf.size(), out, n);
+  return guarded([&]() -> g16_status {
+    std::vector<uint8_t> buf;
+    std::string err;
+    if (!read_file(path, buf, err)) return fail(G16_ERR_IO, err);
+    return wtns_parse(buf.data(), buf.size(), out, n);
+  });
 }
 
 // .wtns as it lies in the file: the header is checked, the values are handed out where they are (the device
@@ -839,34 +875,32 @@ struct g16_wtns {
   uint32_t n = 0;
 };
 
-static g16_status wtns_open_view(g16_wtns* w, g16_wtns** out) {
+static g16_status wtns_open_view(std::unique_ptr<g16_wtns>& w, g16_wtns** out) {
   const g16_status st = wtns_locate(w->data.data(), w->data.size(), &w->pos, &w->n);
-  if (st != G16_OK) {
-    delete w;
-    return st;
-  }
-  *out = w;
+  if (st != G16_OK) return st;
+  *out = w.release();
   return G16_OK;
 }
 
 g16_status g16_wtns_open(const char* path, g16_wtns** out) {
   if (!path || !out) return fail(G16_ERR_INVALID, "null argument");
   *out = nullptr;
-  g16_wtns* w = new g16_wtns();
-  std::string err;
-  if (!w->data.map_file(path, err)) {
-    delete w;
-    return fail(G16_ERR_IO, err);
-  }
-  return wtns_open_view(w, out);
+  return guarded([&]() -> g16_status {
+    std::unique_ptr<g16_wtns> w(new g16_wtns());
+    std::string err;
+    if (!w->data.map_file(path, err)) return fail(G16_ERR_IO, err);
+    return wtns_open_view(w, out);
+  });
 }
 
 g16_status g16_wtns_open_mem(const uint8_t* data, size_t len, g16_wtns** out) {
   if (!data || !out) return fail(G16_ERR_INVALID, "null argument");
   *out = nullptr;
-  g16_wtns* w = new g16_wtns();
-  w->data.copy_of(data, len);
-  return wtns_open_view(w, out);
+  return guarded([&]() -> g16_status {
+    std::unique_ptr<g16_wtns> w(new g16_wtns());
+    w->data.copy_of(data, len);
+    return wtns_open_view(w, out);
+  });
 }
 
 uint32_t g16_wtns_count(const g16_wtns* w) { return w ? w->n : 0; }
@@ -885,6 +919,21 @@ g16_status g16_zkey_write(const char* path, const g16_key_desc* key, const uint8
                           const uint8_t gamma_g2[128], const g16_csr* a, const g16_csr* b,
                           uint32_t num_constraints) {
   if (!path || !key || !ic || !gamma_g2 || !a || !b) return fail(G16_ERR_INVALID, "null argument");
+  // the descriptor is checked before the file is created: every length below is derived from it
+  if ((uint64_t)key->n_vars < (uint64_t)key->n_public + 1) return fail(G16_ERR_INVALID, "zkey: n_vars < n_public + 1");
+  const uint64_t n_l = (uint64_t)key->n_vars - key->n_public - 1;
+  if ((key->n_vars && (!key->a_query || !key->b_g1_query || !key->b_g2_query)) || (n_l && !key->l_query) ||
+      (key->domain_size && !key->h_query))
+    return fail(G16_ERR_INVALID, "zkey: a query array is NULL but its count is not zero");
+  for (const g16_csr* m : {a, b}) {
+    if (!m->row_ptr || (m->nnz && (!m->col || !m->coeff))) return fail(G16_ERR_INVALID, "zkey: matrix with null arrays");
+    if (m->row_ptr[0] != 0 || m->row_ptr[num_constraints] != m->nnz)
+      return fail(G16_ERR_INVALID, "zkey: matrix row_ptr does not span [0, nnz]");
+    for (uint32_t i = 0; i < num_constraints; ++i)
+      if (m->row_ptr[i] > m->row_ptr[i + 1]) return fail(G16_ERR_INVALID, "zkey: matrix row_ptr is not monotone");
+  }
+  if (a->nnz > UINT32_MAX || b->nnz > UINT32_MAX || a->nnz + b->nnz + key->n_public + 1 > UINT32_MAX)
+    return fail(G16_ERR_INVALID, "zkey: the coefficient count does not fit in 32 bits");
   FILE* f = fopen(path, "wb");
   if (!f) return fail(G16_ERR_IO, std::string("cannot create ") + path);
   bool ok = true;
@@ -1085,10 +1134,10 @@ g16_status ark_layout(const uint8_t* data, size_t len, uint32_t flags, g16_ark_l
 }  // namespace
 
 g16_status g16_ark_pk_layout(const uint8_t* data, size_t len, uint32_t flags, g16_ark_layout* out) {
-  return ark_layout(data, len, flags, out, true);
+  return guarded([&] { return ark_layout(data, len, flags, out, true); });
 }
 g16_status g16_ark_vk_layout(const uint8_t* data, size_t len, uint32_t flags, g16_ark_layout* out) {
-  return ark_layout(data, len, flags, out, false);
+  return guarded([&] { return ark_layout(data, len, flags, out, false); });
 }
 
 }  // extern "C"

@@ -369,7 +369,7 @@ static g16_status setup_impl(int device, const g16_csr* at, const g16_csr* bt, c
     if (lag->power < (uint32_t)k) return G16_ERR_INVALID;
     if (!lag->tau_g1 || !lag->tau_g2 || !lag->alpha_tau_g1 || !lag->beta_tau_g1) return G16_ERR_INVALID;
   }
-  if (N < num_inputs || !at->row_ptr || !bt->row_ptr || !ct->row_ptr) return G16_ERR_INVALID;
+  if (setup_matrices_check(at, bt, ct, N, n_public, num_constraints)) return G16_ERR_INVALID;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return G16_ERR_NO_DEVICE;
   if (device < 0 || device >= ndev) return G16_ERR_INVALID;

@@ -27,10 +27,18 @@
 #pragma once
 #include <functional>
 
+#include "../../include/g16_amd.h"
 #include "common.h"
 #include "field29.h"
 
 namespace g16 {
+
+// A matrix as a caller hands it in, checked on the host before anything is allocated, copied or launched: the
+// kernels walk col / coeff[row_ptr[i] .. row_ptr[i + 1]) and index a vector of col_bound entries with col[j],
+// both unchecked.  `rows` rows.  NULL when it is sound, else what is wrong: a NULL array that is needed;
+// row_ptr[0] != 0, row_ptr[rows] != nnz or a step back in between; a col[j] >= col_bound, in the caller's words
+// (a column is a wire for the prover's matrices, a constraint for the key generators' transposes).
+const char* csr_check(const g16_csr* m, uint32_t rows, uint64_t col_bound, const char* col_out_of_range);
 
 constexpr uint32_t SPMV_ONE = 0x80000000u;  // col bit 31: coefficient == 1
 constexpr uint32_t SPMV_SHORT = 4;

@@ -25,6 +25,16 @@ __global__ void __launch_bounds__(256) k_spmv_cook(uint32_t* col, Fr* val, size_
 
 }  // namespace
 
+const char* csr_check(const g16_csr* m, uint32_t rows, uint64_t col_bound, const char* col_out_of_range) {
+  if (!m || !m->row_ptr || (m->nnz && (!m->col || !m->coeff))) return "matrix with null arrays";
+  if (m->row_ptr[0] != 0 || m->row_ptr[rows] != m->nnz) return "matrix row_ptr does not span [0, nnz]";
+  for (uint32_t i = 0; i < rows; ++i)
+    if (m->row_ptr[i] > m->row_ptr[i + 1]) return "matrix row_ptr is not monotone";
+  for (uint64_t j = 0; j < m->nnz; ++j)
+    if (m->col[j] >= col_bound) return col_out_of_range;
+  return nullptr;
+}
+
 void spmv_cook(uint32_t* col_dev, Fr* val_dev, size_t nnz, hipStream_t stream) {
   if (!nnz) return;
   G16_LAUNCH(k_spmv_cook, ceil_div(nnz, 256), 256, 0, stream, col_dev, val_dev, nnz);

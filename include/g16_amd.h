@@ -598,7 +598,11 @@ g16_status g16_debug_alu_bench(int device, int kind, uint32_t blocks, uint32_t i
  * reference tests/groth16.rs:25; H basis: CircomReduction::h_query_scalars, src/circom/qap.rs:90-105).
  * at/bt/ct: TRANSPOSED constraint matrices (row = wire, col = constraint, Montgomery coefficients),
  * `at` including the n_public+1 rows snarkjs appends (row m+i holds coefficient 1 on signal i).
- * toxic: tau, alpha, beta, gamma, delta as 5 x 4 u64 Montgomery Fr.                               */
+ * toxic: tau, alpha, beta, gamma, delta as 5 x 4 u64 Montgomery Fr.
+ * The matrices are checked on the host before anything is allocated, copied or launched, here and in
+ * g16_setup_from_srs / g16_setup_from_prepared -- G16_ERR_INVALID and *out = NULL for: a NULL row_ptr, or NULL
+ * col / coeff with nnz > 0; row_ptr[0] != 0, row_ptr[n_vars] != nnz or a step back in between; a col of `at`
+ * >= num_constraints + n_public + 1, of bt or ct >= num_constraints; n_vars < n_public + 1.          */
 typedef struct g16_setup g16_setup;
 g16_status g16_setup_create(int device, const g16_csr* at, const g16_csr* bt, const g16_csr* ct,
                             uint32_t n_vars, uint32_t n_public, uint32_t num_constraints,

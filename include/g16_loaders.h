@@ -6,7 +6,11 @@
  *   g16_ptau_*  <- snarkjs .ptau (not parsed by the reference)
  * but hand back GPU-ready packed arrays (the on-disk point encoding IS the device encoding) from
  * one bulk read instead of one Read call per 32-byte field (src/zkey.rs:328-368).
- * All returned pointers are owned by the handle and stay valid until *_close.                    */
+ * All returned pointers are owned by the handle and stay valid until *_close.
+ * The files are untrusted: every count a header states is checked against the section that has to hold it before
+ * anything is reserved for it, and no C++ exception leaves these functions -- an allocation that fails comes back
+ * as G16_ERR_INTERNAL ("out of memory"), the half-built handle is freed and *out stays NULL
+ * (tests/loaders/loaders_main.cpp walks the truncations and mutations).                              */
 #ifndef G16_LOADERS_H
 #define G16_LOADERS_H
 
@@ -54,7 +58,10 @@ g16_status g16_zkey_matrices(g16_zkey* z, g16_matrices* out);
  * one minted by g16_setup_create) -- lets synthetic circuits go through the same file format and
  * loader path as circom/snarkjs artefacts (reference format notes: src/zkey.rs:1-27).  ic:
  * (n_public + 1) x 64 bytes; a, b: ConstraintMatrices rows WITHOUT the n_public + 1 rows snarkjs
- * appends (they are generated).                                                                    */
+ * appends (they are generated).  G16_ERR_INVALID, before the file is created: n_vars < n_public + 1; a NULL
+ * query array whose count is not zero; a or b with a NULL row_ptr, a row_ptr that does not run from 0 to nnz
+ * monotonically over num_constraints rows, or NULL col / coeff with nnz > 0; more than 2^32 - 1 coefficients
+ * (a's, b's and the appended rows together: the count field of section 4 is a u32).                        */
 g16_status g16_zkey_write(const char* path, const g16_key_desc* key, const uint8_t* ic,
                           const uint8_t gamma_g2[128], const g16_csr* a, const g16_csr* b,
                           uint32_t num_constraints);
@@ -133,6 +140,10 @@ typedef struct {
   uint32_t num_inputs, num_aux, num_variables;
 } g16_r1cs_header;
 
+/* G16_ERR_IO beyond the reference's own errors: n_constraints > size of section 2 / 12 (a constraint is at least
+ * its three term counts); 1 + n_pub_in + n_pub_out > n_wires, compared in 64 bits (num_inputs and num_aux
+ * would wrap).  A wire index is NOT compared with n_wires here, as in the reference: g16_ctx_create and the
+ * setup entry points refuse a matrix that names a wire or a constraint out of range.                     */
 g16_status g16_r1cs_open(const char* path, g16_r1cs** out);
 g16_status g16_r1cs_open_mem(const uint8_t* data, size_t len, g16_r1cs** out);
 void g16_r1cs_close(g16_r1cs* r);
