@@ -427,15 +427,20 @@ def fr_from_canonical(data, device=0, lib: Optional[B.Library] = None) -> np.nda
     return out
 
 
+def _phase_times(lib, export_name, phases) -> dict:
+    """the phase times behind one of the g16_..._times exports, by phase name"""
+    lib = lib or B.load()
+    ms = (C.c_float * len(phases))()
+    lib.check(getattr(lib, export_name)(ms, len(phases)))
+    return dict(zip(phases, (float(x) for x in ms)))
+
+
 FR_CONVERT_PHASES = ("upload", "convert", "download")
 
 
 def fr_from_canonical_times(lib: Optional[B.Library] = None) -> dict:
     """device milliseconds of this thread's last fr_from_canonical, by phase (g16_fr_convert_times)"""
-    lib = lib or B.load()
-    ms = (C.c_float * len(FR_CONVERT_PHASES))()
-    lib.check(lib.g16_fr_convert_times(ms, len(FR_CONVERT_PHASES)))
-    return dict(zip(FR_CONVERT_PHASES, [float(x) for x in ms]))
+    return _phase_times(lib, "g16_fr_convert_times", FR_CONVERT_PHASES)
 
 
 def _check_canonical(lib, st, ctx, bad):
@@ -1147,10 +1152,7 @@ def prepare_phase2(srs: Srs, power=None, device=0, lib: Optional[B.Library] = No
 def prepare_phase2_times(lib: Optional[B.Library] = None) -> dict:
     """milliseconds per phase of this thread's last prepare_phase2 (g16_srs_prepare_times), the phases of
     setup_from_srs_times"""
-    lib = lib or B.load()
-    ms = (C.c_float * len(SETUP_SRS_PHASES))()
-    lib.check(lib.g16_srs_prepare_times(ms, len(SETUP_SRS_PHASES)))
-    return dict(zip(SETUP_SRS_PHASES, (float(x) for x in ms)))
+    return _phase_times(lib, "g16_srs_prepare_times", SETUP_SRS_PHASES)
 
 
 class _CheckReport:
@@ -1427,10 +1429,7 @@ SRS_CONTRIBUTE_PHASES = ("upload", "scalars", "mul_g1", "mul_g2", "affine", "dow
 def contribute_srs_times(lib: Optional[B.Library] = None) -> dict:
     """milliseconds of device time per phase of this thread's last contribute_srs, summed over the chunks
     (g16_srs_contribute_times); the copies run under the kernels, so the sum exceeds the wall time"""
-    lib = lib or B.load()
-    ms = (C.c_float * len(SRS_CONTRIBUTE_PHASES))()
-    lib.check(lib.g16_srs_contribute_times(ms, len(SRS_CONTRIBUTE_PHASES)))
-    return dict(zip(SRS_CONTRIBUTE_PHASES, (float(x) for x in ms)))
+    return _phase_times(lib, "g16_srs_contribute_times", SRS_CONTRIBUTE_PHASES)
 
 
 SETUP_SRS_PHASES = ("upload", "ntt_g1", "ntt_g2", "ntt_h", "affine", "combine", "download")
@@ -1438,10 +1437,7 @@ SETUP_SRS_PHASES = ("upload", "ntt_g1", "ntt_g2", "ntt_h", "affine", "combine", 
 
 def setup_from_srs_times(lib: Optional[B.Library] = None) -> dict:
     """milliseconds per phase of this thread's last setup_from_srs (g16_setup_from_srs_times)"""
-    lib = lib or B.load()
-    ms = (C.c_float * len(SETUP_SRS_PHASES))()
-    lib.check(lib.g16_setup_from_srs_times(ms, len(SETUP_SRS_PHASES)))
-    return dict(zip(SETUP_SRS_PHASES, (float(x) for x in ms)))
+    return _phase_times(lib, "g16_setup_from_srs_times", SETUP_SRS_PHASES)
 
 
 class CircuitBindingReport:
@@ -2079,10 +2075,7 @@ def rerandomize_times(lib: Optional[B.Library] = None) -> dict:
     """milliseconds of device time per phase of this thread's last rerandomize / rerandomize_keys
     (g16_proofs_rerandomize_times): prepare = structural tests + scalars; mul_g1 and mul_g2 run side by side on two
     streams, so the sum exceeds the wall time"""
-    lib = lib or B.load()
-    ms = (C.c_float * len(RERANDOMIZE_PHASES))()
-    lib.check(lib.g16_proofs_rerandomize_times(ms, len(RERANDOMIZE_PHASES)))
-    return dict(zip(RERANDOMIZE_PHASES, (float(x) for x in ms)))
+    return _phase_times(lib, "g16_proofs_rerandomize_times", RERANDOMIZE_PHASES)
 
 
 class PreparedVerifyingKey:
@@ -2416,10 +2409,7 @@ GT_PHASES = ("upload", "g2_tests", "kernels", "download")
 def gt_times(lib: Optional[B.Library] = None) -> dict:
     """milliseconds of device time per phase of this thread's last pairing_products / gt_multiexp / codec call
     (g16_gt_times); g2_tests runs beside kernels on a second stream"""
-    lib = lib or B.load()
-    ms = (C.c_float * len(GT_PHASES))()
-    lib.check(lib.g16_gt_times(ms, len(GT_PHASES)))
-    return dict(zip(GT_PHASES, (float(x) for x in ms)))
+    return _phase_times(lib, "g16_gt_times", GT_PHASES)
 
 
 VERIFY_PREPARED_PHASES = ("upload", "inputs", "g2_tests", "pairing", "download", "prepare")
@@ -2428,10 +2418,7 @@ VERIFY_PREPARED_PHASES = ("upload", "inputs", "g2_tests", "pairing", "download",
 def verify_prepared_times(lib: Optional[B.Library] = None) -> dict:
     """milliseconds of device time per phase of this thread's last verify_prepared (g16_verify_prepared_times):
     g2_tests runs beside inputs and pairing on a second stream; prepare is the thread's last prepare_verifying_key"""
-    lib = lib or B.load()
-    ms = (C.c_float * len(VERIFY_PREPARED_PHASES))()
-    lib.check(lib.g16_verify_prepared_times(ms, len(VERIFY_PREPARED_PHASES)))
-    return dict(zip(VERIFY_PREPARED_PHASES, (float(x) for x in ms)))
+    return _phase_times(lib, "g16_verify_prepared_times", VERIFY_PREPARED_PHASES)
 
 
 # ---- MSM over caller-supplied bases, division by (X - z), KZG (include/g16_amd.h) ---------------------------------
@@ -2592,10 +2579,7 @@ KZG_PHASES = ("input", "divide_or_scalars", "msm", "output_or_pairing")
 
 def kzg_times(lib: Optional[B.Library] = None) -> dict:
     """device milliseconds per phase of this thread's last KzgKey.open / kzg_verify (g16_kzg_times)"""
-    lib = lib or B.load()
-    ms = (C.c_float * len(KZG_PHASES))()
-    lib.check(lib.g16_kzg_times(ms, len(KZG_PHASES)))
-    return dict(zip(KZG_PHASES, (float(x) for x in ms)))
+    return _phase_times(lib, "g16_kzg_times", KZG_PHASES)
 
 
 def _kzg_points(x, what) -> np.ndarray:

@@ -10,6 +10,7 @@
 #include <mutex>
 
 #include "ctx.h"
+#include "hostcall.h"
 
 using namespace g16;
 
@@ -1860,11 +1861,10 @@ g16_status g16_ctx_create_multi(const g16_key_desc* key, const g16_csr* a, const
   *out = nullptr;
   if (n_dev < 1 || n_dev > 64) return fail(nullptr, G16_ERR_INVALID, "n_dev must be in [1, 64]");
   if (!key->a_query) return fail(nullptr, G16_ERR_INVALID, "a multi-device ctx needs the proving key");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(nullptr, G16_ERR_NO_DEVICE, "no HIP device visible: this library has no CPU fallback");
   for (int i = 0; i < n_dev; ++i)
-    if (device_ids[i] < 0 || device_ids[i] >= ndev) return fail(nullptr, G16_ERR_INVALID, "bad device ordinal");
+    if (const g16_status ds = device_ok(device_ids[i]))
+      return fail(nullptr, ds, ds == G16_ERR_NO_DEVICE ? "no HIP device visible: this library has no CPU fallback"
+                                                       : "bad device ordinal");
   if (n_dev == 1) {
     g16_options o{};
     if (opt) o = *opt;
@@ -1884,8 +1884,7 @@ g16_status g16_check_satisfied(int device, const g16_csr* a, const g16_csr* b, c
                                uint32_t num_constraints, const uint64_t* w, size_t n_vars,
                                int64_t* first_unsatisfied) {
   if (!a || !b || !c_ || !w || !first_unsatisfied) return fail(nullptr, G16_ERR_INVALID, "null argument");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+  if (device_ok(0) != G16_OK)  // any device at all: a bad ordinal is hipSetDevice's to refuse, as G16_ERR_HIP
     return fail(nullptr, G16_ERR_NO_DEVICE, "no HIP device visible");
   for (const g16_csr* m : {a, b, c_})
     for (uint64_t j = 0; j < m->nnz; ++j)
@@ -1906,8 +1905,7 @@ g16_status g16_check_satisfied(int device, const g16_csr* a, const g16_csr* b, c
 
 g16_status g16_fft_in_place(int device, uint64_t* data, int log_n, int inverse, int algo) {
   if (!data || log_n < 0) return fail(nullptr, G16_ERR_INVALID, "bad argument");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+  if (device_ok(0) != G16_OK)  // any device at all: a bad ordinal is hipSetDevice's to refuse, as G16_ERR_HIP
     return fail(nullptr, G16_ERR_NO_DEVICE, "no HIP device visible");
   try {
     G16_HIP(hipSetDevice(device));

@@ -40,7 +40,6 @@ namespace g16 {
 namespace {
 
 constexpr uint32_t AK_DEFAULT_CHUNK = 1u << 18;
-constexpr uint32_t AK_MAX_CHUNK = 1u << 24;
 
 G16_HD void ak_load(Fq& f, const uint32_t* w) {
 #pragma unroll
@@ -203,16 +202,9 @@ g16_status run_codec(bool decode, int device, int group, uint32_t flags, const u
   if (in_stride < in_rec || out_stride < out_rec) return G16_ERR_INVALID;
   if (n == 0) return G16_OK;
   if (!in || !out) return G16_ERR_INVALID;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return G16_ERR_NO_DEVICE;
-  if (device < 0 || device >= ndev) return G16_ERR_INVALID;
-  try {
-    uint32_t chunk = AK_DEFAULT_CHUNK;
-    if (const char* e = getenv("G16_ARKSER_CHUNK")) {  // tests: points per staged chunk
-      const unsigned long long v = strtoull(e, nullptr, 0);
-      if (v >= 1 && v <= AK_MAX_CHUNK) chunk = (uint32_t)v;
-    }
-    if (chunk > n) chunk = (uint32_t)n;
+  if (const g16_status ds = device_ok(device)) return ds;
+  return guarded_call([&]() -> g16_status {
+    const uint32_t chunk = chunk_from_env("G16_ARKSER_CHUNK", AK_DEFAULT_CHUNK, n);
     const uint64_t n_chunks = (n + chunk - 1) / chunk;
 
     G16_HIP(hipSetDevice(device));
@@ -285,11 +277,7 @@ g16_status run_codec(bool decode, int device, int group, uint32_t flags, const u
     G16_HIP(hipMemcpy(&bad, dbad.p, sizeof bad, hipMemcpyDeviceToHost));
     if (n_bad) *n_bad = bad;
     return G16_OK;
-  } catch (const HipError&) {
-    return G16_ERR_HIP;
-  } catch (const std::exception&) {
-    return G16_ERR_INTERNAL;
-  }
+  });
 }
 
 const char* reason_text(uint8_t why) {

@@ -11,8 +11,8 @@
 //                stays affine in registers).  No per-lane table: a window of w bits would trade these for
 //                2^(w-2) full XYZZ additions (12M + 2S) plus 1 KiB of table per lane, which is scratch.
 //                No divergence: the digit schedule is uniform, only lanes at infinity idle.
-//   k_ct_affine  back to canonical affine with ONE Fermat inversion per CT_RUN points (Montgomery's trick down
-//                each lane's run of 8): 3 multiplications per point for the shared inverse instead of ~380.
+//   k_xyzz_to_affine  (toaffine.h) back to canonical affine with ONE Fermat inversion per run of 8 points
+//                (Montgomery's trick down each lane's run): 3 multiplications per point instead of ~380.
 // Two page-locked host slots and two device slots; chunk k + 1 is staged and copied while the kernels of chunk k
 // run, and the results of chunk k come back on a third stream under the kernels of chunk k + 1.
 //
@@ -23,12 +23,12 @@
 //   k_cc_final      six Miller loops, three final exponentiations, the report and the list.
 // The flag, fold and collect kernels, the halves of the final kernel and the staging are those of keycheck.h.
 #include "keycheck.h"
+#include "toaffine.h"
 
 namespace g16 {
 namespace {
 
 constexpr uint32_t CT_DEFAULT_CHUNK = 1u << 18;
-constexpr uint32_t CT_RUN = 8;  // points per lane of k_ct_affine: one inversion per CT_RUN points
 constexpr uint32_t CC_SLOT_BYTES_PER_POINT = 64 + 64 + 16;  // AFTER | BEFORE | rho
 
 // e = sum (pos_i - neg_i) 2^i, non-adjacent; top = index of the leading digit (always +1)
@@ -63,19 +63,6 @@ CtSched naf_of(const U256& e) {
   return s;
 }
 
-void wipe(void* p, size_t n) {
-  volatile uint8_t* v = (volatile uint8_t*)p;
-  while (n--) *v++ = 0;
-}
-
-bool fr_words_canonical(const Fr& a) {
-  for (int i = 7; i >= 0; --i) {
-    if (a.v[i] < FrParams::MOD[i]) return true;
-    if (a.v[i] > FrParams::MOD[i]) return false;
-  }
-  return false;
-}
-
 // ---- g16_key_contribute ------------------------------------------------------------------------------
 __global__ void __launch_bounds__(KC_BLOCK) k_ct_mul(const G1Affine* pts, uint32_t n, const CtSched* sched,
                                                      G1XYZZ* work) {
@@ -95,37 +82,6 @@ __global__ void __launch_bounds__(KC_BLOCK) k_ct_mul(const G1Affine* pts, uint32
     }
   }
   work[i] = acc;
-}
-
-// lane t of block g owns the points g * 64 * CT_RUN + j * 64 + t, j < CT_RUN (neighbouring lanes, neighbouring
-// points).  Prefix products of the ZZZ down the run (an infinite point counts as 1), one inversion, then back
-// up: 1/ZZZ_j = inv(prefix_j ZZZ_j) prefix_j.  1/ZZ = (ZZ / ZZZ)^2 as in XYZZ::to_affine.  The prefixes wait in
-// the x half of the output entry they belong to (written here, read back by the same lane): a register array
-// of CT_RUN field elements would be indexed by the loop counter and end up in scratch.
-__global__ void __launch_bounds__(KC_BLOCK) k_ct_affine(const G1XYZZ* work, uint32_t n, G1Affine* out) {
-  const uint32_t first = blockIdx.x * (KC_BLOCK * CT_RUN) + threadIdx.x;
-  Fq run = Fq::one();
-  uint32_t cnt = 0;
-#pragma unroll 1
-  for (uint32_t i = first; cnt < CT_RUN && i < n; ++cnt, i += KC_BLOCK) {
-    out[i].x = run;
-    const Fq z = work[i].zzz;
-    if (!z.is_zero()) run = run * z;
-  }
-  Fq inv = run.inv();
-#pragma unroll 1
-  for (; cnt > 0; --cnt) {
-    const uint32_t i = first + (cnt - 1) * KC_BLOCK;
-    const G1XYZZ P = work[i];
-    if (P.zzz.is_zero()) {
-      out[i] = G1Affine::infinity();
-      continue;
-    }
-    const Fq iz3 = inv * out[i].x;
-    inv = inv * P.zzz;
-    const Fq iz2 = (iz3 * P.zz).sqr();
-    out[i] = G1Affine{P.x * iz2, P.y * iz3};
-  }
 }
 
 // ---- g16_key_contribution_check ----------------------------------------------------------------------
@@ -246,24 +202,15 @@ extern "C" g16_status g16_key_contribute(int device, const g16_key_desc* key, co
   if (d) {
     memcpy(&sec.d, d, 32);
     if (!fr_words_canonical(sec.d) || sec.d.is_zero()) return G16_ERR_INVALID;
-  } else {  // uniform in [1, r): 254 random bits, rejected outside the range (r > 2^253: < 2 draws on average)
-    for (;;) {
-      if (!os_random(&sec.dc, 32)) return G16_ERR_INTERNAL;
-      sec.dc.v[7] &= 0x3fffffffu;
-      Fr c;
-      memcpy(&c, &sec.dc, 32);
-      const bool in_range = fr_words_canonical(c) && !c.is_zero();
-      wipe(&c, sizeof c);
-      if (in_range) break;
-    }
-    sec.d = Fr::from_canonical(sec.dc);
+  } else if (!FrPool().draw_fr(&sec.d, true)) {
+    return G16_ERR_INTERNAL;  // never a fixed fallback
   }
   sec.d_inv = sec.d.inv();
   sec.dc = sec.d.to_canonical();
   sec.ec = sec.d_inv.to_canonical();
   sec.sched = naf_of(sec.ec);
 
-  try {
+  return guarded_call([&]() -> g16_status {
     G1Affine d1;
     G2Affine d2;
     memcpy(&d1, key->delta_g1, 64);
@@ -318,8 +265,7 @@ extern "C" g16_status g16_key_contribute(int device, const g16_key_desc* key, co
       G16_HIP(hipStreamWaitEvent(comp.s, copied[s].e, 0));
       G16_LAUNCH(k_ct_mul, ceil_div(n, KC_BLOCK), KC_BLOCK, 0, comp.s, (const G1Affine*)dv, n,
                  (const CtSched*)dsched.p, dwork.p);
-      G16_LAUNCH(k_ct_affine, ceil_div(n, KC_BLOCK * CT_RUN), KC_BLOCK, 0, comp.s, (const G1XYZZ*)dwork.p, n,
-                 (G1Affine*)dv);
+      xyzz_to_affine<Fq>(dwork.p, n, (G1Affine*)dv, comp.s);
       G16_HIP(hipEventRecord(computed[s].e, comp.s));
       G16_HIP(hipStreamWaitEvent(down.s, computed[s].e, 0));
       G16_HIP(hipMemcpyAsync(pin[s].p, dv, bytes, hipMemcpyDeviceToHost, down.s));
@@ -332,11 +278,7 @@ extern "C" g16_status g16_key_contribute(int device, const g16_key_desc* key, co
     memcpy(delta_g1_out, &nd1, 64);
     memcpy(delta_g2_out, &nd2, 128);
     return G16_OK;
-  } catch (const HipError&) {
-    return G16_ERR_HIP;
-  } catch (const std::exception&) {
-    return G16_ERR_INTERNAL;
-  }
+  });
 }
 
 extern "C" g16_status g16_key_contribution_check(int device, const g16_key_desc* before, const g16_key_desc* after,
@@ -362,7 +304,7 @@ extern "C" g16_status g16_key_contribution_check(int device, const g16_key_desc*
        memcmp(before->b_g1_query, after->b_g1_query, N * 64) || memcmp(before->b_g2_query, after->b_g2_query, N * 128))
           ? 1
           : 0;
-  try {
+  return guarded_call([&]() -> g16_status {
     const uint32_t chunk = chunk_from_env("G16_CONTRIB_CHUNK", CT_DEFAULT_CHUNK, n_l > dom ? n_l : dom);
     const uint32_t nb_max = ceil_div(chunk, KC_BLOCK);
 
@@ -443,9 +385,5 @@ extern "C" g16_status g16_key_contribution_check(int device, const g16_key_desc*
                (const g16_key_bad_point*)stage.dlists.p, stage.cap, mismatch, stage.dout.p);
     stage.finish(hs.get(), dst.p, report, bad_out);
     return G16_OK;
-  } catch (const HipError&) {
-    return G16_ERR_HIP;
-  } catch (const std::exception&) {
-    return G16_ERR_INTERNAL;
-  }
+  });
 }

@@ -21,15 +21,10 @@
 #include "gt.h"
 
 namespace g16 {
-void set_create_error(const std::string& msg);  // api.hip: what g16_last_error(NULL) returns
-
 namespace {
 
 enum { T_UPLOAD = 0, T_G2, T_KERNEL, T_DOWNLOAD, T_COUNT };
-thread_local float t_gt_ms[T_COUNT];
-
-// in front of the event that opens a timed phase (srs_contribute.hip's k_sx_mark explains why)
-__global__ void k_gt_mark() {}
+thread_local PhaseTimes<T_COUNT> t_gt;
 
 // g1: 64-byte points, g2: 128-byte points, pair p of product i is point off[i] + p of both
 __global__ void __launch_bounds__(COOP_LANES) k_gt_products(const VkDev* vk, const uint8_t* g1, const uint8_t* g2,
@@ -139,31 +134,19 @@ __global__ void __launch_bounds__(GT_CODEC_BLOCK) k_gt_member(const F12* pw, F12
   for (int k = 0; k < 12; ++k) flat[i].c[k] = Fq::zero();
 }
 
-struct TimedEvent {
-  hipEvent_t e = nullptr;
-  bool made = false;
-  ~TimedEvent() {
-    if (made) (void)hipEventDestroy(e);
-  }
-  void create() {
-    G16_HIP(hipEventCreate(&e));
-    made = true;
-  }
-};
-
 enum { E_UP0 = 0, E_UP1, E_G2A, E_G2B, E_K, E_DN, E_COUNT };
 
 // the two streams and the events of one call
 struct GtCall {
   StreamBox s1, s2;
-  TimedEvent ev[E_COUNT];
+  EventBox ev[E_COUNT];
   explicit GtCall(bool second) {
     s1.create();
     if (second) s2.create();
-    for (auto& e : ev) e.create();
+    for (auto& e : ev) e.create(true);
   }
   void open() {
-    G16_LAUNCH(k_gt_mark, 1, 1, 0, s1.s);
+    G16_LAUNCH(k_phase_mark<>, 1, 1, 0, s1.s);
     G16_HIP(hipEventRecord(ev[E_UP0].e, s1.s));
   }
   void mark(int which) { G16_HIP(hipEventRecord(ev[which].e, s1.s)); }
@@ -172,16 +155,9 @@ struct GtCall {
     G16_HIP(hipGetLastError());
     G16_HIP(hipStreamSynchronize(s1.s));
     if (g2) G16_HIP(hipStreamSynchronize(s2.s));
-    const int spans[4][3] = {{E_UP0, E_UP1, T_UPLOAD}, {E_G2A, E_G2B, T_G2}, {E_UP1, E_K, T_KERNEL}, {E_K, E_DN, T_DOWNLOAD}};
-    for (const auto& sp : spans) {
-      float t = 0.f;
-      if (sp[2] == T_G2 && !g2) {
-        t_gt_ms[T_G2] = 0.f;
-        continue;
-      }
-      if (hipEventElapsedTime(&t, ev[sp[0]].e, ev[sp[1]].e) != hipSuccess) t = 0.f;
-      t_gt_ms[sp[2]] = t;
-    }
+    t_gt.take(Stored::REPLACE, ev, {{E_UP0, E_UP1, T_UPLOAD}, {E_UP1, E_K, T_KERNEL}, {E_K, E_DN, T_DOWNLOAD}});
+    if (g2) t_gt.take(Stored::REPLACE, ev, {{E_G2A, E_G2B, T_G2}});
+    else t_gt.ms[T_G2] = 0.f;  // no G2 work in this call
   }
 };
 
@@ -192,14 +168,6 @@ void upload_consts(DevBuf<VkDev>& dvk, hipStream_t s, std::unique_ptr<VkDev>& hv
   hv->ml_alpha_beta = f12_one();
   dvk.alloc(1);
   G16_HIP(hipMemcpyAsync(dvk.p, hv.get(), sizeof(VkDev), hipMemcpyHostToDevice, s));
-}
-
-bool scalar_below_r(const uint64_t* s) {
-  for (int k = 3; k >= 0; --k) {
-    const uint64_t m = (uint64_t)FrParams::MOD[2 * k] | ((uint64_t)FrParams::MOD[2 * k + 1] << 32);
-    if (s[k] != m) return s[k] < m;
-  }
-  return false;
 }
 
 // offsets[0 .. n]: non-decreasing from 0, each group at most `most` long (0: any length); names the group on failure
@@ -222,20 +190,6 @@ bool offsets_ok(const char* fn, const uint32_t* off, uint32_t n, uint32_t most) 
   return true;
 }
 
-template <class F>
-g16_status guarded(F&& body) {
-  try {
-    body();
-    return G16_OK;
-  } catch (const HipError& e) {
-    set_create_error(e.what());
-    return G16_ERR_HIP;
-  } catch (const std::exception& e) {
-    set_create_error(e.what());
-    return G16_ERR_INTERNAL;
-  }
-}
-
 }  // namespace
 }  // namespace g16
 
@@ -249,7 +203,7 @@ extern "C" g16_status g16_pairing_products(int device, const uint8_t* g1, const 
   const uint32_t total = offsets[n];
   if (total && (!g1 || !g2)) return G16_ERR_INVALID;
   if (const g16_status ds = device_ok(device)) return ds;
-  return guarded([&] {
+  return guarded_call([&] {
     G16_HIP(hipSetDevice(device));
     uint64_t k_lo, k_hi;
     six_x_squared(&k_lo, &k_hi);
@@ -276,7 +230,7 @@ extern "C" g16_status g16_pairing_products(int device, const uint8_t* g1, const 
     G16_HIP(hipMemcpyAsync(doff.p, offsets, doff.bytes(), hipMemcpyHostToDevice, s1));
     c.mark(E_UP1);
     G16_HIP(hipStreamWaitEvent(s2, c.ev[E_UP1].e, 0));
-    G16_LAUNCH(k_gt_mark, 1, 1, 0, s2);
+    G16_LAUNCH(k_phase_mark<>, 1, 1, 0, s2);
     G16_HIP(hipEventRecord(c.ev[E_G2A].e, s2));
     if (total)
       G16_LAUNCH(k_vp_g2, ceil_div(total, COOP_LANES), COOP_LANES, 0, s2, (const VkDev*)dvk.p, (const uint8_t*)d2.p, 128u,
@@ -303,12 +257,12 @@ extern "C" g16_status g16_gt_multiexp(int device, const uint8_t* gt, const uint6
   const uint32_t total = offsets[n];
   if (total && (!gt || !scalars)) return G16_ERR_INVALID;
   for (uint32_t j = 0; j < total; ++j)
-    if (!scalar_below_r(scalars + 4 * (size_t)j)) {
+    if (!fr_words_canonical(scalars + 4 * (size_t)j)) {
       set_create_error("g16_gt_multiexp: scalar " + std::to_string(j) + " is not below r");
       return G16_ERR_INVALID;
     }
   if (const g16_status ds = device_ok(device)) return ds;
-  return guarded([&] {
+  return guarded_call([&] {
     G16_HIP(hipSetDevice(device));
     DevBuf<F12> dg, dout;
     DevBuf<uint64_t> ds;
@@ -339,7 +293,7 @@ extern "C" g16_status g16_gt_to_ark(int device, const uint8_t* gt, uint32_t n, u
   if (!n) return G16_OK;
   if (!gt || !out || n > 0xffffffffu / GT_BYTES) return G16_ERR_INVALID;
   if (const g16_status ds = device_ok(device)) return ds;
-  return guarded([&] {
+  return guarded_call([&] {
     G16_HIP(hipSetDevice(device));
     DevBuf<F12> dflat;
     DevBuf<uint8_t> dtower;
@@ -363,7 +317,7 @@ extern "C" g16_status g16_gt_from_ark(int device, const uint8_t* in, uint32_t n,
   if (!n) return G16_OK;
   if (!in || !gt_out || n > 0xffffffffu / GT_BYTES) return G16_ERR_INVALID;
   if (const g16_status ds = device_ok(device)) return ds;
-  return guarded([&] {
+  return guarded_call([&] {
     G16_HIP(hipSetDevice(device));
     DevBuf<F12> dflat, dpow;
     DevBuf<uint8_t> dtower, dreason;
@@ -400,7 +354,5 @@ extern "C" g16_status g16_gt_from_ark(int device, const uint8_t* in, uint32_t n,
 }
 
 extern "C" g16_status g16_gt_times(float* ms, uint32_t cap) {
-  if (!ms) return G16_ERR_INVALID;
-  for (uint32_t i = 0; i < cap; ++i) ms[i] = i < (uint32_t)T_COUNT ? t_gt_ms[i] : 0.f;
-  return G16_OK;
+  return t_gt.read(ms, cap);
 }

@@ -12,10 +12,8 @@
 //   k_affine      XYZZ -> canonical affine, one Fermat inversion per SS_RUN points (Montgomery's trick), with the
 //                 bit reversal of the transform's output folded into the store
 #pragma once
-#include <chrono>
-
-#include "../../include/g16_amd.h"
 #include "ec29.h"
+#include "hostcall.h"
 #include "keygen.h"
 #include "ntt.h"
 
@@ -161,19 +159,6 @@ __global__ void __launch_bounds__(SS_BLOCK) k_affine(const XYZZ29<typename Lazy<
     }
   }
 }
-
-struct PhaseClock {
-  float* ms;
-  hipStream_t s;
-  std::chrono::steady_clock::time_point t0;
-  PhaseClock(float* m, hipStream_t st) : ms(m), s(st), t0(std::chrono::steady_clock::now()) {}
-  void lap(int phase) {
-    G16_HIP(hipStreamSynchronize(s));
-    const auto t1 = std::chrono::steady_clock::now();
-    ms[phase] += std::chrono::duration<float, std::milli>(t1 - t0).count();
-    t0 = t1;
-  }
-};
 
 struct Twiddles {  // of one transform size n = 2^k
   DevBuf<Naf> tw, tw_scaled, top, h;  // omega_n^-e | omega_n^-e / n, e < n/2 | 1/n | omega_2n^-j / (2n), j < n

@@ -9,17 +9,14 @@
 //            small-exponent tests, and the halves every final kernel shares: chk_offsets, chk_pairs, chk_counts,
 //            chk_emit_lists.  What is left to a check is its table of pairs and its own relation bits.
 //   host     CheckStage, the streamed staging of one call (two page-locked host slots, two device slots, the copy
-//            of chunk k + 1 under the kernels of chunk k, one synchronisation before the download), and the small
-//            helpers every entry point starts with: device_ok, rho_all_nonzero, chunk_from_env, draw_rho, vk_consts.
-// The RAII boxes also serve the pipelines with a download leg (g16_key_contribute, srs_contribute.hip, arkser.hip).
+//            of chunk k + 1 under the kernels of chunk k, one synchronisation before the download), rho_all_nonzero
+//            and vk_consts.  The RAII boxes, device_ok and chunk_from_env are hostcall.h's, draw_rho is secret.h's.
 #pragma once
-#include <stdlib.h>
-
 #include <memory>
 
-#include "../../include/g16_amd.h"
-
+#include "hostcall.h"
 #include "pairing.h"
+#include "secret.h"
 
 namespace g16 {
 
@@ -264,68 +261,12 @@ __global__ void __launch_bounds__(KC_SCAN) k_chk_collect(const uint8_t* flags, u
 }  // namespace
 
 // ---- host side -------------------------------------------------------------------------------------
-struct PinnedBuf {
-  uint8_t* p = nullptr;
-  ~PinnedBuf() {
-    if (p) (void)hipHostFree(p);
-  }
-  void alloc(size_t bytes) { G16_HIP(hipHostMalloc((void**)&p, bytes, hipHostMallocPortable)); }
-};
-struct StreamBox {
-  hipStream_t s = nullptr;
-  bool made = false;
-  ~StreamBox() {
-    if (made) (void)hipStreamDestroy(s);
-  }
-  void create() {
-    G16_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    made = true;
-  }
-};
-struct EventBox {
-  hipEvent_t e = nullptr;
-  bool made = false;
-  ~EventBox() {
-    if (made) (void)hipEventDestroy(e);
-  }
-  void create() {
-    G16_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    made = true;
-  }
-};
-
-// G16_OK, or what an entry point returns for this device number
-inline g16_status device_ok(int device) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return G16_ERR_NO_DEVICE;
-  return device < 0 || device >= ndev ? G16_ERR_INVALID : G16_OK;
-}
-
 // a caller's n coefficients of 2 x u64 (NULL: the library draws them)
 inline bool rho_all_nonzero(const uint64_t* rho, uint64_t n) {
   if (rho)
     for (uint64_t i = 0; i < n; ++i)
       if (!(rho[2 * i] | rho[2 * i + 1])) return false;
   return true;
-}
-
-// <name>=<points> (tests): points per staged chunk; never more than the longest array needs
-inline uint32_t chunk_from_env(const char* name, uint32_t dflt, uint64_t longest) {
-  uint32_t chunk = dflt;
-  if (const char* e = getenv(name)) {
-    const unsigned long long v = strtoull(e, nullptr, 0);
-    if (v >= 1 && v <= (1ull << 24)) chunk = (uint32_t)v;
-  }
-  if (longest < 1) longest = 1;
-  return chunk > longest ? (uint32_t)longest : chunk;
-}
-
-// n nonzero 128-bit coefficients from the OS, straight into hr; false: the OS gave none (never a fixed fallback)
-inline bool draw_rho(uint64_t* hr, size_t n) {
-  bool drawn = os_random(hr, n * 16);
-  for (size_t i = 0; drawn && i < n; ++i)
-    while (drawn && !(hr[2 * i] | hr[2 * i + 1])) drawn = os_random(&hr[2 * i], 16);  // probability 2^-128 per entry
-  return drawn;
 }
 
 // the curve and Frobenius constants of a VkDev; the key's own fields are the caller's

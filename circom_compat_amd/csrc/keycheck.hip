@@ -148,7 +148,7 @@ extern "C" g16_status g16_key_check(int device, const g16_key_desc* key, const g
   if (vk && (!vk->ic || vk->ic_count < 1)) return G16_ERR_INVALID;
   if (!rho_all_nonzero(rho, N)) return G16_ERR_INVALID;
   if (const g16_status ds = device_ok(device)) return ds;
-  try {
+  return guarded_call([&]() -> g16_status {
     uint64_t longest = N > dom ? N : dom;
     if (vk && vk->ic_count > longest) longest = vk->ic_count;
     if (longest < 3) longest = 3;  // the single points
@@ -258,9 +258,5 @@ extern "C" g16_status g16_key_check(int device, const g16_key_desc* key, const g
                (const g16_key_bad_point*)stage.dlists.p, stage.cap, vk_mismatch, stage.dout.p);
     stage.finish(hs.get(), dst.p, report, bad_out);
     return G16_OK;
-  } catch (const HipError&) {
-    return G16_ERR_HIP;
-  } catch (const std::exception&) {
-    return G16_ERR_INTERNAL;
-  }
+  });
 }

@@ -16,6 +16,7 @@
 #include "msm.h"
 #include "ntt.h"
 #include "witness_map.h"
+#include "hostcall.h"
 #include "keygen.h"
 
 using namespace g16;
@@ -204,8 +205,7 @@ g16_status g16_setup_create_ex(int device, const g16_csr* at, const g16_csr* bt,
     t_setup_err = why;
     return G16_ERR_INVALID;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return G16_ERR_NO_DEVICE;
+  if (device_ok(0) != G16_OK) return G16_ERR_NO_DEVICE;  // a bad ordinal is hipSetDevice's to refuse, as G16_ERR_HIP
   g16_setup* S = new g16_setup();
   try {
     G16_HIP(hipSetDevice(device));

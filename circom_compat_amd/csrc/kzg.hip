@@ -31,26 +31,19 @@ struct g16_kzg_key {
 namespace {
 
 enum { T_IN = 0, T_MID, T_MSM, T_OUT, T_COUNT };
-thread_local float t_phase_ms[T_COUNT] = {0.f, 0.f, 0.f, 0.f};
+thread_local PhaseTimes<T_COUNT> t_phase;
 
 // T_COUNT + 1 marks on stream s; collect() adds the intervals to the thread's phase times
 struct Marks {
-  hipEvent_t e[T_COUNT + 1] = {};
+  EventBox e[T_COUNT + 1];
   hipStream_t s;
   explicit Marks(hipStream_t stream) : s(stream) {
-    for (auto& x : e) G16_HIP(hipEventCreate(&x));
+    for (auto& x : e) x.create(true);
   }
-  ~Marks() {
-    for (auto x : e)
-      if (x) (void)hipEventDestroy(x);
-  }
-  void mark(int i) { G16_HIP(hipEventRecord(e[i], s)); }
+  void mark(int i) { G16_HIP(hipEventRecord(e[i].e, s)); }
   void collect() {
-    G16_HIP(hipEventSynchronize(e[T_COUNT]));
-    for (int i = 0; i < T_COUNT; ++i) {
-      float t = 0.f;
-      if (hipEventElapsedTime(&t, e[i], e[i + 1]) == hipSuccess) t_phase_ms[i] += t;
-    }
+    G16_HIP(hipEventSynchronize(e[T_COUNT].e));
+    t_phase.take(Stored::ADD, e, {{0, 1, T_IN}, {1, 2, T_MID}, {2, 3, T_MSM}, {3, 4, T_OUT}});
   }
 };
 
@@ -123,7 +116,7 @@ extern "C" g16_status g16_kzg_key_create(int device, const g16_srs_desc* srs, si
   std::unique_ptr<g16_kzg_key> k(new g16_kzg_key);
   const g16_status st = g16_msm_bases_create(device, G16_GROUP_G1, srs->tau_g1, max_len, 0, &o, &k->bases);
   if (st != G16_OK) return st;
-  try {
+  const g16_status made = guarded_call([&] {
     memcpy(k->tau_g2, srs->tau_g2 + 128, 128);
     k->max_len = (uint32_t)max_len;
     const size_t b = k->bases->batch;
@@ -133,11 +126,8 @@ extern "C" g16_status g16_kzg_key_create(int device, const g16_srs_desc* srs, si
     k->rem.alloc(b);
     k->bad.alloc(2);
     k->ws.reserve(max_len, b);
-  } catch (const HipError& e) {
-    return kz_fail(G16_ERR_HIP, e.what());
-  } catch (const std::exception& e) {
-    return kz_fail(G16_ERR_INTERNAL, e.what());
-  }
+  }, kz_fail);
+  if (made != G16_OK) return made;
   *out = k.release();
   return G16_OK;
 }
@@ -173,10 +163,10 @@ extern "C" g16_status g16_kzg_open(g16_kzg_key* k, const void* coeffs, size_t le
   const bool canon = (flags & G16_MSM_SCALARS_CANONICAL) != 0, on_dev = (flags & G16_MSM_SCALARS_DEVICE) != 0;
   g16_msm_bases* h = k->bases;
   std::lock_guard<std::mutex> lock(h->mu);
-  try {
+  return guarded_call([&]() -> g16_status {
     G16_HIP(hipSetDevice(h->device));
     hipStream_t s = h->stream;
-    for (float& t : t_phase_ms) t = 0.f;
+    t_phase.clear();
     Marks ev(s);
     const Fr* in = (const Fr*)coeffs;
     const Fr* zin = (const Fr*)z;
@@ -220,11 +210,7 @@ extern "C" g16_status g16_kzg_open(g16_kzg_key* k, const void* coeffs, size_t le
         return kz_fail(G16_ERR_INVALID, "g16_kzg_open: point " + std::to_string(k0 + bad[1]) + " is >= the field modulus");
     }
     return G16_OK;
-  } catch (const HipError& e) {
-    return kz_fail(G16_ERR_HIP, e.what());
-  } catch (const std::exception& e) {
-    return kz_fail(G16_ERR_INTERNAL, e.what());
-  }
+  }, kz_fail);
 }
 
 extern "C" g16_status g16_kzg_verify(int device, const uint8_t tau_g2[128], const uint8_t* commitments, const uint64_t* z,
@@ -240,9 +226,9 @@ extern "C" g16_status g16_kzg_verify(int device, const uint8_t tau_g2[128], cons
   if (n >= ((size_t)1 << 26)) return kz_fail(G16_ERR_INVALID, "g16_kzg_verify: 2^26 openings or more");
   if (!rho_all_nonzero(rho, n)) return kz_fail(G16_ERR_INVALID, "g16_kzg_verify: a rho entry is zero");
   if (const g16_status ds = device_ok(device)) return kz_fail(ds, "g16_kzg_verify: no usable device (there is no CPU fallback)");
-  try {
+  return guarded_call([&]() -> g16_status {
     G16_HIP(hipSetDevice(device));
-    for (float& t : t_phase_ms) t = 0.f;
+    t_phase.clear();
     Marks ev(nullptr);
     const uint32_t nn = (uint32_t)n;
     // rho as canonical 32-byte integers: the conversion kernel of g16_fr_convert makes them Montgomery
@@ -313,15 +299,9 @@ extern "C" g16_status g16_kzg_verify(int device, const uint8_t tau_g2[128], cons
     ev.collect();
     *ok_out = ok;
     return G16_OK;
-  } catch (const HipError& e) {
-    return kz_fail(G16_ERR_HIP, e.what());
-  } catch (const std::exception& e) {
-    return kz_fail(G16_ERR_INTERNAL, e.what());
-  }
+  }, kz_fail);
 }
 
 extern "C" g16_status g16_kzg_times(float* ms, uint32_t cap) {
-  if (!ms) return G16_ERR_INVALID;
-  for (uint32_t i = 0; i < cap; ++i) ms[i] = i < (uint32_t)T_COUNT ? t_phase_ms[i] : 0.f;
-  return G16_OK;
+  return t_phase.read(ms, cap);
 }

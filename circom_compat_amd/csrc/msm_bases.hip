@@ -233,7 +233,7 @@ extern "C" g16_status g16_msm(g16_msm_bases* h, const void* scalars, size_t len,
   }
   const bool canon = (flags & G16_MSM_SCALARS_CANONICAL) != 0, on_dev = (flags & G16_MSM_SCALARS_DEVICE) != 0;
   std::lock_guard<std::mutex> lock(h->mu);
-  try {
+  return guarded_call([&]() -> g16_status {
     G16_HIP(hipSetDevice(h->device));
     hipStream_t s = h->stream;
     const Fr* in = (const Fr*)scalars;
@@ -264,11 +264,7 @@ extern "C" g16_status g16_msm(g16_msm_bases* h, const void* scalars, size_t len,
       }
     }
     return G16_OK;
-  } catch (const HipError& e) {
-    return mb_fail(G16_ERR_HIP, e.what());
-  } catch (const std::exception& e) {
-    return mb_fail(G16_ERR_INTERNAL, e.what());
-  }
+  }, mb_fail);
 }
 
 extern "C" g16_status g16_msm_once(int device, int group, const void* points, const void* scalars, size_t n,

@@ -1,12 +1,10 @@
 // pairing.h -- the optimal-ate pairing pieces shared by verify.hip (proof verification) and
 // keycheck.hip (proving-key validation): Fq12 in the polynomial basis, the Miller loop over affine
-// twist points, the final exponentiation, the structural predicates of a deserialised point, the
-// host-computed Frobenius constants and the operating-system randomness helper.  The formulation
-// and its provenance are described at the top of verify.hip.
+// twist points, the final exponentiation, the structural predicates of a deserialised point and the
+// host-computed Frobenius constants.  The formulation and its provenance are described at the top of
+// verify.hip.
 #pragma once
-#include <errno.h>
 #include <string.h>
-#include <sys/random.h>
 
 #include <mutex>
 
@@ -336,26 +334,6 @@ inline const HostConsts& host_consts() {
     }
   });
   return H;
-}
-
-// operating-system CSPRNG; false when neither source delivers (never a fixed fallback)
-inline bool os_random(void* buf, size_t len) {
-  uint8_t* p = (uint8_t*)buf;
-  while (len) {
-    const ssize_t r = getrandom(p, len, 0);
-    if (r < 0) {
-      if (errno == EINTR) continue;
-      break;
-    }
-    p += r;
-    len -= (size_t)r;
-  }
-  if (!len) return true;
-  FILE* f = fopen("/dev/urandom", "rb");
-  if (!f) return false;
-  const size_t got = fread(p, 1, len, f);
-  fclose(f);
-  return got == len;
 }
 
 }  // namespace g16

@@ -26,11 +26,10 @@
 #include <algorithm>
 
 #include "field29.h"
+#include "hostcall.h"
 #include "wtns_ingest.h"
 
 namespace g16 {
-void set_create_error(const std::string& msg);  // api.hip: what g16_last_error(NULL) returns
-
 namespace {
 
 constexpr int PD_L = f29::N;
@@ -229,11 +228,10 @@ extern "C" g16_status g16_poly_divide_linear(int device, const void* coeffs, siz
   if (n < 1 || n > PD_MAX_N) return pd_fail(G16_ERR_INVALID, "g16_poly_divide_linear: n must be 1 .. 2^27");
   if (count > 65535) return pd_fail(G16_ERR_INVALID, "g16_poly_divide_linear: more than 65535 polynomials");
   if (!coeffs || !z || !rem_out || (n > 1 && !quot_out)) return pd_fail(G16_ERR_INVALID, "g16_poly_divide_linear: null argument");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return G16_ERR_NO_DEVICE;
-  if (device < 0 || device >= ndev) return pd_fail(G16_ERR_INVALID, "g16_poly_divide_linear: device out of range");
+  if (const g16_status ds = device_ok(device))
+    return ds == G16_ERR_INVALID ? pd_fail(ds, "g16_poly_divide_linear: device out of range") : ds;
   const bool canon = (flags & G16_MSM_SCALARS_CANONICAL) != 0, on_dev = (flags & G16_MSM_SCALARS_DEVICE) != 0;
-  try {
+  return guarded_call([&]() -> g16_status {
     G16_HIP(hipSetDevice(device));
     const size_t total = n * count, qn = (n - 1) * count;
     DevBuf<Fr> din, dq, dz, drem;
@@ -269,9 +267,5 @@ extern "C" g16_status g16_poly_divide_linear(int device, const void* coeffs, siz
     if (!on_dev && qn) G16_HIP(hipMemcpy(quot_out, dq.p, qn * sizeof(Fr), hipMemcpyDeviceToHost));
     G16_HIP(hipMemcpy(rem_out, drem.p, count * sizeof(Fr), hipMemcpyDeviceToHost));
     return G16_OK;
-  } catch (const HipError& e) {
-    return pd_fail(G16_ERR_HIP, e.what());
-  } catch (const std::exception& e) {
-    return pd_fail(G16_ERR_INTERNAL, e.what());
-  }
+  }, pd_fail);
 }

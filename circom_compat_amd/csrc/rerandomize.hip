@@ -17,37 +17,24 @@
 //                 doublings of two ladders.  B lives in the lane's registers; delta is the same for every lane of a
 //                 block (a block never spans two groups) and is read through a block-uniform pointer, so it sits in
 //                 scalar registers, not in the lane's.
-//   k_rr_affine<F> back to canonical affine with one inversion per RR_RUN points (k_sx_affine's scheme), written
-//                 straight into the 256-byte output records.
+//   k_xyzz_to_affine<F>  (toaffine.h) back to canonical affine with one inversion per run of 8 points, written
+//                 straight into the 256-byte output records: A and C of record i are points i and n + i of one array.
 // XYZZ::madd handles equal, opposite and infinite operands, so B = +-delta, C = +-A and points at infinity (all
 // reachable from untrusted input) take the doubling / cancelling branches and need nothing of their own here.
 // The G1 kernels and the G2 kernels run on two streams: a small batch pays the G2 ladder's latency once.
 #include <stdlib.h>
 
 #include "keycheck.h"
+#include "toaffine.h"
 
 namespace g16 {
 namespace {
 
-constexpr uint32_t RR_RUN = 8;  // points per lane of k_rr_affine: one inversion per RR_RUN points
 constexpr uint32_t RR_REC = G16_PROOF_BYTES;
 constexpr uint32_t RR_OFF_B = 64, RR_OFF_C = 192;
 
 enum { T_UPLOAD = 0, T_PREPARE, T_MUL_G1, T_MUL_G2, T_AFFINE, T_DOWNLOAD, T_COUNT };
-thread_local float t_phase_ms[T_COUNT];
-
-void wipe(void* p, size_t n) {
-  volatile uint8_t* v = (volatile uint8_t*)p;
-  while (n--) *v++ = 0;
-}
-
-bool fr_words_canonical(const Fr& a) {
-  for (int i = 7; i >= 0; --i) {
-    if (a.v[i] < FrParams::MOD[i]) return true;
-    if (a.v[i] > FrParams::MOD[i]) return false;
-  }
-  return false;
-}
+thread_local PhaseTimes<T_COUNT> t_phase;
 
 // one block of the ladder kernels: `count` <= KC_BLOCK consecutive proofs from `first`, all under key `key`
 struct Tile {
@@ -141,88 +128,12 @@ __global__ void __launch_bounds__(KC_BLOCK) k_rr_g2(const uint8_t* recs, const u
   work[i] = acc;
 }
 
-// Point j of `total` goes to record j % n, at byte `off0` for j < n and `off1` from there on.  Lane t of block g owns
-// the points g * 64 * RR_RUN + k * 64 + t, k < RR_RUN; prefix products of the ZZZ down the run (an infinite point
-// counts as 1), one inversion, then back up.  The prefixes wait in the x half of the output entry they belong to.
-template <class F>
-__global__ void __launch_bounds__(KC_BLOCK) k_rr_affine(const XYZZ<F>* work, uint32_t total, uint32_t n, uint32_t off0,
-                                                         uint32_t off1, uint8_t* recs_out) {
-  const uint32_t first = blockIdx.x * (KC_BLOCK * RR_RUN) + threadIdx.x;
-  auto slot = [&](uint32_t j) -> Affine<F>* {
-    const bool hi = j >= n;
-    return (Affine<F>*)(recs_out + (size_t)(hi ? j - n : j) * RR_REC + (hi ? off1 : off0));
-  };
-  F run = F::one();
-  uint32_t cnt = 0;
-#pragma unroll 1
-  for (uint32_t j = first; cnt < RR_RUN && j < total; ++cnt, j += KC_BLOCK) {
-    slot(j)->x = run;
-    const F z = work[j].zzz;
-    if (!z.is_zero()) run = run * z;
-  }
-  F inv = run.inv();
-#pragma unroll 1
-  for (; cnt > 0; --cnt) {
-    const uint32_t j = first + (cnt - 1) * KC_BLOCK;
-    const XYZZ<F> P = work[j];
-    Affine<F>* o = slot(j);
-    if (P.zzz.is_zero()) {
-      *o = Affine<F>::infinity();
-      continue;
-    }
-    const F iz3 = inv * o->x;
-    inv = inv * P.zzz;
-    const F iz2 = (iz3 * P.zz).sqr();
-    *o = Affine<F>{P.x * iz2, P.y * iz3};
-  }
-}
-
-// in front of the event that opens a timed phase (srs_contribute.hip's k_sx_mark explains why)
-__global__ void k_rr_mark() {}
-
-struct TimedEvent {
-  hipEvent_t e = nullptr;
-  bool made = false;
-  ~TimedEvent() {
-    if (made) (void)hipEventDestroy(e);
-  }
-  void create() {
-    G16_HIP(hipEventCreate(&e));
-    made = true;
-  }
-};
-
 // the (r1, r2) of the call on the host, and the pool the drawn ones come from: wiped on every way out
 struct Secret {
-  static constexpr size_t POOL = 1024;  // candidates per request to the operating system: one request per scalar
-                                        // would be 2 n system calls
   std::vector<Fr> rs;
-  U256 pool[POOL];
-  size_t left = 0;
-  U256 tmp;
+  FrPool pool;
   ~Secret() {
     if (!rs.empty()) wipe(rs.data(), rs.size() * sizeof(Fr));
-    wipe(pool, sizeof pool);
-    wipe(&tmp, sizeof tmp);
-  }
-  // uniform in [lowest, r): 254 random bits, rejected outside the range
-  bool draw(Fr* out, bool nonzero) {
-    for (;;) {
-      if (!left) {
-        if (!os_random(pool, sizeof pool)) return false;
-        left = POOL;
-      }
-      tmp = pool[--left];
-      wipe(&pool[left], sizeof(U256));
-      tmp.v[7] &= 0x3fffffffu;
-      Fr c;
-      memcpy(&c, &tmp, 32);
-      const bool in_range = fr_words_canonical(c) && !(nonzero && c.is_zero());
-      wipe(&c, sizeof c);
-      if (in_range) break;
-    }
-    *out = Fr::from_canonical(tmp);
-    return true;
   }
 };
 
@@ -247,15 +158,13 @@ g16_status rerandomize(int device, const uint8_t* deltas, const uint32_t* counts
           !fr_words_canonical(sec.rs[2 * (size_t)i + 1]))
         return G16_ERR_INVALID;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return G16_ERR_NO_DEVICE;
-  if (device < 0 || device >= ndev) return G16_ERR_INVALID;
+  if (const g16_status ds = device_ok(device)) return ds;
   if (!scalars)
     for (uint32_t i = 0; i < n; ++i)
-      if (!(sec.draw(&sec.rs[2 * (size_t)i], true) && sec.draw(&sec.rs[2 * (size_t)i + 1], false)))
+      if (!(sec.pool.draw_fr(&sec.rs[2 * (size_t)i], true) && sec.pool.draw_fr(&sec.rs[2 * (size_t)i + 1], false)))
         return G16_ERR_INTERNAL;  // never a fixed fallback
 
-  try {
+  return guarded_call([&]() -> g16_status {
     // a block of the G2 ladder never spans two groups: its delta is block-uniform
     std::vector<Tile> tiles;
     tiles.reserve((size_t)n / KC_BLOCK + n_keys);
@@ -281,7 +190,7 @@ g16_status rerandomize(int device, const uint8_t* deltas, const uint32_t* counts
     DevBuf<G1XYZZ> dw1;
     DevBuf<G2XYZZ> dw2;
     StreamBox s1, s2;
-    TimedEvent ev[E_COUNT];
+    EventBox ev[E_COUNT];
     pin.alloc(bytes);
     din.alloc(bytes);
     dout.alloc(bytes);
@@ -294,10 +203,10 @@ g16_status rerandomize(int device, const uint8_t* deltas, const uint32_t* counts
     dw2.alloc(n);
     s1.create();
     s2.create();
-    for (auto& e : ev) e.create();
+    for (auto& e : ev) e.create(true);
 
     memcpy(pin.p, proofs, bytes);
-    G16_LAUNCH(k_rr_mark, 1, 1, 0, s1.s);
+    G16_LAUNCH(k_phase_mark<>, 1, 1, 0, s1.s);
     G16_HIP(hipEventRecord(ev[E_UP0].e, s1.s));
     G16_HIP(hipMemcpyAsync(din.p, pin.p, bytes, hipMemcpyHostToDevice, s1.s));
     G16_HIP(hipMemcpyAsync(ddelta.p, deltas, ddelta.bytes(), hipMemcpyHostToDevice, s1.s));
@@ -310,25 +219,23 @@ g16_status rerandomize(int device, const uint8_t* deltas, const uint32_t* counts
 
     // G2 on its own stream, beside the G1 work
     G16_HIP(hipStreamWaitEvent(s2.s, ev[E_PREP].e, 0));
-    G16_LAUNCH(k_rr_mark, 1, 1, 0, s2.s);
+    G16_LAUNCH(k_phase_mark<>, 1, 1, 0, s2.s);
     G16_HIP(hipEventRecord(ev[E_G2A].e, s2.s));
     G16_LAUNCH(k_rr_g2, (uint32_t)tiles.size(), KC_BLOCK, 0, s2.s, (const uint8_t*)din.p, (const uint8_t*)dok.p,
                (const U256*)dsc.p, n, (const Tile*)dtiles.p, (const G2Affine*)ddelta.p, dw2.p);
     G16_HIP(hipEventRecord(ev[E_G2B].e, s2.s));
-    G16_LAUNCH((k_rr_affine<Fq2>), ceil_div(n, KC_BLOCK * RR_RUN), KC_BLOCK, 0, s2.s, (const G2XYZZ*)dw2.p, n, n,
-               RR_OFF_B, RR_OFF_B, dout.p);
+    xyzz_to_affine<Fq2>(dw2.p, n, n, RR_OFF_B, RR_OFF_B, RR_REC, dout.p, s2.s);
     G16_HIP(hipEventRecord(ev[E_G2C].e, s2.s));
 
     G16_HIP(hipEventRecord(ev[E_G1A].e, s1.s));
     G16_LAUNCH(k_rr_g1, dim3(ceil_div(n, KC_BLOCK), 2), KC_BLOCK, 0, s1.s, (const uint8_t*)din.p,
                (const uint8_t*)dok.p, (const U256*)dsc.p, n, dw1.p);
     G16_HIP(hipEventRecord(ev[E_G1B].e, s1.s));
-    G16_LAUNCH((k_rr_affine<Fq>), ceil_div(2 * (uint64_t)n, KC_BLOCK * RR_RUN), KC_BLOCK, 0, s1.s,
-               (const G1XYZZ*)dw1.p, 2 * n, n, 0u, RR_OFF_C, dout.p);
+    xyzz_to_affine<Fq>(dw1.p, 2 * n, n, 0u, RR_OFF_C, RR_REC, dout.p, s1.s);
     G16_HIP(hipEventRecord(ev[E_G1C].e, s1.s));
 
     G16_HIP(hipStreamWaitEvent(s1.s, ev[E_G2C].e, 0));
-    G16_LAUNCH(k_rr_mark, 1, 1, 0, s1.s);
+    G16_LAUNCH(k_phase_mark<>, 1, 1, 0, s1.s);
     G16_HIP(hipEventRecord(ev[E_DN0].e, s1.s));
     G16_HIP(hipMemcpyAsync(pin.p, dout.p, bytes, hipMemcpyDeviceToHost, s1.s));
     G16_HIP(hipEventRecord(ev[E_DN1].e, s1.s));
@@ -345,21 +252,12 @@ g16_status rerandomize(int device, const uint8_t* deltas, const uint32_t* counts
     memcpy(proofs_out, pin.p, bytes);
     if (ok_out) memcpy(ok_out, ok.data(), n);
 
-    float ms[T_COUNT] = {0};
-    const int pairs[7][3] = {{E_UP0, E_UP1, T_UPLOAD}, {E_UP1, E_PREP, T_PREPARE}, {E_G1A, E_G1B, T_MUL_G1},
-                             {E_G2A, E_G2B, T_MUL_G2}, {E_G1B, E_G1C, T_AFFINE},   {E_G2B, E_G2C, T_AFFINE},
-                             {E_DN0, E_DN1, T_DOWNLOAD}};
-    for (const auto& p : pairs) {
-      float t = 0.f;
-      if (hipEventElapsedTime(&t, ev[p[0]].e, ev[p[1]].e) == hipSuccess) ms[p[2]] += t;
-    }
-    memcpy(t_phase_ms, ms, sizeof ms);
+    t_phase.take(Stored::REPLACE, ev,
+                 {{E_UP0, E_UP1, T_UPLOAD}, {E_UP1, E_PREP, T_PREPARE}, {E_G1A, E_G1B, T_MUL_G1},
+                  {E_G2A, E_G2B, T_MUL_G2}, {E_G1B, E_G1C, T_AFFINE},   {E_G2B, E_G2C, T_AFFINE},
+                  {E_DN0, E_DN1, T_DOWNLOAD}});
     return G16_OK;
-  } catch (const HipError&) {
-    return G16_ERR_HIP;
-  } catch (const std::exception&) {
-    return G16_ERR_INTERNAL;
-  }
+  });
 }
 
 }  // namespace
@@ -380,7 +278,5 @@ extern "C" g16_status g16_proofs_rerandomize(int device, const uint8_t delta_g2[
 }
 
 extern "C" g16_status g16_proofs_rerandomize_times(float* ms, uint32_t cap) {
-  if (!ms) return G16_ERR_INVALID;
-  for (uint32_t i = 0; i < cap; ++i) ms[i] = i < (uint32_t)T_COUNT ? t_phase_ms[i] : 0.f;
-  return G16_OK;
+  return t_phase.read(ms, cap);
 }

@@ -16,6 +16,8 @@
 //                 one block per long row over its partial sums.  Coefficient 1 / r-1 is one mixed addition /
 //                 subtraction, anything else a double-and-add from the top bit of min(c, r - c).
 // g16_srs_create mints an SRS from a known trapdoor with keygen.hip's k_powers / k_fb_mul (tests, synthetic keys).
+#include <memory>
+
 #include "gtransform.h"
 
 struct g16_srs {
@@ -184,7 +186,7 @@ __global__ void __launch_bounds__(SS_BLOCK) k_comb_fold(const CombLong* rows, co
 // ---- host side ---------------------------------------------------------------------------------------
 enum { T_UPLOAD = 0, T_NTT_G1, T_NTT_G2, T_H, T_AFFINE, T_COMB, T_DOWNLOAD, T_COUNT };
 
-thread_local float t_phase_ms[T_COUNT];
+thread_local PhaseTimes<T_COUNT> t_phase;
 
 struct DevCsr {
   DevBuf<uint32_t> rowptr, col;
@@ -272,11 +274,10 @@ g16_status g16_srs_create(int device, uint32_t log2_domain, const uint64_t* toxi
   if (!toxic || !out) return G16_ERR_INVALID;
   *out = nullptr;
   if (log2_domain > 27) return G16_ERR_DOMAIN_TOO_LARGE;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return G16_ERR_NO_DEVICE;
-  if (device < 0 || device >= ndev) return G16_ERR_INVALID;
-  g16_srs* S = new g16_srs();
-  try {
+  if (const g16_status ds = device_ok(device)) return ds;
+  std::unique_ptr<g16_srs> owned(new g16_srs());  // freed on every way out but the last
+  g16_srs* S = owned.get();
+  return guarded_call([&]() -> g16_status {
     G16_HIP(hipSetDevice(device));
     hipStream_t s = nullptr;
     const uint32_t n = 1u << log2_domain, n1 = 2 * n - 1;
@@ -309,15 +310,9 @@ g16_status g16_srs_create(int device, uint32_t log2_domain, const uint64_t* toxi
     G16_HIP(hipMemset(sc.p, 0, sc.bytes()));  // the powers of the trapdoor do not outlive the call
     S->n_tau_g1 = n1;
     S->n_tau = n;
-    *out = S;
+    *out = owned.release();
     return G16_OK;
-  } catch (const HipError&) {
-    delete S;
-    return G16_ERR_HIP;
-  } catch (const std::exception&) {
-    delete S;
-    return G16_ERR_INTERNAL;
-  }
+  });
 }
 
 g16_status g16_srs_desc_of(g16_srs* s, g16_srs_desc* out) {
@@ -370,15 +365,14 @@ static g16_status setup_impl(int device, const g16_csr* at, const g16_csr* bt, c
     if (!lag->tau_g1 || !lag->tau_g2 || !lag->alpha_tau_g1 || !lag->beta_tau_g1) return G16_ERR_INVALID;
   }
   if (setup_matrices_check(at, bt, ct, N, n_public, num_constraints)) return G16_ERR_INVALID;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return G16_ERR_NO_DEVICE;
-  if (device < 0 || device >= ndev) return G16_ERR_INVALID;
-  g16_setup* S = new g16_setup();
-  try {
+  if (const g16_status ds = device_ok(device)) return ds;
+  std::unique_ptr<g16_setup> owned(new g16_setup());  // freed on every way out but the last
+  g16_setup* S = owned.get();
+  return guarded_call([&]() -> g16_status {
     G16_HIP(hipSetDevice(device));
     hipStream_t s = nullptr;
-    memset(t_phase_ms, 0, sizeof t_phase_ms);
-    PhaseClock clk(t_phase_ms, s);
+    t_phase.clear();
+    PhaseClock clk(t_phase.ms, s);
     S->n_vars = N;
     S->n_public = n_public;
     S->domain = n;
@@ -525,23 +519,15 @@ static g16_status setup_impl(int device, const g16_csr* at, const g16_csr* bt, c
     memcpy(S->delta1, &g1, 64);
     memcpy(S->delta2, &g2, 128);
     memcpy(S->gamma2, &g2, 128);
-    *out = S;
+    *out = owned.release();
     return G16_OK;
-  } catch (const HipError&) {
-    delete S;
-    return G16_ERR_HIP;
-  } catch (const std::exception&) {
-    delete S;
-    return G16_ERR_INTERNAL;
-  }
+  });
 }
 
 extern "C" {
 
 g16_status g16_setup_from_srs_times(float* ms, uint32_t cap) {
-  if (!ms) return G16_ERR_INVALID;
-  for (uint32_t i = 0; i < cap; ++i) ms[i] = i < (uint32_t)T_COUNT ? t_phase_ms[i] : 0.f;
-  return G16_OK;
+  return t_phase.read(ms, cap);
 }
 
 }  // extern "C"

@@ -212,7 +212,7 @@ extern "C" g16_status g16_srs_check(int device, const g16_srs_desc* srs, const u
   const uint64_t n_rho = (n1 - 1) + 3 * (n2 - 1);
   if (!rho_all_nonzero(rho, n_rho)) return G16_ERR_INVALID;
   if (const g16_status ds = device_ok(device)) return ds;
-  try {
+  return guarded_call([&]() -> g16_status {
     const uint32_t chunk = chunk_from_env("G16_SRSCHECK_CHUNK", SC_DEFAULT_CHUNK, n1 > n2 ? n1 : n2);
     // G16_SRSCHECK_SLICED=1 (measurements): the shifted sums as two ladders in two blockIdx.y slices
     const char* sl = getenv("G16_SRSCHECK_SLICED");
@@ -333,9 +333,5 @@ extern "C" g16_status g16_srs_check(int device, const g16_srs_desc* srs, const u
                (const g16_key_bad_point*)stage.dlists.p, stage.cap, host_bits, stage.dout.p);
     stage.finish(hs.get(), dst.p, report, bad_out);
     return G16_OK;
-  } catch (const HipError&) {
-    return G16_ERR_HIP;
-  } catch (const std::exception&) {
-    return G16_ERR_INTERNAL;
-  }
+  });
 }

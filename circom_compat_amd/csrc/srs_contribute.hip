@@ -15,38 +15,24 @@
 //                 addition whenever ANY of its 64 lanes has a non-zero digit, which is almost every position.  The
 //                 scalar is read from memory one word per 32 positions: a register array indexed by the loop
 //                 counter would be scratch.  A lane at infinity, or above the leading bit of its scalar, idles.
-//   k_sx_affine<F> back to canonical affine with ONE inversion per SX_RUN points (Montgomery's trick down each
-//                 lane's run of 8) -- contribute.hip's k_ct_affine over either field; that file is left as it is.
+//   k_xyzz_to_affine<F>  (toaffine.h) back to canonical affine with ONE inversion per run of 8 points
+//                 (Montgomery's trick down each lane's run), in place of the chunk's input points.
 // Two page-locked host slots and two device slots; chunk k + 1 is staged and copied while the kernels of chunk k
 // run, and the results of chunk k come back on a third stream under the kernels of chunk k + 1.
 #include <stdlib.h>
 
 #include "keycheck.h"
 #include "ntt.h"
+#include "toaffine.h"
 
 namespace g16 {
 namespace {
 
 constexpr uint32_t SX_DEFAULT_CHUNK = 1u << 18;
-constexpr uint32_t SX_MAX_CHUNK = 1u << 24;
-constexpr int SX_POW_BITS = 24;  // t^(2^j), j < 24: a lane's index within a chunk is below SX_MAX_CHUNK
-constexpr uint32_t SX_RUN = 8;   // points per lane of k_sx_affine: one inversion per SX_RUN points
+constexpr int SX_POW_BITS = 24;  // t^(2^j), j < 24: a lane's index within a chunk is below 2^24 (chunk_from_env)
 
 enum { T_UPLOAD = 0, T_SCALARS, T_MUL_G1, T_MUL_G2, T_AFFINE, T_DOWNLOAD, T_COUNT };
-thread_local float t_phase_ms[T_COUNT];
-
-void wipe(void* p, size_t n) {
-  volatile uint8_t* v = (volatile uint8_t*)p;
-  while (n--) *v++ = 0;
-}
-
-bool fr_words_canonical(const Fr& a) {
-  for (int i = 7; i >= 0; --i) {
-    if (a.v[i] < FrParams::MOD[i]) return true;
-    if (a.v[i] > FrParams::MOD[i]) return false;
-  }
-  return false;
-}
+thread_local PhaseTimes<T_COUNT> t_phase;
 
 // out[i] = scale * t^i, canonical; tab[j] = t^(2^j)
 __global__ void __launch_bounds__(256) k_sx_scalars(const Fr* tab, const Fr* scale, uint32_t n, U256* out) {
@@ -78,59 +64,11 @@ __global__ void __launch_bounds__(KC_BLOCK) k_sx_mul(const Affine<F>* pts, const
   work[i] = acc;
 }
 
-// lane t of block g owns the points g * 64 * SX_RUN + j * 64 + t, j < SX_RUN.  Prefix products of the ZZZ down the
-// run (an infinite point counts as 1), one inversion, then back up: 1/ZZZ_j = inv(prefix_j ZZZ_j) prefix_j and
-// 1/ZZ = (ZZ / ZZZ)^2.  The prefixes wait in the x half of the output entry they belong to: a register array of
-// SX_RUN field elements would be indexed by the loop counter and end up in scratch.
-template <class F>
-__global__ void __launch_bounds__(KC_BLOCK) k_sx_affine(const XYZZ<F>* work, uint32_t n, Affine<F>* out) {
-  const uint32_t first = blockIdx.x * (KC_BLOCK * SX_RUN) + threadIdx.x;
-  F run = F::one();
-  uint32_t cnt = 0;
-#pragma unroll 1
-  for (uint32_t i = first; cnt < SX_RUN && i < n; ++cnt, i += KC_BLOCK) {
-    out[i].x = run;
-    const F z = work[i].zzz;
-    if (!z.is_zero()) run = run * z;
-  }
-  F inv = run.inv();
-#pragma unroll 1
-  for (; cnt > 0; --cnt) {
-    const uint32_t i = first + (cnt - 1) * KC_BLOCK;
-    const XYZZ<F> P = work[i];
-    if (P.zzz.is_zero()) {
-      out[i] = Affine<F>::infinity();
-      continue;
-    }
-    const F iz3 = inv * out[i].x;
-    inv = inv * P.zzz;
-    const F iz2 = (iz3 * P.zz).sqr();
-    out[i] = Affine<F>{P.x * iz2, P.y * iz3};
-  }
-}
-
-// Launched in front of the event that opens a timed phase.  An event recorded behind an idle stretch of its stream
-// can take the time of the command BEFORE the gap (the copy of the chunk before), and the phase would then count
-// the gap; behind this kernel it takes the time at which the phase's own work is about to start.
-__global__ void k_sx_mark() {}
-
 struct Item {
   bool g2;
   const uint8_t* src;
   uint8_t* dst;
   uint32_t count;
-};
-
-struct TimedEvent {
-  hipEvent_t e = nullptr;
-  bool made = false;
-  ~TimedEvent() {
-    if (made) (void)hipEventDestroy(e);
-  }
-  void create() {
-    G16_HIP(hipEventCreate(&e));
-    made = true;
-  }
 };
 
 // the events of one slot, in the order they complete
@@ -140,6 +78,7 @@ enum { E_UP0 = 0, E_UP1, E_C0, E_C1, E_C2, E_C3, E_DN0, E_DN1, E_COUNT };
 struct Secret {
   Fr s[3];  // t, a, b
   U256 c;
+  FrPool pool;  // the candidates of drawn secrets
   std::vector<Fr> dev;  // what goes to the device: t^(2^j), j < SX_POW_BITS, then one c t^base per chunk
   ~Secret() {
     if (!dev.empty()) wipe(dev.data(), dev.size() * sizeof(Fr));
@@ -147,20 +86,6 @@ struct Secret {
     wipe(&c, sizeof c);
   }
 };
-
-bool draw_fr(Fr* out, U256* tmp) {  // uniform in [1, r): 254 random bits, rejected outside the range
-  for (;;) {
-    if (!os_random(tmp, 32)) return false;
-    tmp->v[7] &= 0x3fffffffu;
-    Fr c;
-    memcpy(&c, tmp, 32);
-    const bool in_range = fr_words_canonical(c) && !c.is_zero();
-    wipe(&c, sizeof c);
-    if (in_range) break;
-  }
-  *out = Fr::from_canonical(*tmp);
-  return true;
-}
 
 }  // namespace
 }  // namespace g16
@@ -180,21 +105,14 @@ extern "C" g16_status g16_srs_contribute(int device, const g16_srs_desc* srs, co
     for (const Fr& x : sec.s)
       if (!fr_words_canonical(x) || x.is_zero()) return G16_ERR_INVALID;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return G16_ERR_NO_DEVICE;
-  if (device < 0 || device >= ndev) return G16_ERR_INVALID;
-  if (!secrets && !(draw_fr(&sec.s[0], &sec.c) && draw_fr(&sec.s[1], &sec.c) && draw_fr(&sec.s[2], &sec.c)))
-    return G16_ERR_INTERNAL;  // never a fixed fallback
+  if (const g16_status ds = device_ok(device)) return ds;
+  if (!secrets)
+    for (Fr& x : sec.s)
+      if (!sec.pool.draw_fr(&x, true)) return G16_ERR_INTERNAL;  // never a fixed fallback
   const Fr &t = sec.s[0], &a = sec.s[1], &b = sec.s[2];
 
-  try {
-    const uint64_t longest = n1 > n2 ? n1 : n2;
-    uint32_t chunk = SX_DEFAULT_CHUNK;
-    if (const char* e = getenv("G16_SRSCONTRIB_CHUNK")) {  // tests: points per staged chunk
-      const unsigned long long v = strtoull(e, nullptr, 0);
-      if (v >= 1 && v <= SX_MAX_CHUNK) chunk = (uint32_t)v;
-    }
-    if (chunk > longest) chunk = (uint32_t)longest;
+  return guarded_call([&]() -> g16_status {
+    const uint32_t chunk = chunk_from_env("G16_SRSCONTRIB_CHUNK", SX_DEFAULT_CHUNK, n1 > n2 ? n1 : n2);
 
     // the chunks of the four arrays, and per chunk its c t^base behind the powers t^(2^j)
     std::vector<Item> items;
@@ -234,11 +152,11 @@ extern "C" g16_status g16_srs_contribute(int device, const g16_srs_desc* srs, co
     DevBuf<U256> dsc;
     DevBuf<Fr> dsec;
     StreamBox copy, comp, down;
-    TimedEvent ev[2][E_COUNT];
+    EventBox ev[2][E_COUNT];
     for (int s = 0; s < 2; ++s) {
       pin[s].alloc(slot_bytes);
       dslot[s].alloc(slot_bytes);
-      for (int e = 0; e < E_COUNT; ++e) ev[s][e].create();
+      for (int e = 0; e < E_COUNT; ++e) ev[s][e].create(true);
     }
     dwork.alloc((size_t)chunk * sizeof(G2XYZZ));
     dsc.alloc(chunk);
@@ -248,17 +166,14 @@ extern "C" g16_status g16_srs_contribute(int device, const g16_srs_desc* srs, co
     down.create();
     G16_HIP(hipMemcpy(dsec.p, sec.dev.data(), sec.dev.size() * sizeof(Fr), hipMemcpyHostToDevice));
 
-    float ms[T_COUNT] = {0};
+    PhaseTimes<T_COUNT> ms{};  // of this call: the chunks add up, the thread's values change when all is done
     auto collect = [&](int s, bool g2) {
-      const int pairs[5][3] = {{E_UP0, E_UP1, T_UPLOAD},
-                               {E_C0, E_C1, T_SCALARS},
-                               {E_C1, E_C2, g2 ? T_MUL_G2 : T_MUL_G1},
-                               {E_C2, E_C3, T_AFFINE},
-                               {E_DN0, E_DN1, T_DOWNLOAD}};
-      for (const auto& p : pairs) {
-        float t = 0.f;
-        if (hipEventElapsedTime(&t, ev[s][p[0]].e, ev[s][p[1]].e) == hipSuccess) ms[p[2]] += t;
-      }
+      ms.take(Stored::ADD, ev[s],
+              {{E_UP0, E_UP1, T_UPLOAD},
+               {E_C0, E_C1, T_SCALARS},
+               {E_C1, E_C2, g2 ? T_MUL_G2 : T_MUL_G1},
+               {E_C2, E_C3, T_AFFINE},
+               {E_DN0, E_DN1, T_DOWNLOAD}});
     };
 
     for (size_t k = 0; k < items.size() + 2; ++k) {
@@ -275,12 +190,12 @@ extern "C" g16_status g16_srs_contribute(int device, const g16_srs_desc* srs, co
       const size_t bytes = (size_t)n * (it.g2 ? 128 : 64);
       uint8_t* dv = dslot[s].p;
       memcpy(pin[s].p, it.src, bytes);
-      G16_LAUNCH(k_sx_mark, 1, 1, 0, copy.s);
+      G16_LAUNCH(k_phase_mark<>, 1, 1, 0, copy.s);
       G16_HIP(hipEventRecord(ev[s][E_UP0].e, copy.s));
       G16_HIP(hipMemcpyAsync(dv, pin[s].p, bytes, hipMemcpyHostToDevice, copy.s));
       G16_HIP(hipEventRecord(ev[s][E_UP1].e, copy.s));
       G16_HIP(hipStreamWaitEvent(comp.s, ev[s][E_UP1].e, 0));
-      G16_LAUNCH(k_sx_mark, 1, 1, 0, comp.s);
+      G16_LAUNCH(k_phase_mark<>, 1, 1, 0, comp.s);
       G16_HIP(hipEventRecord(ev[s][E_C0].e, comp.s));
       G16_LAUNCH(k_sx_scalars, ceil_div(n, 256), 256, 0, comp.s, (const Fr*)dsec.p,
                  (const Fr*)(dsec.p + SX_POW_BITS + k), n, dsc.p);
@@ -289,18 +204,16 @@ extern "C" g16_status g16_srs_contribute(int device, const g16_srs_desc* srs, co
         G16_LAUNCH((k_sx_mul<Fq2>), ceil_div(n, KC_BLOCK), KC_BLOCK, 0, comp.s, (const G2Affine*)dv, (const U256*)dsc.p,
                    n, (G2XYZZ*)dwork.p);
         G16_HIP(hipEventRecord(ev[s][E_C2].e, comp.s));
-        G16_LAUNCH((k_sx_affine<Fq2>), ceil_div(n, KC_BLOCK * SX_RUN), KC_BLOCK, 0, comp.s, (const G2XYZZ*)dwork.p, n,
-                   (G2Affine*)dv);
+        xyzz_to_affine<Fq2>((const G2XYZZ*)dwork.p, n, (G2Affine*)dv, comp.s);
       } else {
         G16_LAUNCH((k_sx_mul<Fq>), ceil_div(n, KC_BLOCK), KC_BLOCK, 0, comp.s, (const G1Affine*)dv, (const U256*)dsc.p,
                    n, (G1XYZZ*)dwork.p);
         G16_HIP(hipEventRecord(ev[s][E_C2].e, comp.s));
-        G16_LAUNCH((k_sx_affine<Fq>), ceil_div(n, KC_BLOCK * SX_RUN), KC_BLOCK, 0, comp.s, (const G1XYZZ*)dwork.p, n,
-                   (G1Affine*)dv);
+        xyzz_to_affine<Fq>((const G1XYZZ*)dwork.p, n, (G1Affine*)dv, comp.s);
       }
       G16_HIP(hipEventRecord(ev[s][E_C3].e, comp.s));
       G16_HIP(hipStreamWaitEvent(down.s, ev[s][E_C3].e, 0));
-      G16_LAUNCH(k_sx_mark, 1, 1, 0, down.s);
+      G16_LAUNCH(k_phase_mark<>, 1, 1, 0, down.s);
       G16_HIP(hipEventRecord(ev[s][E_DN0].e, down.s));
       G16_HIP(hipMemcpyAsync(pin[s].p, dv, bytes, hipMemcpyDeviceToHost, down.s));
       G16_HIP(hipEventRecord(ev[s][E_DN1].e, down.s));
@@ -312,17 +225,11 @@ extern "C" g16_status g16_srs_contribute(int device, const g16_srs_desc* srs, co
     G16_HIP(hipStreamSynchronize(comp.s));
     G16_HIP(hipStreamSynchronize(down.s));
     memcpy(beta_g2_out, &nbg2, 128);
-    memcpy(t_phase_ms, ms, sizeof ms);
+    t_phase = ms;
     return G16_OK;
-  } catch (const HipError&) {
-    return G16_ERR_HIP;
-  } catch (const std::exception&) {
-    return G16_ERR_INTERNAL;
-  }
+  });
 }
 
 extern "C" g16_status g16_srs_contribute_times(float* ms, uint32_t cap) {
-  if (!ms) return G16_ERR_INVALID;
-  for (uint32_t i = 0; i < cap; ++i) ms[i] = i < (uint32_t)T_COUNT ? t_phase_ms[i] : 0.f;
-  return G16_OK;
+  return t_phase.read(ms, cap);
 }

@@ -32,7 +32,7 @@ namespace {
 constexpr uint32_t LC_DEFAULT_CHUNK = 1u << 18;
 constexpr uint32_t LC_N = G16_LAGRANGE_N_ARRAYS;
 
-thread_local float t_prepare_ms[7];  // the phases of g16_setup_from_srs_times
+thread_local PhaseTimes<7> t_prepare;  // the phases of g16_setup_from_srs_times
 
 struct LcState {  // device-resident for the whole call
   CheckTally tally;
@@ -161,11 +161,11 @@ g16_status g16_srs_prepare(int device, const g16_srs_desc* srs, uint32_t power, 
   const uint32_t nP = 1u << power, n_top = 2 * nP;
   if ((uint64_t)srs->n_tau_g1 < (uint64_t)n_top - 1 || srs->n_tau < nP) return G16_ERR_INVALID;
   if (const g16_status ds = device_ok(device)) return ds;
-  try {
+  return guarded_call([&]() -> g16_status {
     G16_HIP(hipSetDevice(device));
     hipStream_t s = nullptr;
-    memset(t_prepare_ms, 0, sizeof t_prepare_ms);
-    PhaseClock clk(t_prepare_ms, s);
+    t_prepare.clear();
+    PhaseClock clk(t_prepare.ms, s);
     DevBuf<G1Affine> in1, o1;
     DevBuf<G2Affine> in2, o2;
     DevBuf<G1XYZZ29> w1;
@@ -213,17 +213,11 @@ g16_status g16_srs_prepare(int device, const g16_srs_desc* srs, uint32_t power, 
       }
     }
     return G16_OK;
-  } catch (const HipError&) {
-    return G16_ERR_HIP;
-  } catch (const std::exception&) {
-    return G16_ERR_INTERNAL;
-  }
+  });
 }
 
 g16_status g16_srs_prepare_times(float* ms, uint32_t cap) {
-  if (!ms) return G16_ERR_INVALID;
-  for (uint32_t i = 0; i < cap; ++i) ms[i] = i < 7 ? t_prepare_ms[i] : 0.f;
-  return G16_OK;
+  return t_prepare.read(ms, cap);
 }
 
 g16_status g16_srs_lagrange_check(int device, const g16_srs_desc* srs, const g16_srs_lagrange_desc* lag,
@@ -239,7 +233,7 @@ g16_status g16_srs_lagrange_check(int device, const g16_srs_desc* srs, const g16
   const uint64_t m1 = 2 * n_top - 1, m2 = n_top - 1;  // points of section 12 / of sections 13-15
   if (!rho_all_nonzero(rho, m1 + 3 * m2)) return G16_ERR_INVALID;
   if (const g16_status ds = device_ok(device)) return ds;
-  try {
+  return guarded_call([&]() -> g16_status {
     const uint32_t chunk = chunk_from_env("G16_LAGCHECK_CHUNK", LC_DEFAULT_CHUNK, m1);
     const uint32_t nb_max = ceil_div(chunk, KC_BLOCK);
 
@@ -357,11 +351,7 @@ g16_status g16_srs_lagrange_check(int device, const g16_srs_desc* srs, const g16
                stage.dout.p);
     stage.finish(hs.get(), dst.p, report, bad_out);
     return G16_OK;
-  } catch (const HipError&) {
-    return G16_ERR_HIP;
-  } catch (const std::exception&) {
-    return G16_ERR_INTERNAL;
-  }
+  });
 }
 
 }  // extern "C"

@@ -482,7 +482,7 @@ g16_status verify_batch_groups(int device, const g16_vk_desc* const* vks, const 
     return G16_ERR_INVALID;
   if (const g16_status ds = device_ok(device)) return ds;
   if (!n) return G16_OK;
-  try {
+  return guarded_call([&]() -> g16_status {
     G16_HIP(hipSetDevice(device));
     Plan pl;
     make_plan(pl, vks, counts, n_keys, nullptr);
@@ -498,11 +498,7 @@ g16_status verify_batch_groups(int device, const g16_vk_desc* const* vks, const 
     G16_HIP(hipDeviceSynchronize());
     G16_HIP(hipMemcpy(ok_out, dok.p, n, hipMemcpyDeviceToHost));
     return G16_OK;
-  } catch (const HipError&) {
-    return G16_ERR_HIP;
-  } catch (const std::exception&) {
-    return G16_ERR_INTERNAL;
-  }
+  });
 }
 
 // g16_verify_aggregate_keys; g16_verify_aggregate is the call with one group
@@ -519,7 +515,7 @@ g16_status verify_aggregate_groups(int device, const g16_vk_desc* const* vks, co
     memset(ok_out, 1, n_keys);
     return G16_OK;
   }
-  try {
+  return guarded_call([&]() -> g16_status {
     std::vector<uint64_t> drawn;
     if (!rho) {
       drawn.resize(2 * (size_t)n);
@@ -573,11 +569,7 @@ g16_status verify_aggregate_groups(int device, const g16_vk_desc* const* vks, co
     G16_HIP(hipMemcpy(ok_out, dok.p, n_keys, hipMemcpyDeviceToHost));
     if (structural_out) G16_HIP(hipMemcpy(structural_out, dstruct.p, n, hipMemcpyDeviceToHost));
     return G16_OK;
-  } catch (const HipError&) {
-    return G16_ERR_HIP;
-  } catch (const std::exception&) {
-    return G16_ERR_INTERNAL;
-  }
+  });
 }
 
 }  // namespace

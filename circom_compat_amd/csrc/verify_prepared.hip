@@ -22,15 +22,10 @@
 #include "pairing_coop.h"
 
 namespace g16 {
-void set_create_error(const std::string& msg);  // api.hip: what g16_last_error(NULL) returns
-
 namespace {
 
 enum { T_UPLOAD = 0, T_INPUTS, T_G2, T_PAIRING, T_DOWNLOAD, T_PREPARE, T_COUNT };
-thread_local float t_phase_ms[T_COUNT];
-
-// in front of the event that opens a timed phase (srs_contribute.hip's k_sx_mark explains why)
-__global__ void k_vp_mark() {}
+thread_local PhaseTimes<T_COUNT> t_phase;
 
 // block 0: ML(beta, -alpha); block 1: gamma's table; block 2: delta's
 __global__ void k_pvk_prepare(VkDev* vk, PvkTable* tabs) {
@@ -194,18 +189,6 @@ __global__ void k_vp_and(uint8_t* ok, const uint8_t* g2ok, uint32_t n, uint32_t 
   if (i < n) ok[i] &= g2ok[i];
 }
 
-struct TimedEvent {
-  hipEvent_t e = nullptr;
-  bool made = false;
-  ~TimedEvent() {
-    if (made) (void)hipEventDestroy(e);
-  }
-  void create() {
-    G16_HIP(hipEventCreate(&e));
-    made = true;
-  }
-};
-
 // a buffer that only grows: releasing device memory waits for the whole device
 template <class T>
 struct GrowBuf {
@@ -261,7 +244,7 @@ struct g16_pvk {
   bool gt_made = false;
   uint64_t k_lo = 0, k_hi = 0;
   StreamBox s1, s2;
-  TimedEvent ev[E_COUNT];
+  EventBox ev[E_COUNT];
   GrowPinned pin;
   GrowBuf<uint8_t> dproofs, dok, dg2ok, dxok;
   GrowBuf<Fr> dpub;
@@ -280,7 +263,7 @@ extern "C" g16_status g16_pvk_create(int device, const g16_vk_desc* vk, g16_pvk*
     set_create_error("g16_pvk_create: device out of range");
     return G16_ERR_INVALID;
   }
-  try {
+  return guarded_call([&]() -> g16_status {
     std::unique_ptr<VkDev> hv(new VkDev());
     fill_consts(hv.get());
     G1Affine alpha;
@@ -321,29 +304,21 @@ extern "C" g16_status g16_pvk_create(int device, const g16_vk_desc* vk, g16_pvk*
     h->dic.alloc(vk->ic_count);
     h->s1.create();
     h->s2.create();
-    for (auto& e : h->ev) e.create();
+    for (auto& e : h->ev) e.create(true);
     hipStream_t s = h->s1.s;
     G16_HIP(hipMemcpyAsync(h->dvk.p, hv.get(), sizeof(VkDev), hipMemcpyHostToDevice, s));
     G16_HIP(hipMemcpyAsync(h->dic.p, ic.data(), h->dic.bytes(), hipMemcpyHostToDevice, s));
-    G16_LAUNCH(k_vp_mark, 1, 1, 0, s);
+    G16_LAUNCH(k_phase_mark<>, 1, 1, 0, s);
     G16_HIP(hipEventRecord(h->ev[E_UP0].e, s));
     G16_LAUNCH(k_pvk_prepare, 3, 1, 0, s, h->dvk.p, h->dtab.p);
     G16_HIP(hipEventRecord(h->ev[E_UP1].e, s));
     G16_HIP(hipMemcpyAsync(&h->ml_alpha_beta, &h->dvk.p->ml_alpha_beta, sizeof(F12), hipMemcpyDeviceToHost, s));
     G16_HIP(hipGetLastError());
     G16_HIP(hipStreamSynchronize(s));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, h->ev[E_UP0].e, h->ev[E_UP1].e) != hipSuccess) ms = 0.f;
-    t_phase_ms[T_PREPARE] = ms;
+    t_phase.take(Stored::REPLACE, h->ev, {{E_UP0, E_UP1, T_PREPARE}});
     *out = h.release();
     return G16_OK;
-  } catch (const HipError& e) {
-    set_create_error(e.what());
-    return G16_ERR_HIP;
-  } catch (const std::exception& e) {
-    set_create_error(e.what());
-    return G16_ERR_INTERNAL;
-  }
+  });
 }
 
 extern "C" void g16_pvk_destroy(g16_pvk* pvk) {
@@ -368,7 +343,7 @@ static g16_status verify_prepared_run(g16_pvk* h, const uint8_t* proofs, const u
   if ((uint64_t)n * n_pub > 0xffffffffull / 32 || n > 0xffffffffu / G16_PROOF_BYTES) return G16_ERR_INVALID;
   if (!n) return G16_OK;
   std::lock_guard<std::mutex> guard(h->mu);
-  try {
+  return guarded_call([&]() -> g16_status {
     G16_HIP(hipSetDevice(h->device));
     const size_t pbytes = (size_t)n * G16_PROOF_BYTES, ibytes = (size_t)n * n_pub * 32;
     if (prepared) h->dxok.need(n);
@@ -384,7 +359,7 @@ static g16_status verify_prepared_run(g16_pvk* h, const uint8_t* proofs, const u
     memcpy(h->pin.p, proofs, pbytes);
     if (ibytes) memcpy(h->pin.p + pbytes, prepared ? (const void*)prepared : (const void*)public_inputs, ibytes);
 
-    G16_LAUNCH(k_vp_mark, 1, 1, 0, s1);
+    G16_LAUNCH(k_phase_mark<>, 1, 1, 0, s1);
     G16_HIP(hipEventRecord(ev[E_UP0].e, s1));
     G16_HIP(hipMemcpyAsync(h->dproofs.d.p, h->pin.p, pbytes, hipMemcpyHostToDevice, s1));
     if (ibytes) G16_HIP(hipMemcpyAsync(h->dpub.d.p, h->pin.p + pbytes, ibytes, hipMemcpyHostToDevice, s1));
@@ -392,7 +367,7 @@ static g16_status verify_prepared_run(g16_pvk* h, const uint8_t* proofs, const u
 
     // the tests of B on the second stream, beside the inputs and the pairing
     G16_HIP(hipStreamWaitEvent(s2, ev[E_UP1].e, 0));
-    G16_LAUNCH(k_vp_mark, 1, 1, 0, s2);
+    G16_LAUNCH(k_phase_mark<>, 1, 1, 0, s2);
     G16_HIP(hipEventRecord(ev[E_G2A].e, s2));
     G16_LAUNCH(k_vp_g2, ceil_div(n, COOP_LANES), COOP_LANES, 0, s2, (const VkDev*)h->dvk.p,
                (const uint8_t*)h->dproofs.d.p + 64, (uint32_t)G16_PROOF_BYTES, n, h->k_lo, h->k_hi, h->dg2ok.d.p);
@@ -419,21 +394,11 @@ static g16_status verify_prepared_run(g16_pvk* h, const uint8_t* proofs, const u
     G16_HIP(hipStreamSynchronize(s2));
     memcpy(ok_out, pin_ok, n);
 
-    const float prepare = t_phase_ms[T_PREPARE];
-    const int spans[5][3] = {{E_UP0, E_UP1, T_UPLOAD}, {E_UP1, E_IN, T_INPUTS}, {E_G2A, E_G2B, T_G2},
-                             {E_IN, E_PAIR, T_PAIRING}, {E_DN0, E_DN1, T_DOWNLOAD}};
-    for (const auto& sp : spans) {
-      float t = 0.f;
-      if (hipEventElapsedTime(&t, ev[sp[0]].e, ev[sp[1]].e) != hipSuccess) t = 0.f;
-      t_phase_ms[sp[2]] = t;
-    }
-    t_phase_ms[T_PREPARE] = prepare;
+    t_phase.take(Stored::REPLACE, ev,  // T_PREPARE stays: it is g16_pvk_create's
+                 {{E_UP0, E_UP1, T_UPLOAD}, {E_UP1, E_IN, T_INPUTS}, {E_G2A, E_G2B, T_G2},
+                  {E_IN, E_PAIR, T_PAIRING}, {E_DN0, E_DN1, T_DOWNLOAD}});
     return G16_OK;
-  } catch (const HipError&) {
-    return G16_ERR_HIP;
-  } catch (const std::exception&) {
-    return G16_ERR_INTERNAL;
-  }
+  });
 }
 
 extern "C" g16_status g16_verify_prepared(g16_pvk* h, const uint8_t* proofs, const uint64_t* public_inputs,
@@ -454,7 +419,7 @@ extern "C" g16_status g16_pvk_prepare_inputs(g16_pvk* h, const uint64_t* public_
   if ((uint64_t)n * n_pub > 0xffffffffull / 32 || n > 0xffffffffu / 64) return G16_ERR_INVALID;
   if (!n) return G16_OK;
   std::lock_guard<std::mutex> guard(h->mu);
-  try {
+  return guarded_call([&]() -> g16_status {
     G16_HIP(hipSetDevice(h->device));
     const size_t ibytes = (size_t)n * n_pub * 32;
     h->dpub.need((size_t)n * n_pub + 1);
@@ -470,11 +435,7 @@ extern "C" g16_status g16_pvk_prepare_inputs(g16_pvk* h, const uint64_t* public_
     G16_HIP(hipGetLastError());
     G16_HIP(hipStreamSynchronize(s1));
     return G16_OK;
-  } catch (const HipError&) {
-    return G16_ERR_HIP;
-  } catch (const std::exception&) {
-    return G16_ERR_INTERNAL;
-  }
+  });
 }
 
 extern "C" g16_status g16_pvk_alpha_g1_beta_g2(const g16_pvk* pvk, uint8_t out[384]) {
@@ -497,7 +458,7 @@ extern "C" g16_status g16_pairing_check(int device, const uint8_t* g1, const uin
                                         uint8_t* ok_out) {
   if (!g1 || !g2 || !ok_out || n_pairs < 1 || n_pairs > COOP_MAX_PAIRS) return G16_ERR_INVALID;
   if (const g16_status ds = device_ok(device)) return ds;
-  try {
+  return guarded_call([&]() -> g16_status {
     G16_HIP(hipSetDevice(device));
     std::unique_ptr<VkDev> hv(new VkDev());
     memset((void*)hv.get(), 0, sizeof(VkDev));
@@ -536,15 +497,9 @@ extern "C" g16_status g16_pairing_check(int device, const uint8_t* g1, const uin
     G16_HIP(hipStreamSynchronize(s2.s));
     *ok_out = ok;
     return G16_OK;
-  } catch (const HipError&) {
-    return G16_ERR_HIP;
-  } catch (const std::exception&) {
-    return G16_ERR_INTERNAL;
-  }
+  });
 }
 
 extern "C" g16_status g16_verify_prepared_times(float* ms, uint32_t cap) {
-  if (!ms) return G16_ERR_INVALID;
-  for (uint32_t i = 0; i < cap; ++i) ms[i] = i < (uint32_t)T_COUNT ? t_phase_ms[i] : 0.f;
-  return G16_OK;
+  return t_phase.read(ms, cap);
 }

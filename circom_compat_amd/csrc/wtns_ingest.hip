@@ -4,33 +4,26 @@
 // this replaces (loaders.cpp, wtns_parse) does the same product one element after the other.
 #include "wtns_ingest.h"
 
-#include "../../include/g16_amd.h"
+#include "hostcall.h"
 
 namespace g16 {
-void set_create_error(const std::string& msg);  // api.hip: what g16_last_error(NULL) returns
-
 namespace {
 
 constexpr int INGEST_BLOCK = 256;
 
 // g16_fr_convert_times: device milliseconds of the calling thread's last g16_fr_convert
 enum { T_UPLOAD = 0, T_CONVERT, T_DOWNLOAD, T_COUNT };
-thread_local float t_phase_ms[T_COUNT] = {0.f, 0.f, 0.f};
+thread_local PhaseTimes<T_COUNT> t_phase;
 
 struct Events {  // the four marks around the three phases, on the null stream
-  hipEvent_t e[T_COUNT + 1] = {};
+  EventBox e[T_COUNT + 1];
   Events() {
-    for (auto& x : e) G16_HIP(hipEventCreate(&x));
+    for (auto& x : e) x.create(true);
   }
-  ~Events() {
-    for (auto x : e)
-      if (x) (void)hipEventDestroy(x);
-  }
-  void mark(int i) { G16_HIP(hipEventRecord(e[i], nullptr)); }
+  void mark(int i) { G16_HIP(hipEventRecord(e[i].e, nullptr)); }
   void collect() {
-    G16_HIP(hipEventSynchronize(e[T_COUNT]));
-    for (int i = 0; i < T_COUNT; ++i)
-      if (hipEventElapsedTime(&t_phase_ms[i], e[i], e[i + 1]) != hipSuccess) t_phase_ms[i] = 0.f;
+    G16_HIP(hipEventSynchronize(e[T_COUNT].e));
+    t_phase.take(Stored::REPLACE, e, {{0, 1, T_UPLOAD}, {1, 2, T_CONVERT}, {2, 3, T_DOWNLOAD}});
   }
 };
 
@@ -78,13 +71,11 @@ extern "C" g16_status g16_fr_convert(int device, const uint8_t* in_le, uint64_t*
     set_create_error("g16_fr_convert: 2^39 elements or more");
     return G16_ERR_INVALID;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return G16_ERR_NO_DEVICE;
-  if (device < 0 || device >= ndev) {
-    set_create_error("g16_fr_convert: device out of range");
-    return G16_ERR_INVALID;
+  if (const g16_status ds = device_ok(device)) {
+    if (ds == G16_ERR_INVALID) set_create_error("g16_fr_convert: device out of range");
+    return ds;
   }
-  try {
+  return guarded_call([&]() -> g16_status {
     G16_HIP(hipSetDevice(device));
     DevBuf<Fr> buf;
     DevBuf<unsigned long long> bad;
@@ -92,7 +83,7 @@ extern "C" g16_status g16_fr_convert(int device, const uint8_t* in_le, uint64_t*
     bad.alloc(1);
     unsigned long long bad_host = INGEST_NONE;
     Events ev;
-    for (float& t : t_phase_ms) t = 0.f;
+    t_phase.clear();
     ev.mark(T_UPLOAD);
     G16_HIP(hipMemcpy(buf.p, in_le, n * 32, hipMemcpyHostToDevice));
     G16_HIP(hipMemcpy(bad.p, &bad_host, 8, hipMemcpyHostToDevice));
@@ -109,17 +100,9 @@ extern "C" g16_status g16_fr_convert(int device, const uint8_t* in_le, uint64_t*
       return G16_ERR_INVALID;
     }
     return G16_OK;
-  } catch (const HipError& e) {
-    set_create_error(e.what());
-    return G16_ERR_HIP;
-  } catch (const std::exception& e) {
-    set_create_error(e.what());
-    return G16_ERR_INTERNAL;
-  }
+  });
 }
 
 extern "C" g16_status g16_fr_convert_times(float* ms, uint32_t cap) {
-  if (!ms) return G16_ERR_INVALID;
-  for (uint32_t i = 0; i < cap; ++i) ms[i] = i < (uint32_t)T_COUNT ? t_phase_ms[i] : 0.f;
-  return G16_OK;
+  return t_phase.read(ms, cap);
 }

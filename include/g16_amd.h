@@ -145,6 +145,15 @@ void g16_ctx_destroy(g16_ctx* ctx);
 g16_status g16_ctx_create_sibling(g16_ctx* donor, const g16_key_desc* key, const g16_csr* a, const g16_csr* b,
                                   uint32_t num_constraints, const g16_options* opt, g16_ctx** out);
 const char* g16_last_error(const g16_ctx* ctx); /* ctx may be NULL: error of the last failed create */
+/* g16_last_error(NULL) also holds the message of the last failed call that takes no ctx.  A call that ends with
+ * G16_ERR_HIP or G16_ERR_INTERNAL because an exception was caught on the host records the exception's text there
+ * (the failing HIP call with its file and line, or the allocation that failed).  That now includes the calls that
+ * used to return the status alone: g16_key_check, g16_key_contribute, g16_key_contribution_check, g16_srs_check,
+ * g16_srs_contribute, g16_srs_create, g16_srs_prepare, g16_srs_lagrange_check, g16_setup_from_srs /
+ * _from_prepared, g16_verify_batch / _aggregate and their _keys forms, g16_verify_prepared / _inputs,
+ * g16_pvk_prepare_inputs, g16_pairing_check, g16_proofs_rerandomize / _keys, g16_points_from_ark / _to_ark.
+ * Not covered: g16_setup_create (its message stays internal) and the calls of g16_loaders.h, which keep their own
+ * thread-local message (g16_loader_last_error).                                                        */
 
 /* Single-process multi-device prover (`device_ids, n_dev`; section 8(e)).
  * One sharded rank per listed device INSIDE the library: the MSMs are cut over the devices as

@@ -1,6 +1,7 @@
 // arith_hooks.hip -- TEST INFRASTRUCTURE ONLY: one-thread-per-case kernels around single operations of
 // field29.h / ec29.h (raw limbs in, RAW result limbs out, so that pytest can check the output classes the
-// headers document) and of field.h / ec.h (storage form in and out).
+// headers document) and of field.h / ec.h (storage form in and out); and the launcher of toaffine.h as the product
+// calls it.
 //
 // Built twice from this one file (csrc/Makefile): with g++ against the SIMT emulator into
 // tests/emu/libg16_emu.so, where the F29_CHECK input asserts stay on, and with hipcc and the product flags
@@ -9,6 +10,7 @@
 // Every wrapper returns 0, a HIP error code, or -1 for an operation the chosen field / curve does not have.
 #include "common.h"
 #include "ec29.h"
+#include "toaffine.h"
 
 using namespace g16;
 
@@ -424,9 +426,31 @@ int run_ec_op(int op, const uint8_t* P, const uint8_t* Q, const uint8_t* l1, con
   return dout.download(out, n * sizeof(Affine<F>));
 }
 
+// out: out_bytes the caller has filled (guard pattern and all); the kernel writes its slots into it
+template <class F>
+int run_to_affine(const uint8_t* work, uint32_t total, uint32_t n, uint32_t off0, uint32_t off1, uint32_t stride,
+                  uint8_t* out, size_t out_bytes) {
+  Dev dwork, dout;
+  ARITH_TRY(dwork.upload(work, (size_t)total * sizeof(XYZZ<F>)));
+  ARITH_TRY(dout.upload(out, out_bytes));
+  xyzz_to_affine<F>((const XYZZ<F>*)dwork.p, total, n, off0, off1, stride, (uint8_t*)dout.p, (hipStream_t)0);
+  ARITH_TRY(finish_launch());
+  return dout.download(out, out_bytes);
+}
+
 }  // namespace
 
 extern "C" {
+// toaffine.h's launcher.  g2: 0 = Fq, 1 = Fq2.  Every slot must lie inside out_bytes: checked here, -2 if not.
+int arith_to_affine(int g2, const uint8_t* work, uint32_t total, uint32_t n, uint32_t off0, uint32_t off1,
+                    uint32_t stride, uint8_t* out, size_t out_bytes) {
+  const size_t pt = g2 ? sizeof(G2Affine) : sizeof(G1Affine);
+  const uint64_t lo = total < n ? total : n, hi = total > n ? total - n : 0;
+  if (lo && (uint64_t)(lo - 1) * stride + off0 + pt > out_bytes) return -2;
+  if (hi && (uint64_t)(hi - 1) * stride + off1 + pt > out_bytes) return -2;
+  return g2 ? run_to_affine<Fq2>(work, total, n, off0, off1, stride, out, out_bytes)
+            : run_to_affine<Fq>(work, total, n, off0, off1, stride, out, out_bytes);
+}
 // field: 0 = Fq29, 1 = Fr29, 2 = Fq2x29 (18 limbs per operand)
 int arith_f29_op(int field, int op, const int32_t* in, int32_t* out, int32_t* flag, size_t n) {
   switch (field) {

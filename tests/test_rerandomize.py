@@ -326,6 +326,17 @@ def test_invalid_arguments_write_nothing(lib, golden):
     assert cc.rerandomize_keys([], lib=lib) == [] and cc.rerandomize_keys([(vk, []), (vk, [])], lib=lib) == [[], []]
 
 
+def test_the_device_behind_the_last_is_invalid(emu, golden):
+    """the emulator has one device: device 1 is the first that does not exist.  The refusal is hostcall.h's device_ok
+    now; it is still G16_ERR_INVALID, with drawn scalars (nothing is drawn for it) as with given ones"""
+    vk, _opk, raws, _pubs = _batch(emu, golden, 2)
+    delta = (C.c_uint8 * 128).from_buffer_copy(bytes(vk.delta_g2))
+    for scalars in ([(3, 4), (5, 0)], None):
+        st, out, ok = _call(emu, delta, raws, scalars, device=1)
+        assert st == B.G16_ERR_INVALID
+        assert (out == 0xA5).all() and (ok == 0xA5).all()
+
+
 # ---- 10. many keys ---------------------------------------------------------------------------------------------
 def test_groups_under_several_keys(lib, golden):
     import circom_compat_amd as cc
