@@ -1168,7 +1168,7 @@ static g16_status msm_common(g16_ctx* c, int which, bool g2, const uint64_t* sca
     uint32_t idx_min = 0;
     const MsmPoints<Fq>* P1 = nullptr;
     size_t maxlen = 0;
-    Fr* stage = c->w_dev.p;  // scalar staging: reuse the witness / h buffers
+    Fr* stage = nullptr;  // host scalars: msm_stage (never w_dev: a resident witness stays), h_dev for the H query
     if (g2) {
       maxlen = c->ptsB2.count;
     } else if (which == G16_QUERY_A) {
@@ -1189,8 +1189,17 @@ static g16_status msm_common(g16_ctx* c, int which, bool g2, const uint64_t* sca
       return fail(c, G16_ERR_INVALID, "unknown query id");
     }
     if (len > maxlen) return fail(c, G16_ERR_INVALID, "more scalars than resident points");
-    if (on_device) stage = (Fr*)const_cast<uint64_t*>(scalars);
-    else G16_HIP(hipMemcpyAsync(stage, scalars, len * 32, hipMemcpyHostToDevice, s));
+    if (on_device) {
+      stage = (Fr*)const_cast<uint64_t*>(scalars);
+    } else {
+      if (!stage) {
+        if (!c->msm_stage.p)
+          c->msm_stage.alloc(std::max({(size_t)c->ptsA.count, (size_t)c->ptsB1.count, (size_t)c->ptsL.count,
+                                       (size_t)c->ptsB2.count, (size_t)1}));
+        stage = c->msm_stage.p;
+      }
+      G16_HIP(hipMemcpyAsync(stage, scalars, len * 32, hipMemcpyHostToDevice, s));
+    }
     sort->run(stage, (uint32_t)len, true, s);
     (void)idx_min;
     if (g2) {

@@ -83,6 +83,9 @@ struct g16_ctx {
   g16::TableSet tbl;  // small keys: fixed-base tables (msm_table.h); g16_prove goes through them when active
 
   g16::DevBuf<g16::Fr> w_dev, h_dev, rs_dev;  // h_dev: storage form (g16_witness_map / g16_msm_g1 staging)
+  // host scalars of g16_msm_g1 (A, B1, L) / g16_msm_g2: a buffer of their own, so that the resident witness in
+  // w_dev survives those calls; allocated at the first such call (the create-time memory plan does not see it)
+  g16::DevBuf<g16::Fr> msm_stage;
   g16::DevBuf<g16::U256> h_canon;             // h as canonical integers: scalars of the H-query MSM
   g16::DevBuf<g16::KeyHeaderDev> key_dev;
   g16::DevBuf<g16::ProofSums> sums_dev;

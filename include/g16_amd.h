@@ -305,7 +305,14 @@ void* g16_witness_buffer(g16_ctx* ctx);
  * for a multi-device ctx -- and returns when it is there.  g16_prove_dev(ctx, r, s,
  * g16_witness_buffer(ctx), ...) then proves from the resident copies without moving the witness
  * (the multi-device ctx otherwise peer-broadcasts a device-resident witness from the first device
- * inside every call).                                                                             */
+ * inside every call).
+ * The resident witness is replaced by the calls that take a witness from the HOST -- they stage it in
+ * the same buffer: g16_prove, g16_witness_map, g16_prove_partial, g16_prove_batch / g16_witness_map_batch,
+ * their *_canonical variants (a refused one, value >= r, included) and the two uploads themselves -- and,
+ * on a multi-device ctx, by g16_prove_dev from any other device pointer (the peer broadcast lands there).
+ * No other call replaces it: g16_msm_g1 / g16_msm_g2 stage their host scalars in a buffer of their own
+ * (allocated at the first such call), the other *_dev calls stage nothing, and a call refused for its arguments
+ * (wrong n_vars, too many scalars) touches no device memory.                                            */
 g16_status g16_witness_upload(g16_ctx* ctx, const uint64_t* w, size_t n_vars);
 /* ---- canonical witnesses ----------------------------------------------------------------------------
  * The witness as snarkjs, rapidsnark and circom's C++ calculator write it (.wtns section 2; g16_wtns_values in
